@@ -5,7 +5,7 @@ One "step" = one full RadixHashJoin on device-resident inputs (radix partition o
 relations, plan, count pass, probe/emit pass), i.e. rhj_join_device() of include/rhj.h.
 value = probe-side tuples (nS) of all ranks / wall time, in 10^9 tuples/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|dense]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|dense] [--dump-outputs DIR]
 
 Workloads (synthetic, row_id[i] = i, keys through the splitmix64
 finaliser so all 64 bits are populated):
@@ -172,6 +172,40 @@ def check_properties(R, S, out, m, w, bits=None, fk=True):
         same = kb[1:] == kb[:-1]
         ok = (~same) | (probe[1:] > probe[:-1]) | ((probe[1:] == probe[:-1]) & (build[1:] < build[:-1]))
         assert bool(ok.all()), "pairs out of canonical order inside a bucket (window at %d)" % a
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: all arrays together
+DUMP_PAIRS = 1 << 21           # a pair list longer than this is dumped as a seeded sample of this many pairs (32 MB + 16 MB of positions)
+DUMP_SEED = 20180611
+
+
+def pair_dump(pairs):
+    """--dump-outputs of a pair list as its caller receives it ([m, 2] int64 row ids on the device): the count and the pairs, or
+    beyond DUMP_PAIRS pairs the pairs at DUMP_PAIRS positions drawn with a fixed seed (ascending, with their positions), so that
+    two builds run with the same arguments can be compared pair for pair."""
+    import torch
+    m = int(pairs.shape[0])
+    out = {"pair_count": np.array([m])}
+    if m > DUMP_PAIRS:
+        pos = torch.randint(0, m, (DUMP_PAIRS,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+        pairs = pairs[pos.to(pairs.device)]
+        out["pair_positions"] = pos.numpy()
+    pairs = pairs.cpu().numpy()
+    if m and not (0 <= pairs.min() and pairs.max() < (1 << 53)):
+        raise RuntimeError("--dump-outputs: row ids beyond 2^53 are not exact in float64")
+    out["pairs"] = pairs
+    return out
+
+
+def write_dump(directory, arrays):
+    """DIR/<name>.npy in float64 for every array, at most DUMP_BYTES in all"""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def _cpu_row(o, pyoracle, w, threads, budget_s, start_nR):
@@ -342,6 +376,11 @@ def run_small(args, world, rank, local, dist):
             for i, l in zip(idx, ls):
                 answers[i] = l
         assert answers == g.small["result_lines"], "the merged answers differ from small.result"
+        if args.dump_outputs:               # the sums of a query's answer line in its row; NULL and the unused columns NaN
+            sums = np.full((len(answers), max(len(a.split()) for a in answers)), np.nan)
+            for i, a in enumerate(answers):
+                sums[i, :len(a.split())] = [np.nan if x == "NULL" else float(x) for x in a.split()]
+            write_dump(args.dump_outputs, {"answers": sums})
         res = {"metric": "queries/s on the SIGMOD'18 small workload (persistent engine per rank; batch submission -> last answer)",
                "value": len(queries) * args.steps / elapsed, "unit": "queries/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -407,6 +446,10 @@ def run_smalljoins(args, rhj, world, rank, backend, dist):
     for r, j in zip(res, recs):                            # every rank holds every list (gathered): all of them check
         helpers.assert_digest(o, rhj.pairs_to_numpy(r), j, "small join %d" % j["idx"])
     if rank == 0:
+        if args.dump_outputs:                              # the 88 lists one after the other, and each list's count
+            d = pair_dump(torch.cat(res))
+            d["join_pair_counts"] = np.array([int(r.shape[0]) for r in res])
+            write_dump(args.dump_outputs, d)
         tuples = sum(int(a.shape[0]) + int(b.shape[0]) for a, b in joins)
         load = [sum(int(a.shape[0]) + int(b.shape[0]) for (a, b), ow in zip(joins, owner) if ow == r) for r in range(world)]
         print(json.dumps({"metric": "joins/s on the 88 RadixHashJoin calls of the SIGMOD'18 small workload", "value": len(joins) * args.steps / elapsed,
@@ -457,6 +500,8 @@ def run_strong(args, w, rhj, world, rank, backend, dist):
     if gather:
         check_properties(R, S, full, M, w)                 # canonical order, every S row once, on every rank
     if rank == 0:
+        if args.dump_outputs:                              # (with --no-gather: rank 0's slice of the result)
+            write_dump(args.dump_outputs, pair_dump(full))
         lo, hi = info["range"]
         share = (hi - lo) / float(1 << w["bits"])
         cr, cs = int(w["nR"] * share), int(w["nS"] * share)           # (equal-width ranges of uniform keys)
@@ -500,7 +545,12 @@ def main():
                     help="HIP events inside rhj_join_device during the timed steps: 2 = per stage (default; the roofline's kernel "
                          "times come from them), 1 = whole join, 0 = none.  Below 2 the stage times are collected in a second, "
                          "untimed pass.  Matters for small joins only: an event between two launches costs them ~6 us")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB: "
+                         "a pair list longer than %d pairs as a seeded sample of that many)" % DUMP_PAIRS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -582,6 +632,8 @@ def main():
             acc[k] += st[k]
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                  # before the untimed passes below write `out` again
+        write_dump(args.dump_outputs, pair_dump(out[:m.value]))
     stage_steps = args.steps
     if args.timing < 2:                   # stage times from a second pass with the per-stage events switched on
         rhj.lib.rhj_set_timing(2)
