@@ -76,7 +76,6 @@ struct JoinArgs {
     const uint64_t  *unit_base;      // [units] exclusive scan of unit_count
     rhj_result_tuple*out;
     uint64_t         out_capacity;
-    uint32_t         ablate;         // timing experiments only (RHJ_ABLATE): 1 no gathers, 2 no table reads
     uint32_t         parent_mask;    // low-radix path: bucket & parent_mask = the bucket of the CALLER's radix this sub-bucket belongs to
     const uint8_t   *parent_flip;    // low-radix path: [parent buckets] 1 = S probes; null: every bucket chooses for itself (rhjoin.c:86)
     // tiled path: what the count pass learnt per probe tuple, indexed like the partitioned relations (S behind R): the emit
@@ -110,7 +109,6 @@ __device__ __forceinline__ uint64_t lanemask_lt()
 // to the rows behind them): six register-to-register steps of a few cycles each, where the shuffle form went through
 // the LDS crossbar six times in a row (~100 cycles each) — these scans sit in the latency chains of every kernel here.
 // (Lanes a shift has no source for keep the 0 handed in as `old`; row_bcast:15 / :31 write rows 1,3 / 2,3 only.)
-#ifndef RHJ_SHFL_SCAN
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t x)
 {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);    // row_shr:1
@@ -121,36 +119,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t x)
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);    // row_bcast:31
     return x;
 }
-#else
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t x)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-#endif
 
 __device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t x)
 {
-#ifndef RHJ_SHFL_SCAN
 #define RHJ_DPP64(ctrl, rows)                                                                                   \
     x += ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), ctrl, rows, 0xf, false) << 32) | \
          (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, ctrl, rows, 0xf, false)
     RHJ_DPP64(0x111, 0xf); RHJ_DPP64(0x112, 0xf); RHJ_DPP64(0x114, 0xf); RHJ_DPP64(0x118, 0xf);
     RHJ_DPP64(0x142, 0xa); RHJ_DPP64(0x143, 0xc);
 #undef RHJ_DPP64
-#else
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-#endif
     return x;
 }
 

@@ -76,7 +76,6 @@ struct Ctx {
     int         bits = 4;
     int         null_on_empty = 0;
     int         force_hbm = 0;
-    int         ablate = 0;
     int         order_any = 0;       // 1: pair order not needed, the library picks the radix (env RHJ_ORDER=any, rhj_set_order(1))
     int         no_fused = 0;
     int         force_fused = 0;     // rhj_set_fused(2): the fused path even where the tiled one is expected to be faster (tiny buckets)
@@ -149,7 +148,6 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_RADIX_BITS"))) { int b = atoi(e); if (b >= 1 && b <= 15) g.bits = b; }
         if ((e = getenv("RHJ_EMPTY"))) g.null_on_empty = (strcmp(e, "null") == 0);
         if ((e = getenv("RHJ_FORCE_HBM_TABLE"))) g.force_hbm = atoi(e);
-        if ((e = getenv("RHJ_ABLATE"))) g.ablate = atoi(e);
         if ((e = getenv("RHJ_ORDER"))) g.order_any = (strcmp(e, "any") == 0);
         if ((e = getenv("RHJ_NO_FUSED"))) g.no_fused = atoi(e);
         if ((e = getenv("RHJ_FORCE_FUSED"))) g.force_fused = atoi(e);
@@ -585,7 +583,7 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
     ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p;
     ja.unit_flag = (uint32_t *)g.uflag.p;
     ja.out = nullptr; ja.out_capacity = 0;
-    ja.ablate = (uint32_t)g.ablate; ja.parent_mask = 0; ja.parent_flip = nullptr;
+    ja.parent_mask = 0; ja.parent_flip = nullptr;
     ja.stash_cnt = nullptr; ja.stash_row = nullptr; ja.stash_nR = nR;
 
     // ---- small joins: two launches for the partition (the plan rides in the second), the fused join third, and
@@ -755,7 +753,7 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
             // whole join's size: the per-bucket rule is the same.)
             // (Not on a slice: a bucket cut between two devices has units that start inside it, and the last workgroup's check
             // adds up to the whole relation.)
-            bool try_spec = attempt == 0 && maybe_narrow && out != nullptr && g.no_spec <= 0 && !g.ablate && !sliced &&
+            bool try_spec = attempt == 0 && maybe_narrow && out != nullptr && g.no_spec <= 0 && !sliced &&
                             (nS >= nR ? nS : nR) / bins >= 4096;     // (units of 2.4 K tuples: 10M x 10M at 12 bits lost 7 % to its per-unit extras)
             if (try_spec && g.spec_score <= 0 && g.no_spec >= 0 && ++g.spec_skipped < 16) try_spec = false;   // (RHJ_NO_SPEC=-1: always try — to time a failing one)
             fa.spec = try_spec ? (nS >= nR ? 1u : 2u) : 0u;
@@ -816,7 +814,7 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
                 }
             }
             if (plan.row_id_overflow) { *overflow = true; return 0; }     // (also: wide row ids met the 12-byte kernels alone)
-            if (plan.fused_ok && plan.matches == FJ_NO_TOTAL && !g.ablate) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
+            if (plan.fused_ok && plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
             if (!plan.fused_ok) {
                 // a bucket needs the tiled path, which reads 16-byte tuples: partition again wide if this one was narrow
                 if (bits > PT_MAX_BITS && !force_wide && !plan.wide_row_ids) { *overflow = true; return 0; }
@@ -979,7 +977,7 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
     ja.units = (const Unit *)g.units.p; ja.meta = (const BucketMeta *)g.meta.p; ja.summary = (const PlanSummary *)g.summary.p;
     ja.tab32 = nullptr; ja.tab64 = nullptr;
     ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p; ja.unit_flag = (uint32_t *)g.uflag.p;
-    ja.ablate = 0; ja.parent_mask = (1u << r) - 1u; ja.parent_flip = parent_flip;
+    ja.parent_mask = (1u << r) - 1u; ja.parent_flip = parent_flip;
     ja.stash_cnt = nullptr; ja.stash_row = nullptr; ja.stash_nR = nR;
     FusedArgs fa;
     fa.stash_cnt = (uint8_t *)g.stash_cnt.p; fa.stash_row = (uint64_t *)g.stash_row.p;
@@ -1265,7 +1263,7 @@ static int join_range(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, u
 // The knobs live in the library's own context; the others take them over at the start of every multi-device call.
 static void adopt_knobs(Ctx &d, const Ctx &s)
 {
-    d.bits = s.bits; d.null_on_empty = s.null_on_empty; d.force_hbm = s.force_hbm; d.ablate = s.ablate; d.order_any = s.order_any;
+    d.bits = s.bits; d.null_on_empty = s.null_on_empty; d.force_hbm = s.force_hbm; d.order_any = s.order_any;
     d.no_fused = s.no_fused; d.force_fused = s.force_fused; d.no_resident = s.no_resident; d.wide_row_ids = s.wide_row_ids;
     d.timing = s.timing; d.no_count_in_pass1 = s.no_count_in_pass1; d.no_spec = s.no_spec; d.no_exact = s.no_exact;
     d.lo_override = s.lo_override; d.msd = s.msd; d.no_lowradix = s.no_lowradix; d.no_small = s.no_small; d.small_tiles = s.small_tiles;

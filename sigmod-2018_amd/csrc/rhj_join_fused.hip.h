@@ -41,9 +41,7 @@ constexpr uint32_t FJ_REC_CAP = 512;                  // records (second and lat
 // (fj_walk_group's staging)
 constexpr size_t fj_ovf_bytes(size_t wgs) { return wgs * 2 * (size_t)32768 * 8 + wgs * (size_t)(1024 / 64) * FJ_REC_CAP * 16; }
 constexpr uint32_t FJ_OVF_J = 15;               // match ordinals 1..15 (2nd..16th match) have an overflow slot
-#ifndef FJ_WIN
-#define FJ_WIN 8                                // entries of a slot compared at once (the array is padded by 8)
-#endif
+constexpr int FJ_WIN = 8;                       // entries of a slot compared at once (the array is padded by 8)
 constexpr uint32_t FJ_GROUPS = FJ_SPAN / 256;   // a group = the 256 tuples one wave counts in one batch
 constexpr uint32_t FJ_PATCH_CAP = 128;          // irregular tuples per unit whose match rounds are noted in the overflow buffer's tail
 constexpr uint32_t FJ_OVF_ENT = FJ_OVF_CAP - FJ_PATCH_CAP / 2;   // overflow entries a unit may use (the tail holds the patch words)
@@ -151,23 +149,15 @@ template <bool N32> __device__ __forceinline__ uint4 pt_load(const rhj_tuple *ba
 // A unit's probe tuples are read once: with the nt policy they leave the build sides' lines in the L2s alone — C3 probe stage
 // 1.893 -> 1.869 ms (gpurun_out/r04t/aux_abn.txt; through a descriptor: nt 1.885, sc1 1.909, nt sc1 1.867, sc0 sc1 1.899, sc0 nt
 // 1.879; the PAIR stores with nt: 1.908 -> 1.971, they lose the L2's write combining; the resident kernels — no gathers — gain
-// nothing: C4 5.38 -> 5.42, and keep the default policy).  -DFJ_PROBE_PLAIN: the default policy everywhere (A/B).
+// nothing: C4 5.38 -> 5.42, and keep the default policy).
 template <bool N32> __device__ __forceinline__ uint4 pt_load_nt(const rhj_tuple *base, uint64_t i)
 {
-#ifndef FJ_PROBE_PLAIN
     if (N32) {
         const uint32_t *x = reinterpret_cast<const uint32_t *>(reinterpret_cast<const Tuple12 *>(base) + i);
         return make_uint4(__builtin_nontemporal_load(x), __builtin_nontemporal_load(x + 1), __builtin_nontemporal_load(x + 2), 0u);
     }
-#endif
     return pt_load<N32>(base, i);
 }
-#ifdef FJ_OUT_NT
-typedef uint32_t fj_v4u __attribute__((ext_vector_type(4)));
-#define FJ_STORE_PAIR(ptr, v) do { const uint4 v_ = (v); const fj_v4u w_ = {v_.x, v_.y, v_.z, v_.w}; __builtin_nontemporal_store(w_, reinterpret_cast<fj_v4u *>(ptr)); } while (0)
-#else
-#define FJ_STORE_PAIR(ptr, v) (*(ptr) = (v))
-#endif
 template <bool N32> __device__ __forceinline__ uint2 pt_load_key(const rhj_tuple *base, uint64_t i)
 {
     if (N32) { const Tuple12 *x = reinterpret_cast<const Tuple12 *>(base) + i; return make_uint2(x->klo, x->khi); }
@@ -443,9 +433,7 @@ __device__ __forceinline__ void fj_build(const IX &X, const rhj_tuple *part, uin
 // sc1 (L1 bypass): a gathered line is used once per candidate, so allocating it in the 32 KiB
 // vector L1 only evicts the streamed probe data.  A/B on MI355X (tools/ab.py, fused kernel on
 // 100Mx100M@12): plain 4.64 ms, nt 4.06 ms, sc1 3.8 ms.
-#ifndef FJ_GATHER_AUX
-#define FJ_GATHER_AUX 16   /* sc1 */
-#endif
+constexpr int FJ_GATHER_AUX = 16;   // sc1
 template <bool N32>
 struct FjGather {
     __amdgpu_buffer_rsrc_t rsrc;
@@ -461,29 +449,12 @@ struct FjGather {
     __device__ __forceinline__ uint4 load(uint32_t pos) const
     {
         if (N32) {
-#ifdef FJ_ABL_G8          // timing experiment only (wrong results): 8-byte gathers from a third less memory
-            typedef uint32_t v2 __attribute__((ext_vector_type(2)));
-            const v2 w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(pos * 8u), 0, FJ_GATHER_AUX);
-            return make_uint4(w.x, w.y, w.x, 0u);
-#endif
             typedef uint32_t v3 __attribute__((ext_vector_type(3)));
             const v3 v = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)(pos * 12u), 0, FJ_GATHER_AUX);
             return make_uint4(v.x, v.y, v.z, 0u);
         }
         typedef uint32_t v4 __attribute__((ext_vector_type(4)));
         const v4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pos * 16u), 0, FJ_GATHER_AUX);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    }
-    // the same descriptor for a STREAM (a unit's probe tuples), with the cache policy as a compile-time constant (1 sc0, 2 nt, 16 sc1)
-    template <int AUX> __device__ __forceinline__ uint4 stream(uint32_t pos) const
-    {
-        if (N32) {
-            typedef uint32_t v3 __attribute__((ext_vector_type(3)));
-            const v3 v = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)(pos * 12u), 0, AUX);
-            return make_uint4(v.x, v.y, v.z, 0u);
-        }
-        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-        const v4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pos * 16u), 0, AUX);
         return make_uint4(v.x, v.y, v.z, v.w);
     }
 };
@@ -535,11 +506,7 @@ __device__ __forceinline__ void fj_count_batch(const IX &X, const FjGather<N32> 
         bool ex[FJ_V];
 #pragma unroll
         for (int k = 0; k < FJ_V; ++k) {
-#ifdef FJ_ABL_G8
-            const bool eq = pos[k] != 0xffffffffu && (g[k].x | 1u) != 0u;          // every tag hit counts (timing only)
-#else
             const bool eq = pos[k] != 0xffffffffu && g[k].x == q[k].x && g[k].y == q[k].y;
-#endif
             if (eq && c[k] == 0) { flo[k] = g[k].z; fhi[k] = g[k].w; }
             ex[k] = OVF && eq && c[k] != 0;
             c[k] += eq;
@@ -1020,7 +987,8 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
     uint32_t sn[V], tm[V];
     // (The lane-by-lane loop below picks one of the lane's four tuples by a run-time index.  hipcc turns a select between
     // loads of the caller's array into a load through a selected POINTER — and the array into 64 bytes of scratch per lane;
-    // values that come out of an (empty) asm statement are not loads any more.)
+    // values that come out of an (empty) asm statement are not loads any more.  qz is not read; pinning it keeps this kernel's
+    // schedule as measured.)
     uint32_t qx[V], qy[V], qz[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
@@ -1041,11 +1009,7 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
         for (int k = 0; k < V; ++k) g[k] = pos[k] != 0xffffffffu ? G.load(pos[k]) : make_uint4(0, 0, 0, 0);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-#ifdef FJ_ABL_G8
-            const bool eq = pos[k] != 0xffffffffu;
-#else
             const bool eq = pos[k] != 0xffffffffu && g[k].x == q[k].x && g[k].y == q[k].y;
-#endif
             first[k] = eq ? g[k].z : 0u;
             c[k] = eq ? 1u : 0u;
         }
@@ -1053,11 +1017,9 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
     uint32_t ne = 0;                                   // records of this group so far (wave-uniform)
     // FJ_SER candidates a lane and step: which candidates a lane walks is a matter of the index alone (LDS), so their gathers are
     // issued together and verified in order afterwards — the chain of a group is steps x one gather latency
-#ifndef FJ_SER
-#define FJ_SER 1                                   // (2 and 3 measured the same on C3: it is not this chain that sets the pace)
-#endif
+    constexpr int FJ_SER = 1;                          // (2 and 3 measured the same on C3: it is not this chain that sets the pace)
     for (;;) {
-        uint32_t ks[FJ_SER], kx[FJ_SER], ky[FJ_SER], pr[FJ_SER], p[FJ_SER];
+        uint32_t ks[FJ_SER], kx[FJ_SER], ky[FJ_SER], p[FJ_SER];
 #pragma unroll
         for (int j = 0; j < FJ_SER; ++j) {
             ks[j] = V;                                 // the first of the lane's tuples with a candidate left
@@ -1065,10 +1027,10 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
             for (int k = V - 1; k >= 0; --k)
                 if ((tm[k] & 0xffu) != 0 || (sn[k] >> 16) > (uint32_t)FJ_WIN) ks[j] = (uint32_t)k;
             uint32_t s_ = sn[0], t_ = tm[0];
-            kx[j] = qx[0]; ky[j] = qy[0]; pr[j] = qz[0];
+            kx[j] = qx[0]; ky[j] = qy[0];
 #pragma unroll
             for (int k = 1; k < V; ++k)
-                if (ks[j] == (uint32_t)k) { s_ = sn[k]; t_ = tm[k]; kx[j] = qx[k]; ky[j] = qy[k]; pr[j] = qz[k]; }
+                if (ks[j] == (uint32_t)k) { s_ = sn[k]; t_ = tm[k]; kx[j] = qx[k]; ky[j] = qy[k]; }
             p[j] = 0xffffffffu;
             if (ks[j] < (uint32_t)V) {
                 if ((t_ & 0xffu) == 0) {               // the window is used up and the slot goes on
@@ -1083,9 +1045,6 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
                 if (ks[j] == (uint32_t)k) { sn[k] = s_; tm[k] = t_; }
         }
         if (__ballot(ks[0] < (uint32_t)V) == 0) break;
-#ifdef FJ_ABL_NOSER          // timing experiment only (wrong results): second and later candidates are not fetched
-        continue;
-#endif
         uint4 g[FJ_SER];
 #pragma unroll
         for (int j = 0; j < FJ_SER; ++j) g[j] = p[j] != 0xffffffffu ? G.load(p[j]) : make_uint4(0, 0, 0, 0);
@@ -1094,21 +1053,11 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
             uint32_t cc = c[0];
 #pragma unroll
             for (int k = 1; k < V; ++k) if (ks[j] == (uint32_t)k) cc = c[k];
-#ifdef FJ_ABL_G8
-            const bool eq = p[j] != 0xffffffffu && (g[j].x | kx[j] | ky[j] | 1u) != 0u;     // (timing only: every tag hit counts)
-#else
             const bool eq = p[j] != 0xffffffffu && g[j].x == kx[j] && g[j].y == ky[j];
-#endif
             const bool isrec = eq && cc != 0;
             const uint64_t mk = __ballot(isrec);
             const uint32_t slot = ne + (uint32_t)__popcll(mk & lt);
-#ifndef FJ_ABL_NOREC      // (timing experiment only, wrong results: second and later matches are found but leave no record and no pair)
-#ifndef FJ_REC16
             if (isrec && slot < FJ_REC_CAP) reinterpret_cast<uint2 *>(rec)[slot] = make_uint2(g[j].z, (ks[j] * WAVE + lane) | (cc << 8));
-#else
-            if (isrec && slot < FJ_REC_CAP) rec[slot] = make_uint4(g[j].z, pr[j], (ks[j] * WAVE + lane) | (cc << 8), 0u);
-#endif
-#endif
             ne += (uint32_t)__popcll(mk);
             cannot = cannot || (eq && cc >= 65535u);   // (the ordinal has sixteen bits)
 #pragma unroll
@@ -1117,9 +1066,6 @@ __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N3
         }
     }
     cannot = cannot || ne > FJ_REC_CAP;
-#ifdef FJ_ABL_NOREC
-    return 0;
-#endif
     return min(ne, FJ_REC_CAP);
 }
 
@@ -1129,11 +1075,10 @@ __device__ __forceinline__ void fj_emit_records(bool flip, const uint4 *rec, uin
 {
     constexpr int V = FJ_V;
     const uint32_t lane = threadIdx.x & 63;
-    (void)q;
     for (uint32_t e0 = 0; e0 < nrec; e0 += WAVE) {
         const uint32_t e = e0 + lane;
-#ifndef FJ_REC16          // 8-byte records {build row id, tuple | ordinal}: the probe row id comes from the lane that holds the tuple (16-byte
-                         // records with the probe row id in them, -DFJ_REC16: C3 probe stage 1.837 -> 1.883 ms)
+        // 8-byte records {build row id, tuple | ordinal}: the probe row id comes from the lane that holds the tuple (16-byte
+        // records with the probe row id in them: C3 probe stage 1.837 -> 1.883 ms)
         const uint2 r8 = e < nrec ? reinterpret_cast<const uint2 *>(rec)[e] : make_uint2(0, 0);
         uint4 r = make_uint4(r8.x, 0u, r8.y, 0u);
         {
@@ -1143,16 +1088,13 @@ __device__ __forceinline__ void fj_emit_records(bool flip, const uint4 *rec, uin
 #pragma unroll
             for (int k = 1; k < V; ++k) { const uint32_t pk = __shfl(q[k].z, s8, 64); if (k8 == (uint32_t)k) r.y = pk; }
         }
-#else
-        const uint4 r = e < nrec ? rec[e] : make_uint4(0, 0, 0, 0);
-#endif
         const int src = (int)(r.z & 63u);
         const uint32_t kk = (r.z >> 6) & 3u;
         uint32_t o = __shfl(off[0], src, 64);
 #pragma unroll
         for (int k = 1; k < V; ++k) { const uint32_t ok_ = __shfl(off[k], src, 64); if (kk == (uint32_t)k) o = ok_; }
         const uint64_t at = wbase + o + (r.z >> 8);
-        if (e < nrec && at < cap) FJ_STORE_PAIR(&out[at], make_pair(flip, r.y, 0u, r.x, 0u));
+        if (e < nrec && at < cap) out[at] = make_pair(flip, r.y, 0u, r.x, 0u);
     }
 }
 
@@ -1174,15 +1116,11 @@ __device__ __forceinline__ uint32_t fj_group_direct(const IX &X, const FjGather<
         wrun += tot;
         cs += c[k];
     }
-#ifdef FJ_ABL_NOLB           // timing experiment only (wrong results): no chained scan, every group writes at its own 256 slots
-    const uint64_t wbase = spec_base + (uint64_t)grp * 256u;
-#else
     const uint64_t wbase = spec_base + fj_group_lookback(gpre, grp, wrun, lane);
-#endif
 #pragma unroll
     for (int k = 0; k < V; ++k) {
         const uint64_t at = wbase + off[k];
-        if (c[k] != 0 && at < cap) FJ_STORE_PAIR(&out[at], make_pair(flip, q[k].z, 0u, first[k], 0u));
+        if (c[k] != 0 && at < cap) out[at] = make_pair(flip, q[k].z, 0u, first[k], 0u);
     }
     fj_emit_records(flip, rec, nrec, off, wbase, out, cap, q);
     return cs;
@@ -1194,14 +1132,12 @@ __device__ __forceinline__ uint32_t fj_group_direct(const IX &X, const FjGather<
 // not need its index any more (no probe tuple with two or more matches: the foreign-key case) is
 // DEFERRED behind the next unit's build + phase 1: by then its output base has long been published,
 // so such units never wait on the chain (the wait was 18 % of a unit in the in-kernel stamps).
-// Diagnostics of the fused kernel (in-kernel phase stamps, RHJ_STAMPS; parts switched off, RHJ_ABLATE)
-// are compiled in only with -DRHJ_INSTRUMENT (tools/): the production kernel carries no trace of them.
+// Diagnostics of the fused kernel (in-kernel phase stamps, RHJ_STAMPS) are compiled in only with -DRHJ_INSTRUMENT (tools/):
+// the production kernel carries no trace of them.
 #ifdef RHJ_INSTRUMENT
 #define FJ_DBG (f.dbg)
-#define FJ_ABLATE (a.ablate)
 #else
 #define FJ_DBG ((uint64_t *)nullptr)
-#define FJ_ABLATE 0u
 #endif
 // The whole body is a device function: k_join_fused runs it over units a host-launched plan wrote, k_small_join
 // (rhj_small.hip.h) as the last phase of its single launch.
@@ -1229,7 +1165,7 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     unsigned long long *st = (unsigned long long *)f.status;
     uint4 *out = reinterpret_cast<uint4 *>(a.out);
-    const bool emitting = out != nullptr && FJ_ABLATE != 3;
+    const bool emitting = out != nullptr;
     if ((a.summary->wide_row_ids == 0) != N32) return;                 // the other instantiation's launch does the join
     uint4 *stg = reinterpret_cast<uint4 *>(f.ovf + (size_t)gridDim.x * 2 * FJ_OVF_CAP) + ((size_t)blockIdx.x * FJ_WAVES + w) * FJ_REC_CAP;   // this wave's piece
     uint32_t pend = 0xffffffffu;                      // unit whose emit pass is deferred
@@ -1290,10 +1226,6 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
     uint2 *srow = reinterpret_cast<uint2 *>(f.stash_row + (flip ? f.nR : 0) + ppos);
     FjGather<N32> G;
     G.init(bdp, bpos, bc);
-#ifdef FJ_PROBE_AUX
-    FjGather<N32> PS;                                 // (A/B: the unit's probe tuples through a descriptor, policy FJ_PROBE_AUX)
-    PS.init(prp, ppos, un.count);
-#endif
     FjOvf O;                                          // double-buffered: the previous unit's emit may still be pending
     O.buf = f.ovf + ((size_t)blockIdx.x * 2 + (iter & 1u)) * FJ_OVF_CAP;
     O.table = f.ovf_base + ((size_t)blockIdx.x * 2 + (iter & 1u)) * (FJ_GROUPS * 16u);
@@ -1304,7 +1236,6 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
     // ---- build
     if (RES) fj_build<true, N32>(X, bdp, bpos, bc, ltup, reinterpret_cast<uint32_t *>(O.buf), wsum, &sh_pick);
     else     fj_build<false, N32>(X, bdp, bpos, bc, ltup, reinterpret_cast<uint32_t *>(O.buf), wsum, &sh_pick, SPEC && !MAYRES && fkp);
-    if (FJ_ABLATE == 1) continue;                      // timing experiment: build only
     if (FJ_DBG && threadIdx.x == 0) FJ_DBG[(size_t)u * 8 + 1] = __builtin_amdgcn_s_memrealtime();
 
     // ---- phase 1: count (+ stash of the first match when the build tuples are not resident)
@@ -1328,11 +1259,7 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
         for (int k = 0; k < FJ_V; ++k) {
             const uint32_t i = t0 + k * WAVE + lane;
             okk[k] = i < un.count;
-#ifdef FJ_PROBE_AUX
-            q[k] = okk[k] ? PS.template stream<FJ_PROBE_AUX>(i) : make_uint4(0, 0, 0, 0);
-#else
             q[k] = okk[k] ? (MAYRES ? pt_load<N32>(prp, ppos + i) : pt_load_nt<N32>(prp, ppos + i)) : make_uint4(0, 0, 0, 0);   // (nt: the gather kernels only)
-#endif
         }
         O.gid = grp;
         uint32_t run[FJ_V], bm[FJ_V];
@@ -1353,11 +1280,11 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
             for (int k = 0; k < FJ_V; ++k) {
                 const uint32_t i = t0 + k * WAVE + lane;
                 if (i < un.count) {
-#if !defined(FJ_FLOOR) && !defined(FJ_ABL_G8)
+#ifndef FJ_FLOOR
                     spec_bad = spec_bad || c[k] != 1u;
 #endif
                     const uint64_t at = spec_base + i;
-                    if (at < a.out_capacity) FJ_STORE_PAIR(&out[at], make_pair(flip, q[k].z, N32 ? 0u : q[k].w, flo[k], fhi[k]));
+                    if (at < a.out_capacity) out[at] = make_pair(flip, q[k].z, N32 ? 0u : q[k].w, flo[k], fhi[k]);
                 }
             }
             if (__ballot(spec_bad) != 0) {            // noticed at once, and by everybody
@@ -1418,11 +1345,7 @@ __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
 #pragma unroll
     for (int i = 0; i < FJ_WAVES; ++i) total += wsum[i];
     if (SPEC) {                                       // the other relation probes: the usual unit at the predicted base, emitted at once
-#if defined(FJ_ABL_NOSER) || defined(FJ_ABL_G8)
-        if (false) {
-#else
-        if (total != spec_total) {
-#endif   // (workgroup-uniform)
+        if (total != spec_total) {   // (workgroup-uniform)
             if (threadIdx.x == 0) __hip_atomic_store(f.ticket + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
@@ -1536,7 +1459,7 @@ __global__ __launch_bounds__(FJ_BLOCK) void k_join_spec(FusedArgs f, uint32_t ld
         const uint32_t last = (1u << f.radix_bits) - 1u;
         const uint64_t n_fk = f.spec == 1u ? f.j.psumS[last] + f.j.histS[last] : f.j.psumR[last] + f.j.histR[last];
         bool failed = __hip_atomic_load(f.ticket + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || predicted != n_fk;
-#if defined(FJ_FLOOR) || defined(FJ_ABL_G8)
+#ifdef FJ_FLOOR
         failed = false;
 #endif
         if (failed) {                                 // the ordinary kernel behind this one starts over
@@ -1632,10 +1555,6 @@ __device__ __forceinline__ void fj_walk_unit(const FusedArgs &f, uint32_t lds_by
     const uint2 *srow = reinterpret_cast<const uint2 *>(f.stash_row + (flip ? f.nR : 0) + ppos);
     FjGather<N32> G;
     G.init(bdp, bpos, bc);
-#ifdef FJ_PROBE_AUX
-    FjGather<N32> PS;                                 // (A/B: the unit's probe tuples through a descriptor, policy FJ_PROBE_AUX)
-    PS.init(prp, ppos, un.count);
-#endif
     __syncthreads();                                  // the previous unit's index is no longer read
     fj_build<RES, N32>(X, bdp, bpos, bc, ltup, reinterpret_cast<uint32_t *>(f.ovf + (size_t)blockIdx.x * 2 * FJ_OVF_CAP), wsum, sh_pick);
     __syncthreads();

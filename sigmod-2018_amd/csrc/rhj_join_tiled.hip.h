@@ -11,9 +11,7 @@ namespace rhj {
 constexpr int PR_BLOCK = 256;                     // probe workgroup
 constexpr int PR_V = 4;                           // probe tuples per thread
 constexpr int PR_UNIT = PR_BLOCK * PR_V;          // 2048 probe tuples per unit
-#ifndef PR_MINW
-#define PR_MINW 5                                 // waves per SIMD the probe kernels are compiled for (96 VGPRs)
-#endif
+constexpr int PR_MINW = 5;                        // waves per SIMD the probe kernels are compiled for (96 VGPRs)
 
 struct PlanArgs {
     const uint64_t *histR, *histS;
@@ -390,7 +388,7 @@ __device__ __forceinline__ void probe_unit(const JoinArgs &a, const Table &T, co
     const uint4 *pr4 = reinterpret_cast<const uint4 *>(pr);
     const uint4 *bd4 = reinterpret_cast<const uint4 *>(bd);
     const uint2 *bd2 = reinterpret_cast<const uint2 *>(bd);
-    const bool exact = WRITE ? a.unit_flag[u] != 0 : a.ablate == 0;      // verify candidates?
+    const bool exact = WRITE ? a.unit_flag[u] != 0 : true;      // verify candidates?
 
     uint4 q[PR_V];
     bool ok[PR_V];
@@ -415,7 +413,7 @@ __device__ __forceinline__ void probe_unit(const JoinArgs &a, const Table &T, co
         const uint64_t h = mix64(((uint64_t)q[k].y << 32) | q[k].x);
         s0[k] = T.home(h);
         tg[k] = T.tag(h);
-        if (ok[k] && a.ablate != 2 && !stashed[k]) T.load_chunk(s0[k], e[k]);
+        if (ok[k] && !stashed[k]) T.load_chunk(s0[k], e[k]);
         else {
 #pragma unroll
             for (int j = 0; j < CH; ++j) e[k][j] = 0;

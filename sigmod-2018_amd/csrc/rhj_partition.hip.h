@@ -295,10 +295,7 @@ __global__ __launch_bounds__(1024) void k_rowid_sample(RelArgs r0, RelArgs r1, i
 // (radix bits 13..15: the cells would cost the second resident workgroup) k_hist_runs counts from the digit bytes, which
 // cost 0.15 ms on 100M + 100M tuples — as many LDS atomics, but in a kernel that does nothing else.
 // DIG: the next pass' digit of every tuple as one byte (k_hist_runs and the low-radix emit read them).
-#ifndef PT_STRIP_N
-#define PT_STRIP_N 4
-#endif
-constexpr uint32_t PT_STRIP = PT_STRIP_N;           // tiles a strip, at most (16-bit cells: 15 is the limit; RelArgs::strip: fewer for small inputs)
+constexpr uint32_t PT_STRIP = 4;                    // tiles a strip, at most (16-bit cells: 15 is the limit; RelArgs::strip: fewer for small inputs)
 // COL (rhj_join_keys_device): the input is a KEY COLUMN — 8 bytes a tuple, the row id is the position (what GetRelation makes of
 // a base relation: {col[i], i}, inter_res.c:199-204) — instead of the ABI's 16-byte tuples: pass 1 reads half the bytes.
 template <bool RANGED, bool H2, bool DIG, bool COL = false>
@@ -753,13 +750,8 @@ __global__ __launch_bounds__(1024) void k_bucket_psum(int bits1, int bits, const
 // T12: 12-byte intermediates in; O12: 12-byte tuples out too (the join's own partition when the row ids fit 32 bits:
 // the fused kernel then streams and gathers 12 instead of 16 bytes per tuple; rhj_partition_device() hands out
 // rhj_tuple and keeps 16-byte output).  (A run-time switch here cost 30 %: compiled apart, launched side by side.)
-#ifndef SR_VN
-#define SR_VN 8         // tuples per thread and batch of pass 2 (the batch is independent of pass 1's 4096-tuple tiles)
-#endif
-#ifndef SR_MINW
-#define SR_MINW 4
-#endif
-constexpr int SR_V = SR_VN;
+constexpr int SR_V = 8;          // tuples per thread and batch of pass 2 (the batch is independent of pass 1's 4096-tuple tiles)
+constexpr int SR_MINW = 4;
 constexpr int SR_TILE = PT_BLOCK * SR_V;
 constexpr uint32_t SR_RUNOFF = PT_MAX_GROUP + 8;  // run-start table of a pass-2 tile: entries behind the last run hold the tile's total
 #ifdef RHJ_INSTRUMENT
@@ -768,16 +760,6 @@ __device__ uint64_t g_sr_dbg[256 * 16];           // diagnostics build: phase st
 #else
 #define SR_STAMP(slot) do { } while (0)
 #endif
-#ifndef SR_AOS
-#define SR_AOS 0        // A/B only: 1 = 12-byte tuples staged in 16-byte slots
-#endif
-#ifndef SR_NOSHFL
-#define SR_NOSHFL 1
-#endif
-#ifndef SR_PIPE
-#define SR_PIPE 1       // 1: the next batch's tuple loads are issued before the current batch is written out (0: the round-2 loop, for A/B)
-#endif
-#if SR_PIPE
 // A batch of a pass-2 tile costs a workgroup a chain of dependent steps; in-kernel stamps of the round-2 loop (r03, 10.6 us
 // per batch, two workgroups per CU): ranks 2.4 us, staging 1.2, run table of the next tile 1.3, run search + load issue 1.8,
 // write-out 2.1, barriers 1.5 — with the loads and stores switched off the kernel still took 0.52 of its 0.70 ms per 100 M
@@ -923,17 +905,10 @@ __global__ __launch_bounds__(PT_BLOCK, SR_MINW) void k_scatter_runs(RelArgs r0, 
             const uint32_t d = (uint32_t)(key >> shift) & mask;
             const uint64_t peers = digit_peers(d, ok, bits);
             const uint32_t rank = (uint32_t)__popcll(peers & lt);
-#if SR_NOSHFL
             // the whole digit group reads its counter, then its lowest lane adds the group (a wave's LDS operations complete in
             // order; one lane per counter writes: no ordering between lanes is relied on) — no shuffle from the leader
             const uint32_t old = mycnt[d];
             if (ok && rank == 0) mycnt[d] = old + (uint32_t)__popcll(peers);
-#else
-            uint32_t old = 0;
-            if (ok && rank == 0) { old = mycnt[d]; mycnt[d] = old + (uint32_t)__popcll(peers); }   // lowest lane of each digit group
-            const int leader = ok ? __ffsll((unsigned long long)peers) - 1 : 0;
-            old = __shfl(old, leader, 64);
-#endif
             rk[k] = (old + rank) | (d << 16);
         }
         SR_STAMP(2);
@@ -972,7 +947,7 @@ __global__ __launch_bounds__(PT_BLOCK, SR_MINW) void k_scatter_runs(RelArgs r0, 
             if (w * (WAVE * SR_V) + k * WAVE + lane < count) {
                 const uint32_t d = rk[k] >> 16;
                 const uint32_t p = dstart[d] + mycnt[d] + (rk[k] & 0xffffu);
-                if (T12 && !SR_AOS) { s_klo[p] = tk[k]; s_khi[p] = th[k]; s_rid[p] = tr[k]; }
+                if (T12) { s_klo[p] = tk[k]; s_khi[p] = th[k]; s_rid[p] = tr[k]; }
                 else stage[p] = make_uint4(tk[k], th[k], tr[k], tw[k]);
             }
         }
@@ -1014,7 +989,7 @@ __global__ __launch_bounds__(PT_BLOCK, SR_MINW) void k_scatter_runs(RelArgs r0, 
             const uint32_t p = k * PT_BLOCK + threadIdx.x;
             if (p < wcount) {
                 uint4 v;
-                if (T12 && !SR_AOS) v = make_uint4(s_klo[p], s_khi[p], s_rid[p], 0u);
+                if (T12) v = make_uint4(s_klo[p], s_khi[p], s_rid[p], 0u);
                 else v = stage[p];
                 const uint32_t d = (uint32_t)((((uint64_t)v.y << 32) | v.x) >> shift) & mask;
                 if (O12) reinterpret_cast<Tuple12 *>(r.out)[delta[d] + p] = Tuple12{v.x, v.y, v.z};
@@ -1025,157 +1000,5 @@ __global__ __launch_bounds__(PT_BLOCK, SR_MINW) void k_scatter_runs(RelArgs r0, 
         SR_STAMP(9);
     }
 }
-#else
-template <bool T12, bool O12>
-__global__ __launch_bounds__(PT_BLOCK, SR_MINW) void k_scatter_runs(RelArgs r0, RelArgs r1, int shift, int bits, uint32_t search0,
-                                                           const PlanSummary *summary)
-{
-    if ((summary->wide_row_ids == 0) != T12) return;      // the other instantiation's launch moves the data
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint4    *stage = reinterpret_cast<uint4 *>(smem);                        // [SR_TILE]
-    uint32_t *wcnt = reinterpret_cast<uint32_t *>(smem + (size_t)SR_TILE * 16); // [PT_WAVES][bins]
-    const uint32_t bins = 1u << bits, mask = bins - 1u;
-    uint32_t *dstart = wcnt + PT_WAVES * bins;                                 // [bins]
-    uint32_t *delta = dstart + bins;                                           // [bins]
-    uint64_t *sm = reinterpret_cast<uint64_t *>(delta + bins);                 // scan scratch [PT_BLOCK / 64 + 1]
-    uint32_t *gbase = reinterpret_cast<uint32_t *>(sm + PT_BLOCK / 64 + 2);    // [bins] next output position per digit
-    uint32_t *runoff = gbase + bins;                                           // [PT_MAX_GROUP + 1] first element of run i
-    uint32_t *rbase = runoff + PT_MAX_GROUP + 1;                               // [PT_MAX_GROUP] physical index of element e of run i = rbase[i] + e
-
-    const RelArgs &r = blockIdx.y ? r1 : r0;
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t lt = lanemask_lt();
-    const uint4 *in = reinterpret_cast<const uint4 *>(r.in);
-    uint4 *out = reinterpret_cast<uint4 *>(r.out);
-
-    // Workgroups are dispatched round-robin over the 8 XCDs (blockIdx.x % 8), each with its own L2.
-    // Consecutive pass-2 tiles write ADJACENT pieces of every digit's output, so the cache line at the
-    // seam is completed by the neighbour tile: the tiles are dealt to the XCDs in blocks of as many
-    // consecutive tiles as an XCD has workgroups, which walk the block together — both halves of a seam
-    // line meet in the same L2 and leave as one full-line write (-6 % against a plain grid stride) — and
-    // the blocks go round-robin over the XCDs, so that the oversized tiles of a hot digit (Zipf keys) are
-    // shared by all of them (-5 % on 100M x 1B against one contiguous eighth per XCD; same on uniform
-    // keys).  The next tile's run table and output offsets are fetched while the current tile is moved.
-    const uint32_t xcd = blockIdx.x & 7u, per_xcd = gridDim.x >> 3;           // gridDim.x is a multiple of 8
-    const uint32_t slot = blockIdx.x >> 3;
-    const uint32_t tstep = 8u * per_xcd;                                        // the next block of this XCD
-    const uint32_t t_end = r.tiles;
-    const uint32_t t_first = xcd * per_xcd + slot;
-    uint32_t nphys = 0, nlen = 0, ngb = 0;
-    if (t_first < t_end) {
-        pt_run_of(r, t_first, threadIdx.x, nphys, nlen);
-        if (threadIdx.x < bins) ngb = pt_start(r, t_first, threadIdx.x, bins);
-    }
-    for (uint32_t tile2 = t_first; tile2 < t_end; tile2 += tstep) {
-    uint32_t total;
-    {
-        const uint32_t phys = nphys, len = nlen;
-        uint64_t tot64;
-        const uint32_t off = (uint32_t)block_excl_scan<PT_BLOCK>(len, &tot64, sm);
-        total = (uint32_t)tot64;
-        if (threadIdx.x < PT_MAX_GROUP) { runoff[threadIdx.x] = threadIdx.x < r.group ? off : total; rbase[threadIdx.x] = phys - off; }
-        if (threadIdx.x == 0) runoff[PT_MAX_GROUP] = total;
-        if (threadIdx.x < bins) gbase[threadIdx.x] = ngb;
-        const uint32_t nt = tile2 + tstep;
-        nphys = 0; nlen = 0;
-        if (nt < t_end) {
-            pt_run_of(r, nt, threadIdx.x, nphys, nlen);
-            if (threadIdx.x < bins) ngb = pt_start(r, nt, threadIdx.x, bins);
-        }
-    }
-    __syncthreads();
-
-    for (uint32_t sb = 0; sb < total; sb += SR_TILE) {
-        const uint32_t count = min((uint32_t)SR_TILE, total - sb);
-        for (uint32_t i = threadIdx.x; i < PT_WAVES * bins; i += PT_BLOCK) wcnt[i] = 0;
-
-        uint4 t[SR_V];
-        bool ok[SR_V];
-        uint32_t pos = 0;                             // last run that starts at or before the element
-#pragma unroll
-        for (int k = 0; k < SR_V; ++k) {
-            const uint32_t i = w * (WAVE * SR_V) + k * WAVE + lane;
-            ok[k] = i < count;
-            const uint32_t e = sb + i;
-            if (k == 0) {
-                for (uint32_t s2 = search0; s2 >= 1; s2 >>= 1)
-                    if (runoff[pos + s2] <= e) pos += s2;
-            } else {
-                // 64 elements further on: usually the next run or the one after it
-                if (runoff[pos + 1] <= e) ++pos;
-                if (runoff[pos + 1] <= e) ++pos;
-                if (runoff[pos + 1] <= e) {           // short or empty runs in between: search again
-                    pos = 0;
-                    for (uint32_t s2 = search0; s2 >= 1; s2 >>= 1)
-                        if (runoff[pos + s2] <= e) pos += s2;
-                }
-            }
-            if (ok[k]) {
-                if (T12) { const Tuple12 x = reinterpret_cast<const Tuple12 *>(r.in)[rbase[pos] + e]; t[k] = make_uint4(x.klo, x.khi, x.rid, 0u); }
-                else t[k] = in[rbase[pos] + e];
-            }
-        }
-        __syncthreads();
-
-        uint32_t lrank[SR_V], dig[SR_V];
-        uint32_t *mycnt = wcnt + w * bins;
-#pragma unroll
-        for (int k = 0; k < SR_V; ++k) {
-            const uint64_t key = ((uint64_t)t[k].y << 32) | t[k].x;
-            const uint32_t d = (uint32_t)(key >> shift) & mask;
-            dig[k] = d;
-            const uint64_t peers = digit_peers(d, ok[k], bits);
-            const uint32_t rank = (uint32_t)__popcll(peers & lt);
-            uint32_t old = 0;
-            if (ok[k] && rank == 0) {
-                old = mycnt[d];
-                mycnt[d] = old + (uint32_t)__popcll(peers);
-            }
-            const int leader = ok[k] ? __ffsll((unsigned long long)peers) - 1 : 0;
-            old = __shfl(old, leader, 64);
-            lrank[k] = old + rank;
-        }
-        __syncthreads();
-
-        uint64_t mytotal = 0;
-        if (threadIdx.x < bins) {
-            uint32_t run = 0;
-            for (int ww = 0; ww < PT_WAVES; ++ww) {
-                const uint32_t c = wcnt[ww * bins + threadIdx.x];
-                wcnt[ww * bins + threadIdx.x] = run;
-                run += c;
-            }
-            mytotal = run;
-        }
-        const uint64_t ds = block_excl_scan<PT_BLOCK>(mytotal, nullptr, sm);
-        if (threadIdx.x < bins) {
-            dstart[threadIdx.x] = (uint32_t)ds;
-            const uint32_t gb = gbase[threadIdx.x];
-            delta[threadIdx.x] = gb - (uint32_t)ds;                 // mod 2^32
-            gbase[threadIdx.x] = gb + (uint32_t)mytotal;
-        }
-        __syncthreads();
-
-#pragma unroll
-        for (int k = 0; k < SR_V; ++k)
-            if (ok[k]) stage[dstart[dig[k]] + mycnt[dig[k]] + lrank[k]] = t[k];
-        __syncthreads();
-
-#pragma unroll
-        for (int k = 0; k < SR_V; ++k) {
-            const uint32_t p = k * PT_BLOCK + threadIdx.x;
-            if (p < count) {
-                const uint4 v = stage[p];
-                const uint32_t d = (uint32_t)((((uint64_t)v.y << 32) | v.x) >> shift) & mask;
-                if (O12) reinterpret_cast<Tuple12 *>(r.out)[delta[d] + p] = Tuple12{v.x, v.y, v.z};
-                else out[delta[d] + p] = v;
-            }
-        }
-        __syncthreads();
-    }
-    }   // grid-stride loop
-}
-
-#endif
 
 }  // namespace rhj

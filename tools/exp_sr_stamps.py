@@ -1,4 +1,4 @@
-"""Phase stamps of pass 2 (k_scatter_runs, diagnostics build): python tools/exp_sr_stamps.py [n] [bits]   (RHJ_LIB=.../librhj_instr.so)
+"""Phase stamps of pass 2 (k_scatter_runs, diagnostics build): python tools/exp_sr_stamps.py [n] [bits]   (RHJ_LIB=sigmod-2018_amd/build/librhj_instr.so)
 slots: 0 loop top | 1 after barrier (loads landed? no: counters zero) | 2 ranks done | 3 barrier | 4 digit prefixes + barrier | 5 staged |
 6 next run table | 7 barrier | 8 next loads issued | 9 written out + counters zeroed"""
 import importlib, ctypes as C, torch, sys, json

@@ -4,7 +4,7 @@ import numpy as np
 sys.path.insert(0, ".")
 import bench
 os.environ["RHJ_STAMPS"] = "1"
-os.environ.setdefault("RHJ_LIB", os.path.join("sigmod-2018_amd", "librhj_instr.so"))
+os.environ.setdefault("RHJ_LIB", os.path.join("sigmod-2018_amd", "build", "librhj_instr.so"))
 mod = importlib.import_module("sigmod-2018_amd"); rhj = mod.RHJ(device=0)
 nR, nS = [int(x) for x in sys.argv[1:3]]
 bits = int(sys.argv[3]) if len(sys.argv) > 3 else 12

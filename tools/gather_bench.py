@@ -4,7 +4,7 @@ region.  Needs the diagnostics build (make -C sigmod-2018_amd instr).  Prints G 
 L2-resident to C3's 24.4 K tuples per workgroup, with and without a probe-like stream next to the gathers."""
 import ctypes as C, importlib, json, os, sys
 sys.path.insert(0, ".")
-os.environ.setdefault("RHJ_LIB", os.path.join("sigmod-2018_amd", "librhj_instr.so"))
+os.environ.setdefault("RHJ_LIB", os.path.join("sigmod-2018_amd", "build", "librhj_instr.so"))
 mod = importlib.import_module("sigmod-2018_amd"); rhj = mod.RHJ(device=0)
 f = rhj.lib.rhj_debug_gather_bench
 f.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]

@@ -1,10 +1,13 @@
 #!/bin/bash
-# kernel-trace stats for several library variants: tools/prof_kern.sh <outdir> <pattern> <bench args...> ; variants from $RHJ_VARIANTS (space separated lib names)
+# kernel-trace stats for several library variants: tools/prof_kern.sh <outdir> <pattern> <bench args...> ; variants from $RHJ_VARIANTS (space
+# separated lib names: librhj.so is the package's library, the others are `make variant` builds under sigmod-2018_amd/build/)
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=gpurun_out/$1; pat=$2; shift 2
 mkdir -p $out
 for v in $RHJ_VARIANTS; do
-  lib=$GRAFT_REPO_ROOT/sigmod-2018_amd/$v
-  ( cd /tmp && export TMPDIR=/tmp RHJ_LIB=$lib && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/$v -- python3 $GRAFT_REPO_ROOT/bench.py "$@" --no-cpu-baseline > $GRAFT_REPO_ROOT/$out/$v.json 2> $GRAFT_REPO_ROOT/$out/$v.err )
+  lib=$root/sigmod-2018_amd/build/$v
+  [ "$v" = librhj.so ] && lib=$root/sigmod-2018_amd/librhj.so
+  ( cd /tmp && export TMPDIR=/tmp RHJ_LIB=$lib && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/$v -- python3 $root/bench.py "$@" --no-cpu-baseline > $root/$out/$v.json 2> $root/$out/$v.err )
   f=$(find $out/$v -name "*kernel_stats.csv" | head -1)
   echo "== $v"
   python3 - <<PY

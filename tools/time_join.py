@@ -1,5 +1,6 @@
 """Stage times of rhj_join_device on a synthetic FK join WITHOUT checking the result (timing experiments with builds
-whose results are wrong on purpose): python tools/time_join.py <workload> [steps]   (RHJ_LIB selects the build)"""
+whose results are wrong on purpose): python tools/time_join.py <workload> [steps]   (RHJ_LIB selects the build, e.g.
+sigmod-2018_amd/build/librhj_floor.so from `make -C sigmod-2018_amd variant V=floor RHJ_DEFS=-DFJ_FLOOR`)"""
 import importlib, sys, json, ctypes as C
 sys.path.insert(0, ".")
 import bench, torch
