@@ -283,7 +283,8 @@ int rhj_partition_device(const rhj_tuple *d_in, uint64_t n, rhj_tuple *d_out,
 /* Filter scan on a device-resident column.  d_sel == NULL: scan col[0..n);
  * else scan col[d_sel[i]] for i in [0,n).  d_out gets the ascending indices i
  * (capacity n).  op is '<', '>' or '='; value is already converted as the
- * reference does ((uint64_t)(int)value, filter.c:116).  */
+ * reference does ((uint64_t)(int)value, filter.c:116).  d_col and d_sel need only
+ * 8-byte alignment (a view such as col + 1 is fine).  */
 int rhj_filter_device(const uint64_t *d_col, const uint64_t *d_sel, uint64_t n,
                       char op, uint64_t value, uint64_t *d_out, uint64_t *hits);
 

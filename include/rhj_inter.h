@@ -119,7 +119,10 @@ int rhj_sum_views_device(int views, const uint64_t *const *d_cols, const uint64_
 /* ascending i with colA[selA ? selA[i] : i] == colB[selB ? selB[i] : i] */
 int rhj_filter_eq2_device(const uint64_t *d_colA, const uint64_t *d_selA, const uint64_t *d_colB, const uint64_t *d_selB,
                           uint64_t n, uint64_t *d_out, uint64_t *hits);
-/* min, max and the reference's distinct-value estimate of a device column (n >= 1) */
+/* min, max and the reference's distinct-value estimate of a device column (n >= 1).  A range u - l + 1 below
+ * 50 000 000 counts one flag per value; 50 000 000 or more folds (u - l) modulo 5 000 000.  The full range
+ * (l = 0, u = 2^64 - 1), whose u - l + 1 wraps to 0, is folded the same way; the reference's code is undefined
+ * there (it indexes a calloc of 0 entries, relation_map.c:64-74). */
 int rhj_column_stats_device(const uint64_t *d_col, uint64_t n, uint64_t *l, uint64_t *u, double *d);
 
 /* 1 when the object was created by this library's device-resident side */

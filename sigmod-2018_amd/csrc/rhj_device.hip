@@ -1184,7 +1184,8 @@ int filter_device(const uint64_t *d_col, const uint64_t *d_sel, uint64_t n, char
     }
     uint64_t *total = &((PlanSummary *)g.summary.p)->matches;
     RHJ_STAGE(ST_HIST);
-    RHJ_LAUNCH(k_filter_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, d_col, d_sel, n, oc, value,
+    const bool vec = ((uintptr_t)(d_sel ? d_sel : d_col) & 15u) == 0;     // the mask pass's 16-byte loads need an aligned base
+    RHJ_LAUNCH(k_filter_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, d_col, d_sel, n, oc, value, vec,
                        (uint64_t *)g.fmask.p, (uint64_t *)g.ftile.p);
     if (filter_write_out(n, tiles, total, d_out, hits)) return -1;
     memset(&g.stats, 0, sizeof(g.stats));

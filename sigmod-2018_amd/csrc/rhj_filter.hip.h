@@ -18,15 +18,17 @@ __device__ __forceinline__ bool filter_pred(uint64_t v, uint64_t k, int op)
 
 // Pass 1: evaluate the predicate once.  A lane takes two consecutive elements per round
 // (one 16-byte load); the round's result is kept as two 64-bit ballot masks (even / odd
-// elements), and hits are counted per 4096-element tile.
+// elements), and hits are counted per 4096-element tile.  `vec`: the scanned vector (sel, or col
+// without one) starts on a 16-byte boundary; a caller may pass any 8-byte-aligned view (dcol[1:]),
+// and then every wave takes the scalar loads of the partial wave.
 __global__ __launch_bounds__(256) void k_filter_mask(const uint64_t *col, const uint64_t *sel, uint64_t n, int op,
-                                                     uint64_t value, uint64_t *masks, uint64_t *tile_count)
+                                                     uint64_t value, bool vec, uint64_t *masks, uint64_t *tile_count)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t wbase = (uint64_t)blockIdx.x * FILTER_TILE + (uint64_t)w * FILTER_WAVE_ELEMS;
     uint64_t v0[FILTER_ROUNDS], v1[FILTER_ROUNDS];
-    const bool fast = wbase + FILTER_WAVE_ELEMS <= n;          // whole wave range in bounds
+    const bool fast = vec && wbase + FILTER_WAVE_ELEMS <= n;   // 16-byte loads, whole wave range in bounds
 #pragma unroll
     for (int k = 0; k < FILTER_ROUNDS; ++k) {
         const uint64_t i = wbase + (uint64_t)k * 2 * WAVE + 2 * lane;

@@ -858,7 +858,9 @@ int rhj_column_stats_device(const uint64_t *d_col, uint64_t n, uint64_t *l, uint
     if (hipMemcpyAsync(h, acc, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
     *l = h[0]; *u = h[1];
     // relation_map.c:66-84: one flag per value of [l, u], at most 50 000 000 flags; a larger (or exactly that
-    // large) range is folded modulo 5 000 000 into the same 50 000 000-entry array before counting
+    // large) range is folded modulo 5 000 000 into the same 50 000 000-entry array before counting.  The full
+    // range (l = 0, u = 2^64 - 1) wraps `size` to 0 and is folded like any other range of 50 000 000 or more;
+    // the reference's code is undefined there (calloc of 0 entries, then indexed)
     uint64_t size = h[1] - h[0] + 1;
     if (size > 50000000ull || size == 0) size = 50000000ull;
     const uint64_t fold = size < 50000000ull ? 0 : 5000000ull;

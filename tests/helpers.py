@@ -113,3 +113,21 @@ def spec_join(R, S, bits):
                 a, c = int(p["row_id"]), int(build["row_id"][q])
                 out.append((c, a) if flip else (a, c))
     return np.array(out, dtype=PAIR) if out else np.zeros(0, dtype=PAIR)
+
+
+# relation_map.c:64-84 (and rhj_column_stats_device, sigmod-2018_amd/csrc/rhj_inter.hip): one flag per value of
+# [l, u] below this range, folded modulo STATS_FOLD at this range or above
+STATS_CAP = 50_000_000
+STATS_FOLD = 5_000_000
+
+
+def column_stats_model(col):
+    """(l, u, d) of a u64 column as relation_map.c:53-84 computes them, in Python ints: u - l + 1 is
+    never allowed to wrap, so the full range (0, 2^64 - 1) is the range 2^64 and folds like any other
+    range of STATS_CAP or more (the reference's own code is undefined there)."""
+    col = np.asarray(col, dtype=np.uint64)
+    lo, hi = int(col.min()), int(col.max())
+    x = col - np.uint64(lo)                       # in [0, hi - lo]: no wrap
+    if hi - lo + 1 >= STATS_CAP:
+        x = x % np.uint64(STATS_FOLD)
+    return lo, hi, float(len(np.unique(x)))

@@ -282,6 +282,39 @@ def test_scripted_plans_match_the_reference_host_code(mod, rhj):
         for e in engines:
             e.L.FreeInterResults(e.head)
 
+    # one plan at the size of real data: a filter with more hits, and a JoinInterNode over a node with more rows, than
+    # the filter scan's scan-free write pass takes (FILTER_SELF_TILES * FILTER_TILE, rhj_filter.hip.h:107), on foreign-key
+    # relations so that the node stays linear in the input
+    self_edge = 1024 * 4096
+    N = 5_000_000 + 321
+    pk = rng.permutation(N).astype(np.uint64)                              # R0.c0: a key per row
+    fk = rng.integers(0, N, N, dtype=np.uint64)                            # R1.c0: a key of R0 per row
+    r0c1 = rng.integers(0, 8, N, dtype=np.uint64)
+    at = np.empty(N, dtype=np.int64)
+    at[pk] = np.arange(N)                                                  # the R0 row of each key
+    r1c2 = np.where(rng.random(N) < 0.9, r0c1[at[fk]], rng.integers(0, 8, N, dtype=np.uint64))
+    big = [rng.integers(1 << 62, 1 << 64, N, dtype=np.uint64) for _ in range(2)]     # summed: the sums wrap
+    rels_big = [[pk, r0c1, big[0]], [fk, rng.integers(0, 1000, N, dtype=np.uint64), r1c2, big[1]]]
+    rm_big, keep_big = make_map(mod, rels_big)
+    plan = [("filter", 1, 1, ">", 99), ("join", 1, 0, 0, 0), ("join", 0, 1, 1, 2)]
+    hits = int((rels_big[1][1] > np.uint64(99)).sum())
+    assert hits > self_edge                 # the filter's hits, and the rows of the node JoinInterNode scans (one R0 row per key)
+    engines = [Engine(mod, ref), Engine(mod, lib, rhj)]
+    run_plan(engines, mod, rm_big, [0, 1], plan)
+    n, tabs = engines[0].tables()[0]
+    assert 0 < n < hits and sorted(tabs) == [0, 1]
+    node = engines[1].head.contents.data.contents
+    lib.rhj_sum_views_device.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p, u64p]
+    dcols = [dev(rhj, big[0]), dev(rhj, big[1])]
+    cols = (C.c_void_p * 2)(*[d.data_ptr() for d in dcols])
+    sels = (C.c_void_p * 2)(node.table[0], node.table[1])
+    ns = (C.c_uint64 * 2)(n, n)
+    got = (C.c_uint64 * 2)()
+    assert lib.rhj_sum_views_device(2, cols, sels, ns, got) == 0
+    assert list(got) == [int(big[j][tabs[j]].sum(dtype=np.uint64)) for j in (0, 1)]
+    for e in engines:
+        e.L.FreeInterResults(e.head)
+
 
 def test_find_result_tuples_of_two_live_resident_results_do_not_alias(mod, rhj):
     """FindResultTuples (results.c:126-142) returns a pointer into the list; a device-resident list hands out a host copy of
