@@ -1,0 +1,346 @@
+"""The join kernels on keys built to collide in their hashes (tests/hashkeys.py), against the oracle bit for bit, order
+included.  Ordinary random relations carry one planted bucket whose keys share a slot and a tag, sit at the tag clamp,
+share their low 32 bits, or collide in k_join_exact's stored bits.  Every case also asserts the path it meant to reach
+(stats()["path"], rhj_last_spec / rhj_last_exact, hbm_units), so a fall-through to another kernel cannot pass.
+
+Path rules (sigmod-2018_amd/csrc/rhj_device.hip, join_device_once):
+  small      bits <= PT_MAX_BITS and both relations within small_tiles tiles of SM_TILE tuples, unless rhj_set_small(0)
+  resident   k_join_fused<true>: nmin / bins <= 7000 and resident allowed (H32, FjHashT<true>)
+  gather     k_join_fused<false>: rhj_set_resident(0) (mix64, FjHashT<false>)
+  spec       k_join_spec: bits > PT_MAX_BITS, max(nR, nS) / bins >= 4096; <true> when resident, <false> when not
+  exact      k_join_exact: spec, rhj_set_exact(1), resident off (or nmin / bins > 7000), bits >= 10, nmin / bins <= XJ_MAX_BUILD;
+             xj_body hands over (last_exact 2) a max_build above XJ_MAX_BUILD or without LDS room for hs_min slots
+  tiled      rhj_set_fused(0) (Tab32 in LDS) or rhj_set_force_hbm_table(1) (Tab64 in HBM, hbm_units > 0)
+"""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import hashkeys as hk
+from helpers import make_rel
+from pyoracle import PAIR
+
+pytestmark = pytest.mark.gpu
+
+# constants of sigmod-2018_amd/csrc (rhj_device.hip, rhj_join_fused.hip.h, rhj_join_exact.hip.h)
+LDS_BUDGET = 160 * 1024
+FJ_LDS_EXTRA = 2048
+FJ_WIN = 8
+FJ_BATCH = 1024 * 4
+FJ_GROUPS = 65536 // 256
+XJ_HEAD = FJ_GROUPS * 4
+XJ_MAX_BUILD = 7 * FJ_BATCH
+WALK_FANOUT = 16                       # a probe tuple with more matches has its pairs written by k_join_walk
+
+# rhj_set_* knobs and their defaults; every case restores all of them
+DEFAULTS = {"spec": 1, "exact": 0, "resident": 1, "fused": 1, "small": 1, "lowradix": 1, "force_hbm_table": 0}
+
+
+def restore(rhj):
+    for k, v in DEFAULTS.items():
+        getattr(rhj.lib, "rhj_set_" + k)(v)
+
+
+@pytest.fixture(scope="module")
+def rhj():
+    mod = importlib.import_module("sigmod-2018_amd")
+    r = mod.RHJ(device=0)
+    restore(r)
+    yield r
+    restore(r)
+
+
+@pytest.fixture
+def knobs(rhj):
+    def set_(**kw):
+        for k, v in kw.items():
+            getattr(rhj.lib, "rhj_set_" + k)(v)
+    try:
+        yield set_
+    finally:
+        restore(rhj)
+
+
+def same(got, want, what):
+    want = np.ascontiguousarray(want, dtype=PAIR)
+    assert len(got) == len(want), "%s: %d pairs, oracle %d" % (what, len(got), len(want))
+    assert np.array_equal(got["row_idR"], want["row_idR"]) and np.array_equal(got["row_idS"], want["row_idS"]), what
+
+
+def dev_join(rhj, R, S, capacity=None):
+    t, m = rhj.join_device(rhj.to_device(R), rhj.to_device(S), capacity=capacity)
+    out = rhj.pairs_to_numpy(t)
+    assert m == len(out)
+    return out
+
+
+def background(rng, n, bits, avoid):
+    """n distinct random keys outside the buckets in `avoid`."""
+    k = np.unique(rng.integers(0, 1 << 64, size=n + n // 8 + 64, dtype=np.uint64, endpoint=False))
+    mask = np.uint64((1 << bits) - 1)
+    k = k[~np.isin(k & mask, np.array(sorted(avoid), dtype=np.uint64))]
+    return rng.permutation(k)[:n]
+
+
+def relations(rng, bits, nR, nS, planted, fk=False):
+    """R and S of about nR / nS tuples: random background keys (S drawn from R's, and for a non-foreign-key join half of
+    them fresh) and the planted buckets' keys, (b, R keys, S keys), shuffled in."""
+    avoid = {int(b) for b, _, _ in planted}
+    bgR = background(rng, nR, bits, avoid)
+    if fk:
+        bgS = bgR[rng.integers(0, len(bgR), size=nS)]
+    else:
+        bgS = np.concatenate([bgR[rng.integers(0, len(bgR), size=nS // 2)], background(rng, nS - nS // 2, bits, avoid)])
+    r = np.concatenate([bgR] + [np.asarray(x, dtype=np.uint64) for _, x, _ in planted])
+    s = np.concatenate([bgS] + [np.asarray(y, dtype=np.uint64) for _, _, y in planted])
+    return make_rel(rng.permutation(r)), make_rel(rng.permutation(s))
+
+
+def interleave(rng, *parts):
+    return rng.permutation(np.concatenate([np.asarray(p, dtype=np.uint64) for p in parts]))
+
+
+# ---- paths ------------------------------------------------------------------------------------------------------------
+# name: bits, knobs, hash family, path, nR, nS
+PATHS = {
+    "small": (8, {}, "h32", "small", 150_000, 200_000),
+    "resident_one_pass": (8, {"small": 0}, "h32", "fused", 150_000, 200_000),
+    "resident_two_pass": (10, {"small": 0, "fused": 2}, "h32", "fused", 300_000, 400_000),
+    "gather": (9, {"small": 0, "resident": 0}, "mix64", "fused", 300_000, 400_000),
+    "tiled32": (6, {"fused": 0}, "tab32", "tiled", 150_000, 200_000),
+    "tiled64": (6, {"force_hbm_table": 1}, "tab64", "tiled", 150_000, 200_000),
+}
+
+
+def check_path(rhj, path, kind):
+    st = rhj.stats()
+    assert st["path"] == path, (kind, st["path"])
+    if kind == "tiled64":
+        assert st["hbm_units"] > 0
+    return st
+
+
+def cluster(family, b, bits, n, hs, seed, raw_tag=0x1234):
+    """n distinct keys of bucket b in one slot with one tag under the path's hash (hs: the bucket's slot count where the
+    kernel's slot depends on it)."""
+    if family == "h32":
+        return hk.h32_clones(b, bits, n, seed=seed)
+    if family == "mix64":
+        lo, span = hk.mix64_slot_range(7, hs)
+        return hk.mix64_keys(b, bits, n, lo, span, raw_tag, seed=seed)
+    if family == "tab32":                                    # one top word: one home at every table size
+        return hk.mix64_keys(b, bits, n, 0x9E3779B9, 1, raw_tag, seed=seed)
+    return hk.keys_with_hash(b, bits, [0x2468ACE0], hash="tab64", per=n, seed=seed)
+
+
+@pytest.mark.parametrize("name", list(PATHS))
+def test_one_slot_cluster(rhj, oracle, knobs, name):
+    """F1: a bucket's build side is hundreds of keys of one slot and one tag, far beyond the FJ_WIN window (fj_round's
+    continuation, the cooperative sort of long slots, Tab32/Tab64 clusters of equal tags); three of them appear more than
+    WALK_FANOUT times (k_join_walk); the probe side interleaves present keys with absent ones of the same slot and tag, so
+    foreign tag hits lie between one tuple's matches."""
+    bits, kn, family, path, nR, nS = PATHS[name]
+    knobs(**kn)
+    rhj.set_bits(bits)
+    rng = np.random.default_rng(11)
+    b = (1 << bits) // 3
+    n_present, n_absent, dup = 600, 300, WALK_FANOUT + 4
+    bc = n_present + 3 * (dup - 1)                          # the planted bucket's build side (R: S is bigger there)
+    keys = cluster(family, b, bits, n_present + n_absent, max(bc, 64), seed=5)
+    assert len(keys) == n_present + n_absent
+    present, absent = keys[:n_present], keys[n_present:]
+    Rk = np.concatenate([present] + [np.repeat(present[:3], dup - 1)])
+    Sk = interleave(rng, present, present[::2], absent, absent[:200], present[:3])
+    assert len(Sk) * len(np.unique(keys)) < 2 * 10 ** 7 and len(Sk) > len(Rk)
+    R, S = relations(rng, bits, nR, nS, [(b, Rk, Sk)])
+    want = oracle.join(R, S, bits)
+    same(dev_join(rhj, R, S), want, name)
+    check_path(rhj, path, name)
+
+
+def tag_edge_keys(family, b, bits, hs):
+    """F2: raw tags at the clamp (0xfffd, 0xfffe, 0xffff share one fused tag) and at 0 in one slot; Tab64 low words 0 and
+    2^32 - 1.  Returns (build keys, absent keys that meet them in the table)."""
+    if family == "h32":
+        k = hk.keys_with_hash(b, bits, [0x77770000, 0x7777FFFD, 0x7777FFFE, 0x7777FFFF], hash="h32", per=60)
+        return np.concatenate([k[:60], k[60:120], k[150:180]]), np.concatenate([k[120:150], k[180:]])
+    if family == "mix64":
+        lo, span = hk.mix64_slot_range(3, hs)
+        parts = [hk.mix64_keys(b, bits, 60, lo, span, t, seed=t) for t in (0, 0xFFFD, 0xFFFE, 0xFFFF)]
+    elif family == "tab32":
+        parts = [hk.mix64_keys(b, bits, 60, 0x13572468, 1, t, seed=t) for t in (0, 0xFFFD, 0xFFFE, 0xFFFF)]
+    else:
+        k = hk.keys_with_hash(b, bits, [0, hk.M32], hash="tab64", per=120)
+        return np.concatenate([k[:60], k[120:180]]), np.concatenate([k[60:120], k[180:]])
+    return np.concatenate([parts[0], parts[1], parts[3][:30]]), np.concatenate([parts[2], parts[3][30:]])
+
+
+@pytest.mark.parametrize("name", list(PATHS))
+def test_tag_edges(rhj, oracle, knobs, name):
+    bits, kn, family, path, nR, nS = PATHS[name]
+    knobs(**kn)
+    rhj.set_bits(bits)
+    rng = np.random.default_rng(12)
+    b = (1 << bits) - 2
+    bc = 150                                                # the build side: 60 + 60 + 30 keys, 120 for Tab64
+    build, absent = tag_edge_keys(family, b, bits, bc)
+    assert len(build) == (120 if family == "tab64" else bc)
+    h = hk.mix64(np.concatenate([build, absent]))
+    if family in ("mix64", "tab32"):
+        assert len(np.unique(hk.clamp_tag(hk.mix_raw_tag(h)))) == 2
+    Sk = interleave(rng, build, build[::3], absent)
+    R, S = relations(rng, bits, nR, nS, [(b, build, Sk)])
+    want = oracle.join(R, S, bits)
+    same(dev_join(rhj, R, S), want, name)
+    check_path(rhj, path, name)
+
+
+def high_word_keys(family, b, bits, hs):
+    """F3: pairs of keys of one slot and tag that differ only in their high word.  Returns (both keys of every pair, the
+    first key of every pair)."""
+    if family == "h32":
+        k = hk.h32_clones(b, bits, min(64, 1 << bits), seed=3, shared_low=True)
+        return k, k[::2]
+    p = hk.mix64_lowword_pairs(b, bits, hs, 6, seed=bits)
+    return p.reshape(-1), p[:, 0]
+
+
+@pytest.mark.parametrize("name", list(PATHS))
+def test_high_words(rhj, oracle, knobs, name):
+    """F3: keys sharing their low 32 bits inside one slot and tag, one of each pair on the build side; and the extreme keys
+    0, 1, 2^63 - 1, 2^63, 2^64 - 1 on both sides, several times."""
+    bits, kn, family, path, nR, nS = PATHS[name]
+    knobs(**kn)
+    rhj.set_bits(bits)
+    rng = np.random.default_rng(13)
+    b = 5
+    pairs, first = high_word_keys(family, b, bits, 64)          # 64 slots: the fused minimum, above this build side
+    assert len(first) <= 64 or family == "h32"
+    Rk = first
+    Sk = interleave(rng, pairs, pairs, first)
+    mask = np.uint64((1 << bits) - 1)
+    ext = hk.EXTREME_KEYS
+    planted = [(b, Rk, Sk)]
+    for eb in sorted({int(x) for x in ext & mask}):
+        e = ext[(ext & mask) == np.uint64(eb)]
+        planted.append((eb, np.concatenate([e, e[:1]]), np.concatenate([e, e, e])))
+    R, S = relations(rng, bits, nR, nS, planted)
+    want = oracle.join(R, S, bits)
+    same(dev_join(rhj, R, S), want, name)
+    check_path(rhj, path, name)
+    if name == "small":
+        # the same through the host ABI and through the key-column entry point (row id = position)
+        same(rhj.RadixHashJoin(R, S), want, "RadixHashJoin")
+        import torch
+        Rp, Sp = make_rel(R["value"]), make_rel(S["value"])
+        want_k = oracle.join(Rp, Sp, bits)
+        kR = torch.from_numpy(Rp["value"].view(np.int64).copy()).to(rhj.dev)
+        kS = torch.from_numpy(Sp["value"].view(np.int64).copy()).to(rhj.dev)
+        out = torch.empty((len(want_k) + 8, 2), dtype=torch.int64, device=rhj.dev)
+        m = C.c_uint64(0)
+        assert rhj.lib.rhj_join_keys_device(kR.data_ptr(), len(Rp), kS.data_ptr(), len(Sp), out.data_ptr(), out.shape[0], C.byref(m)) == 0
+        same(rhj.pairs_to_numpy(out)[:m.value], want_k, "rhj_join_keys_device")
+
+
+# ---- the foreign-key speculation (k_join_spec) ---------------------------------------------------------------------
+SPEC_BITS = 9
+
+
+@pytest.mark.parametrize("resident", [1, 0], ids=["spec_h32", "spec_mix64"])
+@pytest.mark.parametrize("absent", [False, True], ids=["fk_holds", "fk_fails"])
+def test_spec_on_a_cluster(rhj, oracle, knobs, resident, absent):
+    """F1 under k_join_spec<true> (H32) and <false> (mix64): a primary-key relation with one bucket of 1500 keys of one slot
+    and tag, probed by a foreign-key relation; with absent keys of that slot and tag in it the hypothesis fails (last_spec 2)
+    and the ordinary kernel takes over inside the call."""
+    knobs(resident=resident, spec=1)
+    rhj.set_bits(SPEC_BITS)
+    rng = np.random.default_rng(14)
+    nR, nS = 1_200_000, 2_200_000
+    assert nS // (1 << SPEC_BITS) >= 4096
+    b = 77
+    n_c, filler = 1500, 800
+    bc = n_c + filler
+    if resident:
+        keys = hk.h32_clones(b, SPEC_BITS, n_c + 40, seed=9)
+        fill = hk.h32_clones(b, SPEC_BITS, filler, seed=10)        # another hash value
+    else:
+        fill = np.unique(rng.integers(0, 1 << 54, size=filler, dtype=np.uint64) << np.uint64(SPEC_BITS) | np.uint64(b))[:filler]
+        lo, span = hk.mix64_slot_range(bc // 2, bc)                # hs = the build side (FjHashT<false>, fj_body)
+        keys = hk.mix64_keys(b, SPEC_BITS, n_c + 40, lo, span, 0xFFFE, seed=9)
+    keys, extra = keys[:n_c], keys[n_c:]
+    assert len(fill) == filler and not np.isin(fill, keys).any() and not np.isin(fill, extra).any()
+    Rk = np.concatenate([keys, fill])
+    Sk = interleave(rng, Rk, keys, keys[:1000], extra if absent else keys[:40])
+    assert len(Sk) * n_c < 2 * 10 ** 7
+    R, S = relations(rng, SPEC_BITS, nR, nS, [(b, Rk, Sk)], fk=True)
+    want = oracle.join(R, S, SPEC_BITS)
+    same(dev_join(rhj, R, S, capacity=len(S) + 8), want, "spec")
+    assert rhj.stats()["path"] == "fused"
+    assert rhj.lib.rhj_last_spec() == (2 if absent else 1)
+
+
+# ---- k_join_exact -------------------------------------------------------------------------------------------------
+def exact_max_build(bits):
+    """The largest max_build xj_body takes: XJ_MAX_BUILD, or the LDS room for the entries beside hs_min slot starts."""
+    lds_bytes = LDS_BUDGET - FJ_LDS_EXTRA
+    room = (lds_bytes - XJ_HEAD - 64 - 2 * (hk.xj_hs_min(bits) + 16)) // 5 - 3 - FJ_WIN
+    return min(XJ_MAX_BUILD, room)
+
+
+def exact_join(rhj, oracle, bits, planted, nR):
+    """A foreign-key join big enough for the speculation (the bigger relation, S, has 4096 tuples a bucket and more) with
+    the planted buckets; returns last_exact after checking the pairs."""
+    rng = np.random.default_rng(bits)
+    nS = 4096 * (1 << bits) + 50_000
+    rhj.set_bits(bits)
+    rhj.lib.rhj_set_spec(1)                        # (both reset the try-or-not scores a handover lowers)
+    rhj.lib.rhj_set_exact(1)
+    R, S = relations(rng, bits, nR, nS, planted, fk=True)
+    want = oracle.join(R, S, bits)
+    same(dev_join(rhj, R, S, capacity=len(S) + 8), want, "k_join_exact at %d bits" % bits)
+    st = rhj.stats()
+    assert st["path"] == "fused" and rhj.lib.rhj_last_spec() in (1, 2)
+    return rhj.lib.rhj_last_exact(), st
+
+
+@pytest.mark.parametrize("bits", [10, 12])
+@pytest.mark.parametrize("present", ["both", "a_absent", "b_absent"])
+def test_exact_colliders(rhj, oracle, knobs, bits, present):
+    """F4: keys whose 40 stored hash bits equal another key's (kind a: product bit 40 differs, the neighbouring slot at
+    hs == hs_min) or whose ent does (kind b: product bit 39 differs, inside ext, the same slot).  Present on the primary-key
+    side, the hypothesis holds and k_join_exact keeps the join (last_exact 1); probed but absent, the hypothesis fails
+    (last_exact 2) — a false match would hold it with a wrong pair."""
+    knobs(resident=0)
+    b = 3
+    seeds = hk.exact_seed_keys(b, bits, 200, seed=bits)
+    col = np.array([hk.exact_colliders(k, bits) for k in seeds], dtype=np.uint64)
+    ka, kb = col[:, 0], col[:, 1]
+    hm = hk.xj_hs_min(bits)
+    assert np.array_equal(hk.xj_ent(ka, bits), hk.xj_ent(seeds, bits)) and np.array_equal(hk.xj_ext(ka, bits), hk.xj_ext(seeds, bits))
+    assert np.array_equal(hk.xj_slot(kb, bits, hm), hk.xj_slot(seeds, bits, hm))
+    Rk = {"both": np.concatenate([seeds, ka, kb]), "a_absent": np.concatenate([seeds, kb]), "b_absent": np.concatenate([seeds, ka])}[present]
+    Sk = np.concatenate([seeds, ka, kb, seeds, ka, kb])
+    nR = 256 * (1 << bits)                            # ~256 build tuples a bucket: hs == hs_min
+    assert len(Rk) <= hm
+    got, st = exact_join(rhj, oracle, bits, [(b, Rk, Sk)], nR)
+    assert st["max_build"] <= hm
+    assert got == (1 if present == "both" else 2)
+
+
+@pytest.mark.parametrize("bits", [10, 11])
+@pytest.mark.parametrize("over", [0, 1])
+def test_exact_at_its_largest_build_side(rhj, oracle, knobs, bits, over):
+    """The largest build side k_join_exact admits (the LDS room at 10 bits, XJ_MAX_BUILD from 11) and one more, which is
+    handed over (last_exact 2); exact both ways."""
+    knobs(resident=0)
+    mb = exact_max_build(bits) + over
+    assert (mb - over == XJ_MAX_BUILD) == (bits >= 11)
+    rng = np.random.default_rng(bits * 10 + over)
+    b = (1 << bits) - 1
+    Rk = np.unique(rng.integers(0, 1 << 50, size=mb + 100, dtype=np.uint64) << np.uint64(bits) | np.uint64(b))[:mb]
+    Sk = np.concatenate([Rk, Rk[rng.integers(0, mb, size=5000)]])
+    got, st = exact_join(rhj, oracle, bits, [(b, rng.permutation(Rk), Sk)], 700 * (1 << bits))
+    assert st["max_build"] == mb
+    assert got == (2 if over else 1)

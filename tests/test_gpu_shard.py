@@ -112,39 +112,42 @@ def test_ranged_join_at_the_sizes_a_sharded_run_has(rhj, shard, oracle, bits, n,
     dR, dS = rhj.to_device(R), rhj.to_device(S)
     want = oracle.join(R, S, bits)
     rhj.set_bits(bits)
-    rhj.lib.rhj_set_spec(1)
-    rhj.lib.rhj_set_exact(1)
-    plain, m = rhj.join_device(dR, dS, capacity=n)
-    assert m == len(want) and np.array_equal(rhj.pairs_to_numpy(plain)[:m], want)
-    assert rhj.lib.rhj_last_spec() == spec
-    del plain
-    mask = np.uint64((1 << bits) - 1)
-    hr = np.bincount((R["value"] & mask).astype(np.int64), minlength=1 << bits)
-    hs = np.bincount((S["value"] & mask).astype(np.int64), minlength=1 << bits)
-    for ranges in (shard.equal_ranges(bits, 3), shard.bucket_ranges(hr, hs, 3)):
-        at = 0
-        for rng in ranges:
-            part = rhj.pairs_to_numpy(ops.join(dR, dS, bits, rng))
-            assert rhj.lib.rhj_last_spec() == spec, (bits, rng)       # the speculation is tried on a rank's share as on the whole join
-            assert np.array_equal(part, want[at:at + len(part)]), (bits, rng)
-            at += len(part)
-        assert at == len(want)
-    if spec:
-        # one S tuple without a partner, in the middle range: that rank's speculation fails (the ordinary kernel takes over in the
-        # same call), the other ranks' holds
-        S2 = S.copy()
-        victim = int(np.nonzero((S2["value"] & mask) == np.uint64((1 << bits) // 2))[0][0])
-        S2["value"][victim] = (S2["value"][victim] & mask) | np.uint64(1 << 62)
-        want2 = oracle.join(R, S2, bits)
-        dS2 = rhj.to_device(S2)
-        at, went = 0, []
-        for rng in shard.equal_ranges(bits, 3):
-            rhj.lib.rhj_set_spec(1)
-            part = rhj.pairs_to_numpy(ops.join(dR, dS2, bits, rng))
-            went.append(rhj.lib.rhj_last_spec())
-            assert np.array_equal(part, want2[at:at + len(part)]), (bits, rng)
-            at += len(part)
-        assert at == len(want2) and went == [1, 2, 1]
+    try:
+        rhj.lib.rhj_set_spec(1)
+        rhj.lib.rhj_set_exact(1)
+        plain, m = rhj.join_device(dR, dS, capacity=n)
+        assert m == len(want) and np.array_equal(rhj.pairs_to_numpy(plain)[:m], want)
+        assert rhj.lib.rhj_last_spec() == spec
+        del plain
+        mask = np.uint64((1 << bits) - 1)
+        hr = np.bincount((R["value"] & mask).astype(np.int64), minlength=1 << bits)
+        hs = np.bincount((S["value"] & mask).astype(np.int64), minlength=1 << bits)
+        for ranges in (shard.equal_ranges(bits, 3), shard.bucket_ranges(hr, hs, 3)):
+            at = 0
+            for rng in ranges:
+                part = rhj.pairs_to_numpy(ops.join(dR, dS, bits, rng))
+                assert rhj.lib.rhj_last_spec() == spec, (bits, rng)       # the speculation is tried on a rank's share as on the whole join
+                assert np.array_equal(part, want[at:at + len(part)]), (bits, rng)
+                at += len(part)
+            assert at == len(want)
+        if spec:
+            # one S tuple without a partner, in the middle range: that rank's speculation fails (the ordinary kernel takes over in the
+            # same call), the other ranks' holds
+            S2 = S.copy()
+            victim = int(np.nonzero((S2["value"] & mask) == np.uint64((1 << bits) // 2))[0][0])
+            S2["value"][victim] = (S2["value"][victim] & mask) | np.uint64(1 << 62)
+            want2 = oracle.join(R, S2, bits)
+            dS2 = rhj.to_device(S2)
+            at, went = 0, []
+            for rng in shard.equal_ranges(bits, 3):
+                rhj.lib.rhj_set_spec(1)
+                part = rhj.pairs_to_numpy(ops.join(dR, dS2, bits, rng))
+                went.append(rhj.lib.rhj_last_spec())
+                assert np.array_equal(part, want2[at:at + len(part)]), (bits, rng)
+                at += len(part)
+            assert at == len(want2) and went == [1, 2, 1]
+    finally:
+        rhj.lib.rhj_set_exact(0)                   # the default: later modules run without k_join_exact
 
 
 def test_allgatherv_and_independent_joins_on_device_tensors(rhj, shard, oracle, nccl_world):
