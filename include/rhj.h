@@ -158,10 +158,11 @@ void rhj_set_resident(int on);
  * scan, plan, scatter and the fused join as the phases of ONE kernel launch (csrc/rhj_small.hip.h); 0: the same
  * steps as separate launches.  Results are identical either way (env RHJ_NO_SMALL=1). */
 void rhj_set_small(int on);
-/* 1 (default): a join on at most 8 radix bits whose buckets' build sides are beyond the LDS index (the reference's 4 bits
- * from ~0.5 M tuples per relation on) runs on r + k bits internally and is emitted in the canonical order of the r bits in
- * force (csrc/rhj_lowradix.hip.h); 0: such joins take the tiled path with hash tables in HBM.  Results are identical
- * either way (env RHJ_NO_LOWRADIX=1). */
+/* 1 (default): a canonical join on at most 13 radix bits whose buckets' build sides are beyond the LDS index (the reference's
+ * 4 bits from ~0.5 M tuples per relation on; 12 bits from ~140 M) runs on r + k bits internally (k = rhj_sub_bits()) and is
+ * emitted in the canonical order of the r bits in force: at r <= 8 the low-radix path (csrc/rhj_lowradix.hip.h), at 9..13
+ * the sub-bucket path (csrc/rhj_subbucket.hip.h); 0: such joins take the tiled path with hash tables in HBM.  Results are
+ * identical either way (env RHJ_NO_LOWRADIX=1). */
 void rhj_set_lowradix(int on);
 /* 1 (default): the two-pass partition's first pass counts the second pass' digits itself at radix widths up to 12 bits
  * (csrc/rhj_partition.hip.h, k_local_part); 0: a kernel of its own counts them from one byte per tuple at every width, as
@@ -234,6 +235,11 @@ void rhj_set_order(int any);
 int  rhj_get_order(void);
 /* the radix width order mode "any" would use for relations of these sizes (pure function: needs no device) */
 int  rhj_auto_radix_bits(uint64_t nR, uint64_t nS);
+/* the extra bits k a canonical join on `bits` radix bits of relations of these sizes runs on internally (the low-radix path
+ * at bits <= 8, the sub-bucket path at 9..13; rhj_set_lowradix): 0 where the buckets fit the LDS index as they are, where
+ * no k < 15 - bits brings the sub-buckets under 30 000 tuples, and always at 14 and 15 bits; -1 for bits outside 1..15
+ * (pure function: needs no device) */
+int  rhj_sub_bits(int bits, uint64_t nR, uint64_t nS);
 /* How much of a join rhj_get_stats() times with HIP events: 2 (default) every stage, 1 the whole join only, 0 nothing
  * (all ms_* zero).  An event between two launches keeps the second kernel from being fed while the first drains, ~6 us
  * each: 10 % of a 1M x 1M join, 1 % of 100M x 100M (env RHJ_TIMING).  A caller that never reads the stage times — the
@@ -252,7 +258,7 @@ typedef struct rhj_stats {
     uint64_t n_r, n_s, matches;
     uint64_t units, hbm_units, max_build, table_slots;
     int radix_bits;
-    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h) */
+    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit) */
 } rhj_stats;
 
 /* Join two device-resident AoS relations (rhj_tuple[nR], rhj_tuple[nS]).

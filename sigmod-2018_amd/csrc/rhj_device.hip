@@ -106,7 +106,7 @@ struct Ctx {
     hipEvent_t  ev[ST_N + 1] = {};
     hipEvent_t  ev_x[4] = {};
     Buf partR, partS, tmpR, tmpS, cntR, cntS, chunk, histpsum, passhp, units, bunits, ldsb, meta, summary,
-        ucount, ubase, uflag, tab32, tab64, stash_cnt, stash_row, status, dbg, bsum, digR, digS, ovf, ovf_base, runR, runS, walk, xrows, lr_tmp, lr_words, lr_status, stripR, stripS, slice_tot, sbase;
+        ucount, ubase, uflag, tab32, tab64, stash_cnt, stash_row, status, dbg, bsum, digR, digS, ovf, ovf_base, runR, runS, walk, xrows, lr_tmp, lr_words, lr_status, stripR, stripS, slice_tot, sbase, sb_cnt, sb_meta, sb_map;
     Buf inR, inS, out, fcol_sel, fmask, ftile, fbase, fout;
     void *pin = nullptr;            // small pinned block for read-backs
     void *pin_ring[4] = {nullptr, nullptr, nullptr, nullptr};   // D2H staging of result pairs (16 MiB each)
@@ -914,40 +914,34 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
     return rc;
 }
 
-// ---- the low-radix path (rhj_lowradix.hip.h) ------------------------------------------------------------------------
-// A canonical join on r <= 8 radix bits whose buckets' build sides are beyond the LDS index runs on r + k bits and is
-// emitted in the order of r bits.  Returns 2 when the path does not apply or gave up (the caller takes the tiled path).
+// ---- the low-radix and sub-bucket paths (rhj_lowradix.hip.h, rhj_subbucket.hip.h) -------------------------------------
+// A canonical join on r <= 13 radix bits whose buckets' build sides are beyond the LDS index runs on r + k bits and is
+// emitted in the order of r bits.  Both return 2 when the path does not apply or gave up (the caller takes the tiled path).
 static int lowradix_sub_bits(int r, uint64_t nR, uint64_t nS)
 {
     const uint64_t nmin = nR < nS ? nR : nS;
-    if (r > PT_MAX_BITS || (nmin >> r) <= 33000) return 0;                // the fused path takes such buckets as they are (its LDS index holds 36 K build tuples)
+    if (r + 1 >= MAX_BITS || (nmin >> r) <= 33000) return 0;            // the fused path takes such buckets as they are (its LDS index holds 36 K build tuples)
+    const int kmax = r <= PT_MAX_BITS ? PT_MAX_BITS : MAX_BITS - 1 - r;   // the sub-bucket path stays below the widest radix
     int k = 1;
-    while (k < PT_MAX_BITS && r + k < MAX_BITS && (nmin >> (r + k)) > 20000) ++k;
-    if ((nmin >> (r + k)) > 30000) return 0;                              // even 8 more bits leave the build sides too big
+    while (k < kmax && r + k < MAX_BITS && (nmin >> (r + k)) > 20000) ++k;
+    if ((nmin >> (r + k)) > 30000) return 0;                              // even the widest split leaves the build sides too big
     return k;
 }
 
-int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                   uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches, int kb)
+// The part both paths share: the caller's r-bit buckets split into 2^kb sub-buckets each, hist / psum of the r + kb-bit layout
+// (sub-bucket s of bucket b at (s << r) | b) and the partitioned relations in partR / partS.  Chooses every caller's bucket's
+// probe side (k_lr_parent), plans and runs the fused kernel in its low-radix form: the pairs go to lr_tmp, every probe tuple's
+// count and stash row to stash_cnt / stash_row.  Returns 2 for what these paths refuse — wide row ids, a build side beyond the
+// LDS index, a unit that needed the index walk (its tuples' pairs are not where their stash rows say), a pass-2 tile of
+// several batches (words[0]), 2^32 pairs or more — and fills ja (out = lr_tmp) and *M otherwise.
+static int lr_internal_join(uint64_t nR, uint64_t nS, int r, int kb, const uint64_t *hist, const uint64_t *psum, uint32_t *words,
+                            bool count_only, const char *path, JoinArgs &ja, uint64_t *M_out)
 {
     rhj_stats &st = g.stats;
-    const int r = g.bits, T = r + kb;
+    const int T = r + kb;
     const uint32_t bins = 1u << T;
-    PartState ps;
-    if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple)) ||
-        ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple)) || ensure(g.lr_words, 4096))
-        return -1;
-    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
-    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
-    ps.tmp[0] = (rhj_tuple *)g.tmpR.p; ps.tmp[1] = (rhj_tuple *)g.tmpS.p;
-    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; ps.r[i].range_bits = (uint32_t)r; }   // (a share: the CALLER's buckets)
-    ps.lo_bits = r;                                            // pass 1 on exactly the caller's bits: pass 2 reads in canonical order
-    uint32_t *words = (uint32_t *)g.lr_words.p;                // word 0: a pass-2 tile / chunk beyond one batch; word 1: k_lr_emit's ticket
     uint8_t *parent_flip = (uint8_t *)(words + 16);            // [2 << r]
-    HIP_TRY(hipMemsetAsync(words, 0, 64, g.stream));
-    if (run_partition(ps, T, 2, false, true)) return -1;
-    RHJ_STAGE(ST_PLAN);
-    RHJ_LAUNCH(k_lr_parent, dim3(1u << r), dim3(256), 0, g.stream, (const uint64_t *)ps.hist, (const uint64_t *)(ps.hist + bins), r, kb, parent_flip);
+    RHJ_LAUNCH(k_lr_parent, dim3(1u << r), dim3(256), 0, g.stream, hist, hist + bins, r, kb, parent_flip);
 
     const uint32_t build_chunk = 4096;
     uint32_t lds_cap = (LDS_BUDGET - FJ_LDS_EXTRA - 128) * 2 / 9;
@@ -964,16 +958,15 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         ensure(g.walk, (unit_bound + 1) * sizeof(FjWalkItem)))
         return -1;
     PlanArgs pa;
-    pa.histR = ps.hist; pa.histS = ps.hist + bins;
+    pa.histR = (uint64_t *)hist; pa.histS = (uint64_t *)hist + bins;
     pa.units = (Unit *)g.units.p; pa.build_units = (Unit *)g.bunits.p; pa.lds_buckets = (uint32_t *)g.ldsb.p;
     pa.meta = (BucketMeta *)g.meta.p; pa.summary = (PlanSummary *)g.summary.p;
     pa.lds_cap = lds_cap; pa.lds_max_slots = LDS_BUDGET / 4 / 4 * 4; pa.build_chunk = build_chunk; pa.span_lds = FJ_SPAN;
     pa.parent_mask = (1u << r) - 1u; pa.parent_flip = parent_flip; pa.zero = nullptr; pa.zero_words = 0;
     RHJ_LAUNCH(k_plan, dim3(T >= 11 ? 8 : 1), dim3(1024), 0, g.stream, pa, T);
 
-    JoinArgs ja;
     ja.partR = (const rhj_tuple *)g.partR.p; ja.partS = (const rhj_tuple *)g.partS.p;
-    ja.histR = ps.hist; ja.histS = ps.hist + bins; ja.psumR = ps.psum; ja.psumS = ps.psum + bins;
+    ja.histR = hist; ja.histS = hist + bins; ja.psumR = psum; ja.psumS = psum + bins;
     ja.units = (const Unit *)g.units.p; ja.meta = (const BucketMeta *)g.meta.p; ja.summary = (const PlanSummary *)g.summary.p;
     ja.tab32 = nullptr; ja.tab64 = nullptr;
     ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p; ja.unit_flag = (uint32_t *)g.uflag.p;
@@ -987,7 +980,6 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
     fa.ovf = (uint64_t *)g.ovf.p; fa.ovf_base = (uint32_t *)g.ovf_base.p; fa.walk = (FjWalkItem *)g.walk.p;
     const uint32_t fused_lds = LDS_BUDGET - FJ_LDS_EXTRA;
     const unsigned fgrid = (unsigned)(unit_bound < (uint64_t)g.cus ? unit_bound : (uint64_t)g.cus);
-    const bool count_only = !use_ctx_out && out == nullptr;
     struct Back { PlanSummary p; uint32_t ticket[4]; uint32_t words[4]; } *hb = (Back *)g.pin;
     uint64_t M = 0;
     RHJ_STAGE(ST_PROBE);
@@ -1009,13 +1001,11 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         HIP_TRY(hipMemcpyAsync(hb->words, words, 16, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
-        // what this path refuses: wide row ids, a build side beyond the LDS index, a unit that needed the index walk (its
-        // tuples' pairs are not where their stash rows say), a pass-2 tile of several batches, 2^32 pairs or more
         if (hb->p.wide_row_ids || hb->p.row_id_overflow || !hb->p.fused_ok || hb->ticket[2] != 0 || hb->words[0] != 0 ||
             hb->p.matches == FJ_NO_TOTAL || hb->p.matches >= (1ull << 32)) {
             static const bool trace = getenv("RHJ_TRACE") != nullptr;
-            if (trace) fprintf(stderr, "rhj-trace:   low-radix path gives up: wide ids %u/%u, fused_ok %llu, walk units %u, big tile %u, matches %llu\n",
-                               hb->p.wide_row_ids, hb->p.row_id_overflow, (unsigned long long)hb->p.fused_ok, hb->ticket[2], hb->words[0],
+            if (trace) fprintf(stderr, "rhj-trace:   %s path gives up: wide ids %u/%u, fused_ok %llu, walk units %u, big tile %u, matches %llu\n",
+                               path, hb->p.wide_row_ids, hb->p.row_id_overflow, (unsigned long long)hb->p.fused_ok, hb->ticket[2], hb->words[0],
                                (unsigned long long)hb->p.matches);
             return 2;
         }
@@ -1023,19 +1013,55 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         if (count_only || M * sizeof(rhj_result_tuple) <= g.lr_tmp.cap) break;
     }
     st.units = hb->p.units; st.hbm_units = 0; st.max_build = hb->p.max_build;
+    *M_out = M;
+    return 0;
+}
+
+// the caller's buffer for M pairs: the context's own (grown) one, or out when it holds them all (else rc 1: the first
+// out_capacity pairs are written)
+static int lr_out_buffer(uint64_t M, bool use_ctx_out, rhj_result_tuple **ctx_out, rhj_result_tuple *&out, uint64_t &out_capacity, int &rc)
+{
+    rc = 0;
+    if (use_ctx_out) {
+        if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;
+        out = (rhj_result_tuple *)g.out.p;
+        out_capacity = M;
+        if (ctx_out) *ctx_out = out;
+    } else if (M > out_capacity) {
+        rc = 1;
+    }
+    return 0;
+}
+
+int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
+                   uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches, int kb)
+{
+    rhj_stats &st = g.stats;
+    const int r = g.bits, T = r + kb;
+    PartState ps;
+    if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple)) ||
+        ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple)) || ensure(g.lr_words, 64 + ((size_t)2 << r) + 4096))
+        return -1;
+    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
+    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
+    ps.tmp[0] = (rhj_tuple *)g.tmpR.p; ps.tmp[1] = (rhj_tuple *)g.tmpS.p;
+    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; ps.r[i].range_bits = (uint32_t)r; }   // (a share: the CALLER's buckets)
+    ps.lo_bits = r;                                            // pass 1 on exactly the caller's bits: pass 2 reads in canonical order
+    uint32_t *words = (uint32_t *)g.lr_words.p;                // word 0: a pass-2 tile / chunk beyond one batch; word 1: k_lr_emit's ticket
+    HIP_TRY(hipMemsetAsync(words, 0, 64, g.stream));
+    if (run_partition(ps, T, 2, false, true)) return -1;
+    RHJ_STAGE(ST_PLAN);
+    const bool count_only = !use_ctx_out && out == nullptr;
+    JoinArgs ja;
+    uint64_t M = 0;
+    const int rj = lr_internal_join(nR, nS, r, kb, ps.hist, ps.psum, words, count_only, "low-radix", ja, &M);
+    if (rj) return rj;
     st.reserved = 4;                                           // path id: low-radix
     *matches = M;
     st.matches = M;
     int rc = 0;
     if (!count_only && M) {
-        if (use_ctx_out) {
-            if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;
-            out = (rhj_result_tuple *)g.out.p;
-            out_capacity = M;
-            if (ctx_out) *ctx_out = out;
-        } else if (M > out_capacity) {
-            rc = 1;
-        }
+        if (lr_out_buffer(M, use_ctx_out, ctx_out, out, out_capacity, rc)) return -1;
         LrArgs la;
         la.j = ja; la.j.out = out; la.j.out_capacity = out_capacity;
         la.p2R = ps.p2[0]; la.p2S = ps.p2[1];
@@ -1057,10 +1083,11 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         const unsigned egrid = (unsigned)(nslots < (uint32_t)g.cus * 8u ? nslots : (uint32_t)g.cus * 8u);
         RHJ_LAUNCH(k_lr_emit, dim3(egrid), dim3(LR_BLOCK), lr_lds_bytes(kb), g.stream, la, nslots);
         RHJ_STAGE(ST_END);
-        HIP_TRY(hipMemcpyAsync(hb->words, words, 16, hipMemcpyDeviceToHost, g.stream));
+        uint32_t *hw = (uint32_t *)g.pin + 256;
+        HIP_TRY(hipMemcpyAsync(hw, words, 16, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hb->words[0] != 0) return 2;
+        if (hw[0] != 0) return 2;
     } else {
         RHJ_STAGE(ST_END);
         HIP_TRY(hipStreamSynchronize(g.stream));
@@ -1071,6 +1098,100 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
     st.ms_scatter = stage_ms(ST_SCATTER, ST_PLAN);
     st.ms_plan = stage_ms(ST_PLAN, ST_PROBE);
     st.ms_probe = stage_ms(ST_PROBE, ST_END);
+    st.ms_total = stage_ms(ST_HIST, ST_END);
+    return rc;
+}
+
+// The sub-bucket path (rhj_subbucket.hip.h): r = 9..13.  The r-bit partition lands in tmpR / tmpS (pass 1's intermediate in
+// partR / partS), pass B splits it into partR / partS on the next kb bits; the internal join is the low-radix path's.
+// Stage times: ms_hist / ms_scan / ms_scatter the r-bit partition's, ms_build pass B, ms_plan parent choice + plan, ms_probe the
+// internal join, ms_offsets the emit.
+int join_device_sb(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
+                   uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches, int kb)
+{
+    rhj_stats &st = g.stats;
+    const int r = g.bits, T = r + kb;
+    if (kb > SB_MAX_K || nR >= (1ull << 31) || nS >= (1ull << 31)) return 2;      // (the emit map keeps 31-bit positions)
+    const uint32_t bins_r = 1u << r, binsT = 1u << T, digits = 1u << kb;
+    PartState ps;
+    if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple)) ||
+        ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple)) || ensure(g.lr_words, 64 + ((size_t)2 << r) + 4096))
+        return -1;
+    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.tmpR.p, nullptr, nR, 0, 0, nullptr, nullptr};
+    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.tmpS.p, nullptr, nS, 0, 0, nullptr, nullptr};
+    ps.tmp[0] = (rhj_tuple *)g.partR.p; ps.tmp[1] = (rhj_tuple *)g.partS.p;
+    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; ps.r[i].range_bits = (uint32_t)r; }
+    uint32_t *words = (uint32_t *)g.lr_words.p;                // word 0: (nothing raises it on this path); words 4..5: the emit scan's total
+    HIP_TRY(hipMemsetAsync(words, 0, 64, g.stream));
+    if (run_partition(ps, r, 2, false, true)) return -1;
+    RHJ_STAGE(ST_BUILD);
+
+    // ---- pass B
+    const uint32_t rowlen = (uint32_t)(((nR > nS ? nR : nS) + SB_CHUNK - 1) / SB_CHUNK) + bins_r + 1;
+    const size_t ncnt = (size_t)2 * digits * rowlen;
+    const size_t meta_bytes = (size_t)4 * binsT * 8 + (size_t)2 * (bins_r + 1) * 4 + (size_t)(bins_r + 1) * 8 + 64;
+    if (ensure(g.sb_cnt, ncnt * 8) || ensure(g.sb_meta, meta_bytes) || ensure(g.sb_map, (nR + nS) * 4 + 64)) return -1;
+    SbArgs sa;
+    sa.in[0] = (const Tuple12 *)g.tmpR.p; sa.in[1] = (const Tuple12 *)g.tmpS.p;
+    sa.out[0] = (Tuple12 *)g.partR.p; sa.out[1] = (Tuple12 *)g.partS.p;
+    sa.histr = ps.hist; sa.psumr = ps.psum;
+    uint64_t *histT = (uint64_t *)g.sb_meta.p, *psumT = histT + 2 * (size_t)binsT;
+    sa.histT = histT; sa.psumT = psumT;
+    sa.ebase = psumT + 2 * (size_t)binsT;
+    sa.cbase = (uint32_t *)(sa.ebase + bins_r + 1);
+    sa.ccnt = (uint64_t *)g.sb_cnt.p;
+    sa.emap = (uint32_t *)g.sb_map.p;
+    sa.summary = (const PlanSummary *)g.summary.p;
+    sa.r_bits = (uint32_t)r; sa.k_bits = (uint32_t)kb; sa.rowlen = rowlen;
+    RHJ_LAUNCH(k_sb_meta, dim3(1), dim3(1024), 0, g.stream, sa);
+    RHJ_LAUNCH(k_sb_count, dim3(rowlen, 2), dim3(SB_BLOCK), 0, g.stream, sa);
+    if (launch_offsets(sa.ccnt, sa.ccnt, nullptr, ncnt, ncnt, (uint64_t *)(words + 4))) return -1;
+    RHJ_LAUNCH(k_sb_hist, dim3((binsT + 255) / 256, 2), dim3(256), 0, g.stream, sa);
+    RHJ_LAUNCH(k_scan_psum, dim3(2), dim3(1024), 0, g.stream, T, (const uint64_t *)histT, psumT);
+    RHJ_LAUNCH(k_sb_scatter, dim3(rowlen, 2), dim3(SB_BLOCK), 0, g.stream, sa);
+    uint64_t *hE = (uint64_t *)g.pin + 256;                    // the emit sequence's length, read back with the join's summary
+    HIP_TRY(hipMemcpyAsync(hE, sa.ebase + bins_r, 8, hipMemcpyDeviceToHost, g.stream));
+    RHJ_STAGE(ST_PLAN);
+
+    const bool count_only = !use_ctx_out && out == nullptr;
+    JoinArgs ja;
+    uint64_t M = 0;
+    const int rj = lr_internal_join(nR, nS, r, kb, histT, psumT, words, count_only, "sub-bucket", ja, &M);
+    if (rj) return rj;
+    st.reserved = 5;                                           // path id: sub-bucket
+    *matches = M;
+    st.matches = M;
+    int rc = 0;
+    RHJ_STAGE(ST_OFFSETS);
+    if (!count_only && M) {
+        if (lr_out_buffer(M, use_ctx_out, ctx_out, out, out_capacity, rc)) return -1;
+        const uint64_t E = *hE;
+        const uint64_t nslots = (E + SB_CHUNK - 1) / SB_CHUNK;
+        if (ensure(g.lr_status, (size_t)nslots * 8 + 64)) return -1;
+        SbEmitArgs ea;
+        ea.emap = sa.emap; ea.n = E;
+        ea.stash_cnt = (const uint8_t *)g.stash_cnt.p; ea.stash_row = (const uint2 *)g.stash_row.p;
+        ea.tmp = (const uint4 *)g.lr_tmp.p; ea.nR = nR;
+        ea.ctotal = (uint64_t *)g.lr_status.p;
+        ea.out = (uint4 *)out; ea.out_capacity = out_capacity;
+        RHJ_LAUNCH(k_sb_totals, dim3((unsigned)nslots), dim3(SB_BLOCK), 0, g.stream, ea);
+        if (launch_offsets(ea.ctotal, ea.ctotal, nullptr, nslots, nslots, (uint64_t *)(words + 4))) return -1;
+        RHJ_LAUNCH(k_sb_emit, dim3((unsigned)nslots), dim3(SB_BLOCK), 0, g.stream, ea);
+    }
+    RHJ_STAGE(ST_END);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    static const bool trace = getenv("RHJ_TRACE") != nullptr;
+    if (trace) fprintf(stderr, "rhj-trace:   sub-bucket path: %d + %d bits, %llu pairs, emit sequence %llu\n", r, kb,
+                       (unsigned long long)M, (unsigned long long)*hE);
+    st.radix_bits = r;
+    st.ms_hist = stage_ms(ST_HIST, ST_SCAN);
+    st.ms_scan = stage_ms(ST_SCAN, ST_SCATTER);
+    st.ms_scatter = stage_ms(ST_SCATTER, ST_BUILD);
+    st.ms_build = stage_ms(ST_BUILD, ST_PLAN);
+    st.ms_plan = stage_ms(ST_PLAN, ST_PROBE);
+    st.ms_probe = stage_ms(ST_PROBE, ST_OFFSETS);
+    st.ms_offsets = stage_ms(ST_OFFSETS, ST_END);
     st.ms_total = stage_ms(ST_HIST, ST_END);
     return rc;
 }
@@ -1108,7 +1229,8 @@ static int join_device_radix(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *
 {
     bool overflow = false;
     {
-        // few radix bits over big inputs, canonical order wanted: run on finer buckets, emit in the caller's order
+        // few radix bits over big inputs, canonical order wanted: run on finer buckets, emit in the caller's order (r <= 8: the
+        // low-radix path, 9..13: the sub-bucket path)
         // (also for a rank's share of a sharded join — the partition's first pass, on the caller's bits, drops the other buckets —
         // but not for a share cut inside a bucket: that is a matter of the plan's units, and these are sub-buckets)
         const int kb = (!g.no_lowradix && !g.no_fused && !g.force_hbm && !g.wide_row_ids && !g.slice_skip && !g.slice_end && nR < (1ull << 32) && nS < (1ull << 32))
@@ -1121,7 +1243,8 @@ static int join_device_radix(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *
             g.stats.n_r = nR; g.stats.n_s = nS; g.stats.radix_bits = g.bits;
             *matches = 0;
             if (ctx_out) *ctx_out = nullptr;
-            const int rc3 = join_device_lr(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, kb);
+            const int rc3 = g.bits <= PT_MAX_BITS ? join_device_lr(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, kb)
+                                                  : join_device_sb(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, kb);
             if (rc3 != 2) return rc3;
         }
     }
@@ -1350,6 +1473,7 @@ int rhj_last_exact(void) { return g.last_exact; }
 void rhj_set_count_in_pass1(int on) { g.no_count_in_pass1 = !on; }
 void rhj_set_order(int any) { g.order_any = any != 0; }
 int rhj_auto_radix_bits(uint64_t nR, uint64_t nS) { return auto_radix_bits(nR, nS); }
+int rhj_sub_bits(int bits, uint64_t nR, uint64_t nS) { return bits < 1 || bits > MAX_BITS ? -1 : lowradix_sub_bits(bits, nR, nS); }
 int rhj_get_order(void) { return g.order_any; }
 void rhj_set_timing(int level) { g.timing = level < 0 ? 0 : level > 2 ? 2 : level; }
 /* diagnostic: copy the per-unit phase stamps of the last fused run (RHJ_STAMPS=1) */
@@ -1704,7 +1828,7 @@ static void release_current()
     (void)hipSetDevice(g.device);
     (void)hipStreamSynchronize(g.stream);
     Buf *all[] = {&g.partR, &g.partS, &g.tmpR, &g.tmpS, &g.cntR, &g.cntS, &g.chunk, &g.histpsum, &g.passhp,
-                  &g.units, &g.bunits, &g.ldsb, &g.meta, &g.summary, &g.ucount, &g.ubase, &g.uflag, &g.bsum, &g.digR, &g.digS, &g.ovf, &g.ovf_base, &g.walk, &g.xrows, &g.lr_tmp, &g.lr_words, &g.lr_status, &g.runR, &g.runS, &g.stripR, &g.stripS, &g.slice_tot, &g.sbase, &g.stash_cnt, &g.stash_row, &g.status, &g.tab32,
+                  &g.units, &g.bunits, &g.ldsb, &g.meta, &g.summary, &g.ucount, &g.ubase, &g.uflag, &g.bsum, &g.digR, &g.digS, &g.ovf, &g.ovf_base, &g.walk, &g.xrows, &g.lr_tmp, &g.lr_words, &g.lr_status, &g.runR, &g.runS, &g.stripR, &g.stripS, &g.slice_tot, &g.sbase, &g.sb_cnt, &g.sb_meta, &g.sb_map, &g.stash_cnt, &g.stash_row, &g.status, &g.tab32,
                   &g.tab64, &g.inR, &g.inS, &g.out, &g.fcol, &g.fcol_sel, &g.fmask, &g.ftile, &g.fbase, &g.fout};
     for (Buf *b : all) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     for (auto &kv : g.columns) (void)hipFree(kv.second.dev);

@@ -33,6 +33,9 @@
 //                          emit passes over 1024-tuple probe tiles.
 //   rhj_lowradix.hip.h     joins on few radix bits (the reference ships 4) over inputs too big for them: run on r + k bits, emitted
 //                          in the canonical order of r bits by replaying pass 2 of the partition over the probe side.
+//   rhj_subbucket.hip.h    the same on 9..13 radix bits: the r-bit partition, a stable split of every bucket on the next k bits
+//                          (pass B, which records where the probe side's tuples went), the low-radix path's internal join, an
+//                          emit that walks the canonical positions.
 //   rhj_filter.hip.h       predicate -> ballot masks -> ascending index list.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
@@ -46,6 +49,7 @@
 #include "rhj_join_fused.hip.h"
 #include "rhj_join_exact.hip.h"
 #include "rhj_lowradix.hip.h"
+#include "rhj_subbucket.hip.h"
 #include "rhj_small.hip.h"
 #include "rhj_filter.hip.h"
 #include "rhj_diag.hip.h"
