@@ -64,8 +64,33 @@ struct Buf {
 
 constexpr int MAX_BITS = 15;
 constexpr uint32_t LDS_BUDGET = 160 * 1024;       // bytes per workgroup on gfx950
+constexpr uint32_t FUSED_LDS = LDS_BUDGET - FJ_LDS_EXTRA;                     // dynamic LDS of the fused kernels
+constexpr uint32_t LDS_MAX_SLOTS = LDS_BUDGET / 4 / 4 * 4;                    // tiled path: k_build_lds owns the whole LDS
+constexpr uint32_t FUSED_LDS_CAP = (FUSED_LDS - 128) * 2 / 9;                 // fused: 4 B entry + >= 0.5 B of slot starts per build tuple
+static_assert(LDS_MAX_SLOTS * 4 / 5 <= 65534 && FUSED_LDS_CAP <= 65534, "LDS-indexed build sides: 16-bit position + 1");
+constexpr uint32_t BUILD_CHUNK = 4096;            // build tuples per 64-bit-table build unit
 
 enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSETS, ST_PROBE, ST_END, ST_N };
+
+// The workspace buffers of a context, listed once: Ctx declares them and rhj_release() frees them from this list.
+#define RHJ_WORKSPACE(X)                                                                                                   \
+    X(partR) X(partS) X(tmpR) X(tmpS) X(cntR) X(cntS) X(chunk) X(histpsum) X(passhp) X(units) X(bunits) X(ldsb) X(meta)   \
+    X(summary) X(ucount) X(ubase) X(uflag) X(tab32) X(tab64) X(stash_cnt) X(stash_row) X(status) X(dbg) X(bsum) X(digR)  \
+    X(digS) X(ovf) X(ovf_base) X(runR) X(runS) X(walk) X(xrows) X(lr_tmp) X(lr_words) X(lr_status) X(stripR) X(stripS)   \
+    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map)                                                                   \
+    X(inR) X(inS) X(out) X(fcol_sel) X(fmask) X(ftile) X(fbase) X(fout)                                                    \
+    X(fcol)                                                      /* staging of an unregistered column (host Filter()) */
+
+// The small pinned host block the device's answers are read back into, one member per kind of read-back.
+struct Pinned {
+    PlanSummary summary;        // a join's or a partition's plan summary (the small path's k_join_fused stores it here itself)
+    uint64_t    walk_units;     // k_join_fused, behind the summary: the units it left to k_join_walk
+    uint32_t    ticket[8];      // the fused kernels' ticket words (FusedArgs::ticket; word 4: the speculation failed)
+    uint32_t    lr_words[4];    // the split paths' words 0..3 (word 0: a pass-2 tile beyond one batch)
+    uint64_t    emit_len;       // sub-bucket path: the emit sequence's length
+    uint64_t    hits;           // filter (k_filter_write<true> stores it itself) and select_range: the count
+};
+static_assert(offsetof(Pinned, walk_units) == sizeof(PlanSummary), "k_join_fused stores the walk count at host_summary + sizeof(PlanSummary) / 8");
 
 struct Ctx {
     bool        ready = false;
@@ -91,7 +116,6 @@ struct Ctx {
     int         no_exact = 1;        // 1: never launch k_join_exact (the default: it measured slower than the gather kernels, profiles/README.md r04a; env RHJ_EXACT=1 / rhj_set_exact(1) turn it on)
     int         exact_score = 2;     // > 0: launch it where it applies (a join it did adds 1, up to 4; one it handed back for its input takes 2 off)
     int         exact_skipped = 0;   // eligible joins not given to it since the score went to zero: every 16th tries again
-    int         cols_input = 0;      // this join's inputs are key columns (rhj_join_keys_device): pass 1 of the two-pass partition reads 8 bytes a tuple
     int         last_exact = 0;      // the last join: 0 not launched, 1 k_join_exact did the join, 2 it handed over (rhj_last_exact)
     int         msd = 0;             // RHJ_MSD=1: pass 1 of the two-pass partition takes the HIGH bits of the radix, pass 2 the low ones (A/B)
     int         lo_override = 0;     // RHJ_LO_BITS: pass-1 digit bits of the two-pass partition (experiments; default bits / 2)
@@ -99,16 +123,14 @@ struct Ctx {
     int         no_lowradix = 0;     // 1: never take the low-radix path (env RHJ_NO_LOWRADIX; rhj_set_lowradix(0)): big joins on few bits go tiled
     int         no_small = 0;        // 1: never take the three-launch path for small joins (env RHJ_NO_SMALL, rhj_set_small(0))
     uint32_t    small_tiles = 512;   // largest relation, in 8192-tuple tiles, the small path takes (env RHJ_SMALL_TILES; at most SM_MAX_TILES)
-    uint32_t    range_lo = 0, range_span = 0;   // rhj_join_device_range: the buckets this call joins (span 0: all of them)
-    uint64_t    slice_skip = 0, slice_end = 0;  // rhj_join_device_slice: the first bucket's probe tuples from slice_skip on, the last bucket's before slice_end (0: all)
     int         cus = 256;           // compute units of the device (one fused workgroup each)
     uint64_t    node_pairs = 65535;
     hipEvent_t  ev[ST_N + 1] = {};
     hipEvent_t  ev_x[4] = {};
-    Buf partR, partS, tmpR, tmpS, cntR, cntS, chunk, histpsum, passhp, units, bunits, ldsb, meta, summary,
-        ucount, ubase, uflag, tab32, tab64, stash_cnt, stash_row, status, dbg, bsum, digR, digS, ovf, ovf_base, runR, runS, walk, xrows, lr_tmp, lr_words, lr_status, stripR, stripS, slice_tot, sbase, sb_cnt, sb_meta, sb_map;
-    Buf inR, inS, out, fcol_sel, fmask, ftile, fbase, fout;
-    void *pin = nullptr;            // small pinned block for read-backs
+#define RHJ_BUF(name) Buf name;
+    RHJ_WORKSPACE(RHJ_BUF)
+#undef RHJ_BUF
+    Pinned *pin = nullptr;          // 4 KiB pinned block for read-backs
     void *pin_ring[4] = {nullptr, nullptr, nullptr, nullptr};   // D2H staging of result pairs (16 MiB each)
     hipEvent_t ev_ring[4] = {};
     // REGISTERED host columns (rhj_register_relation_map / the resident InitRelationMap) -> device copy.
@@ -118,7 +140,6 @@ struct Ctx {
     std::map<const void *, Column> columns;
     std::map<const void *, size_t> pinned;                       // hipHostRegister'ed host ranges (base -> bytes)
     int pin_refusals = 0;                                        // ranges of 64 KiB or more the host refused to pin
-    Buf fcol;                                                    // staging of an unregistered column (host Filter())
     std::multimap<size_t, void *> free_blocks;                  // rhj_dev_alloc: cached blocks by size
     std::map<void *, size_t> live_blocks;                       // rhj_dev_alloc: blocks handed out
     rhj_stats stats = {};
@@ -209,7 +230,7 @@ int ctx_init()
     if (!g.stream_set) { HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking)); g.own_stream = true; }
     for (auto &ev : g.ev) HIP_TRY(hipEventCreate(&ev));
     for (auto &ev : g.ev_x) HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipHostMalloc(&g.pin, 4096, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&g.pin, 4096, hipHostMallocDefault));
     // dynamic LDS above 64 KiB has to be requested per kernel
     HIP_TRY(hipFuncSetAttribute((const void *)k_build_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
     {
@@ -252,6 +273,7 @@ struct PartState {
     uint64_t *hist, *psum;   // [2][bins] of the join's radix (filled by run_partition)
     const PlanArgs *plan = nullptr;   // the join's plan arguments: a small one-pass partition runs the plan in its scan launch
     bool plan_done = false;
+    int      cols_input = 0;  // the inputs are key columns (rhj_join_keys_device): pass 1 of the two-pass partition reads 8 bytes a tuple
 };
 
 uint32_t tiles_for(uint64_t n)
@@ -411,10 +433,9 @@ int run_partition(PartState &ps, int bits, int nrel, bool force_wide, bool final
     // (g.seen_wide): the sample then reports a wide input as an overflow and the caller runs again wide.
     const bool launch_narrow = !force_wide;
     ps.launch_wide = force_wide || g.seen_wide;
-    if (ensure(g.summary, sizeof(PlanSummary))) return -1;
     PlanSummary *dsum = (PlanSummary *)g.summary.p;
     RHJ_STAGE(ST_HIST);
-    RHJ_LAUNCH(k_rowid_sample, dim3(1), dim3(1024), 0, g.stream, a0, a1, nrel, force_wide ? 1 : 0, ps.launch_wide ? 0 : 1, dsum, g.cols_input);
+    RHJ_LAUNCH(k_rowid_sample, dim3(1), dim3(1024), 0, g.stream, a0, a1, nrel, force_wide ? 1 : 0, ps.launch_wide ? 0 : 1, dsum, ps.cols_input);
     {
         const uint32_t h2_off = (uint32_t)((scatter_lds_bytes(lo) + 15) & ~(size_t)15);
         const size_t lds1 = count_in_pass1 ? h2_off + ((size_t)2 << bits) : scatter_lds_bytes(lo);
@@ -424,7 +445,7 @@ int run_partition(PartState &ps, int bits, int nrel, bool force_wide, bool final
         const bool ranged = a0.range_span != 0;
 #define RHJ_LP(R, H, D) RHJ_LAUNCH((k_local_part<R, H, D>), grid1, dim3(PT_BLOCK), lds1, g.stream, a0, a1, sh1, lo, sh2, hi, dsum, h2_off)
 #define RHJ_LPC(H, D) RHJ_LAUNCH((k_local_part<false, H, D, true>), grid1, dim3(PT_BLOCK), lds1, g.stream, a0, a1, sh1, lo, sh2, hi, dsum, h2_off)
-        if (g.cols_input) { if (!count_in_pass1) RHJ_LPC(false, true); else if (want_dig) RHJ_LPC(true, true); else RHJ_LPC(true, false); }   // (never ranged: join_keys)
+        if (ps.cols_input) { if (!count_in_pass1) RHJ_LPC(false, true); else if (want_dig) RHJ_LPC(true, true); else RHJ_LPC(true, false); }   // (never ranged: join_keys)
         else if (ranged)  { if (!count_in_pass1) RHJ_LP(true, false, true); else if (want_dig) RHJ_LP(true, true, true); else RHJ_LP(true, true, false); }
         else              { if (!count_in_pass1) RHJ_LP(false, false, true); else if (want_dig) RHJ_LP(false, true, true); else RHJ_LP(false, true, false); }
 #undef RHJ_LPC
@@ -488,74 +509,208 @@ float ev_ms(hipEvent_t a, hipEvent_t b)
 }
 float stage_ms(int a, int b) { return stage_on(a) && stage_on(b) ? ev_ms(g.ev[a], g.ev[b]) : 0.f; }
 
-// The whole device-side join.  out == nullptr && use_ctx_out: the pairs land in the
-// context's own buffer (grown after the count pass), returned through *ctx_out.
-int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                     uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches,
-                     bool force_wide, bool *overflow)
+// ---- one join ----------------------------------------------------------------------------------------------------------------
+
+// A join as an entry point asks for it.  out == nullptr: the pairs are only counted, or with use_ctx_out they land in the
+// context's own buffer (grown as needed) and come back through *ctx_out.
+struct JoinReq {
+    const rhj_tuple   *R;
+    uint64_t           nR;
+    const rhj_tuple   *S;
+    uint64_t           nS;
+    rhj_result_tuple  *out;
+    uint64_t           out_capacity;
+    bool               use_ctx_out;
+    rhj_result_tuple **ctx_out;
+    uint64_t          *matches;
+    int                bits;                           // the radix (RHJ_ORDER=any: join_device picks it)
+    uint32_t           range_lo = 0, range_span = 0;   // rhj_join_device_range: the buckets this call joins (span 0: all of them)
+    uint64_t           slice_skip = 0, slice_end = 0;  // rhj_join_device_slice: the first bucket's probe tuples from slice_skip on, the last bucket's before slice_end (0: all)
+    int                cols_input = 0;                 // R and S are key columns (rhj_join_keys_device): pass 1 of the two-pass partition reads 8 bytes a tuple
+
+    bool count_only() const { return !use_ctx_out && out == nullptr; }
+};
+
+// every attempt at a join starts here: the stats of this attempt alone (the upload's time, taken before the call, stays)
+static int begin_join(const JoinReq &q)
 {
-    *overflow = false;
     if (ctx_init()) return -1;
     rhj_stats &st = g.stats;
     const float keep_h2d = st.ms_h2d;
     memset(&st, 0, sizeof(st));
     st.ms_h2d = keep_h2d;
-    st.n_r = nR; st.n_s = nS; st.radix_bits = g.bits;
-    *matches = 0;
-    if (ctx_out) *ctx_out = nullptr;
-    if (nR == 0 || nS == 0) return 0;                         // rhjoin.c:15-16
-    if (nR >= (1ull << 32) || nS >= (1ull << 32)) {
-        fprintf(stderr, "rhj: relations of 2^32 tuples or more are not supported (offsets are 32-bit; the reference "
-                        "itself is limited to 2^31-1, SURVEY.md finding 9)\n");
-        return -2;
-    }
-    const int bits = g.bits;
-    const uint32_t bins = 1u << bits;
+    st.n_r = q.nR; st.n_s = q.nS; st.radix_bits = q.bits;
+    *q.matches = 0;
+    if (q.ctx_out) *q.ctx_out = nullptr;
+    return 0;
+}
 
+// the resident variant of the fused kernels: only when an average bucket could fit beside the index (~7.4 K tuples)
+static bool resident(uint64_t nmin, uint32_t bins) { return nmin / bins <= 7000 && !g.no_resident; }
+
+// fused kernels: workgroups are persistent (ticket loop) and the LDS request leaves room for one per CU
+static unsigned fused_grid(uint64_t unit_bound) { return (unsigned)(unit_bound < (uint64_t)g.cus ? unit_bound : (uint64_t)g.cus); }
+
+// The plan's workspace (grown here, the histograms last) and its and the join kernels' arguments: 2^bits buckets over partR /
+// partS with histograms and offsets in hb ([2][bins] each, R's then S's), LDS-indexed build sides of up to lds_cap tuples, span
+// probe tuples a unit, and on the split paths the side choice of the caller's bucket (parent_mask / parent_flip, else 0 / null).
+static int plan_args(uint64_t nR, uint64_t nS, int bits, Buf &hb, uint32_t lds_cap, uint32_t span, uint32_t parent_mask,
+                     const uint8_t *parent_flip, PlanArgs &pa, JoinArgs &ja)
+{
+    const uint32_t bins = 1u << bits;
+    const uint64_t nmin = nR < nS ? nR : nS;
+    const uint64_t max_units = (uint64_t)bins + (nR + nS) / PR_UNIT + 2;
+    const uint64_t max_bunits = (uint64_t)bins + nmin / BUILD_CHUNK + 2;
+    if (ensure(g.units, max_units * sizeof(Unit)) || ensure(g.bunits, max_bunits * sizeof(Unit)) || ensure(g.ldsb, (size_t)bins * 4) ||
+        ensure(g.meta, (size_t)bins * sizeof(BucketMeta)) || ensure(g.summary, sizeof(PlanSummary) + 64) ||
+        ensure(g.ucount, max_units * 8) || ensure(g.ubase, max_units * 8) || ensure(g.uflag, max_units * 4) ||
+        ensure(hb, (size_t)4 * bins * 8))
+        return -1;
+    uint64_t *hist = (uint64_t *)hb.p, *psum = hist + 2 * bins;
+    pa.histR = hist; pa.histS = hist + bins;
+    pa.units = (Unit *)g.units.p; pa.build_units = (Unit *)g.bunits.p; pa.lds_buckets = (uint32_t *)g.ldsb.p;
+    pa.meta = (BucketMeta *)g.meta.p; pa.summary = (PlanSummary *)g.summary.p;
+    pa.lds_cap = lds_cap; pa.lds_max_slots = LDS_MAX_SLOTS; pa.build_chunk = BUILD_CHUNK; pa.span_lds = span;
+    pa.parent_mask = parent_mask; pa.parent_flip = parent_flip; pa.zero = nullptr; pa.zero_words = 0;
+    ja.partR = (const rhj_tuple *)g.partR.p; ja.partS = (const rhj_tuple *)g.partS.p;
+    ja.histR = hist; ja.histS = hist + bins; ja.psumR = psum; ja.psumS = psum + bins;
+    ja.units = (const Unit *)g.units.p; ja.meta = (const BucketMeta *)g.meta.p; ja.summary = (const PlanSummary *)g.summary.p;
+    ja.tab32 = nullptr; ja.tab64 = nullptr;
+    ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p; ja.unit_flag = (uint32_t *)g.uflag.p;
+    ja.out = nullptr; ja.out_capacity = 0;
+    ja.parent_mask = parent_mask; ja.parent_flip = parent_flip;
+    ja.stash_cnt = nullptr; ja.stash_row = nullptr; ja.stash_nR = nR;
+    return 0;
+}
+
+// The fused kernels' workspace (grown in this order: stash, status_bytes of ticket and status words, overflow lists, walk list)
+// and their arguments but fa.j.  lr_mode: the split paths' form; host_summary: the small path's pinned summary (else null).
+static int fused_args(uint64_t nR, uint64_t nS, int bits, uint64_t unit_bound, uint64_t status_bytes, uint32_t lr_mode,
+                      uint64_t *host_summary, FusedArgs &fa)
+{
+    if (ensure(g.stash_cnt, nR + nS + 64) || ensure(g.stash_row, (nR + nS + 8) * 8) || ensure(g.status, status_bytes) ||
+        ensure(g.ovf, fj_ovf_bytes((size_t)g.cus)) || ensure(g.ovf_base, (size_t)g.cus * 2 * FJ_GROUPS * 16 * 4) ||
+        ensure(g.walk, (unit_bound + 1) * sizeof(FjWalkItem)))
+        return -1;
+    fa.stash_cnt = (uint8_t *)g.stash_cnt.p; fa.stash_row = (uint64_t *)g.stash_row.p;
+    fa.status = (uint64_t *)g.status.p + 8;               // words 0..7 hold the ticket
+    fa.ticket = (uint32_t *)g.status.p;
+    fa.nR = nR;
+    fa.allow_resident = lr_mode ? 0 : !g.no_resident; fa.radix_bits = (uint32_t)bits; fa.lr_mode = lr_mode; fa.spec = 0; fa.xrows = nullptr;
+    fa.unit_bound = unit_bound; fa.host_summary = host_summary; fa.dbg = nullptr;
+    fa.ovf = (uint64_t *)g.ovf.p; fa.ovf_base = (uint32_t *)g.ovf_base.p; fa.walk = (FjWalkItem *)g.walk.p;
+    return 0;
+}
+
+// The pairs' buffer of the small and fused paths, whose join kernel counts them itself: the caller's, or with use_ctx_out the
+// context's own, of at least max(nR, nS) + 1024 pairs before the kernel ...
+static int out_guess(const JoinReq &q, rhj_result_tuple *&out, uint64_t &cap)
+{
+    out = q.out; cap = q.out_capacity;
+    if (!q.use_ctx_out) return 0;
+    if (ensure(g.out, ((q.nR > q.nS ? q.nR : q.nS) + 1024) * sizeof(rhj_result_tuple))) return -1;
+    out = (rhj_result_tuple *)g.out.p;
+    cap = g.out.cap / sizeof(rhj_result_tuple);
+    return 0;
+}
+
+// ... and grown to the kernel's M when that was short: 1 = launch the kernel again, 0 = the pairs are in place, -1 = error
+static int out_grow(const JoinReq &q, uint64_t M, rhj_result_tuple *&out, uint64_t &cap)
+{
+    if (!q.use_ctx_out || M <= cap) return 0;
+    if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;    // rare: fan-out above the guess
+    out = (rhj_result_tuple *)g.out.p;
+    cap = M;
+    return 1;
+}
+
+// The pairs' buffer of the paths that learn M before they write: the context's own, grown to M pairs (use_ctx_out), or the
+// caller's, rc 1 when M passes its capacity (the first out_capacity pairs are written).
+static int out_exact(const JoinReq &q, uint64_t M, rhj_result_tuple *&out, uint64_t &cap, int &rc)
+{
+    out = q.out; cap = q.out_capacity; rc = 0;
+    if (q.use_ctx_out) {
+        if (ensure(g.out, (M ? M : 1) * sizeof(rhj_result_tuple))) return -1;
+        out = (rhj_result_tuple *)g.out.p;
+        cap = M;
+        if (q.ctx_out) *q.ctx_out = out;
+    } else if (M > cap) {
+        rc = 1;
+    }
+    return 0;
+}
+
+// the end of a small (path 3) or fused (path 1) join: stats, *matches, *ctx_out; rc 1 when the caller's buffer was short
+static int fused_epilogue(const JoinReq &q, const PlanSummary &plan, uint64_t M, rhj_result_tuple *out, uint64_t cap, int path)
+{
+    rhj_stats &st = g.stats;
+    st.units = plan.units; st.hbm_units = 0; st.max_build = plan.max_build;
+    st.reserved = path;                                // path id (stats()["path"])
+    *q.matches = M;
+    st.matches = M;
+    if (q.ctx_out) *q.ctx_out = out;
+    if (path == 3) {
+        st.ms_hist = stage_ms(ST_HIST, ST_SCATTER);
+        st.ms_scan = 0.f;                              // no scan launch: every scatter workgroup sums the columns it needs
+        st.ms_scatter = stage_ms(ST_SCATTER, ST_PROBE);
+    } else {
+        st.ms_hist = stage_ms(ST_HIST, ST_SCAN);
+        st.ms_scan = stage_ms(ST_SCAN, ST_SCATTER);
+        st.ms_scatter = stage_ms(ST_SCATTER, ST_PLAN);
+        st.ms_plan = stage_ms(ST_PLAN, ST_PROBE);
+    }
+    st.ms_probe = stage_ms(ST_PROBE, ST_END);
+    st.ms_total = stage_ms(ST_HIST, ST_END);
+    return (!q.use_ctx_out && out && M > cap) ? 1 : 0;
+}
+
+// What the small, fused and tiled paths of one join share (join_setup): decisions on its sizes, partition state, kernel arguments
+struct JoinSetup {
+    int       bits;
+    uint32_t  bins;
+    uint64_t  nmin;
+    bool      small;           // the small path takes the join
+    bool      want_fused;      // the fused path runs behind the partition (else the tiled path)
+    bool      wide;            // the partition keeps 16-byte tuples (forced, or for the tiled path, which reads rhj_tuple)
+    uint64_t  unit_bound;      // fused path: the host-side bound on the unit count
+    uint64_t  status_bytes;    // fused path: its ticket and status words
     PartState ps;
+    PlanArgs  pa;
+    JoinArgs  ja;
+};
+
+// What the small and fused paths return besides 0 / 1 (done; 1: the caller's buffer was short) and -1: RUN_WIDE, wide row ids
+// met the 12-byte kernels (the join runs again wide), or the tiled path's handover — the plan in place, or a plan of fused-sized
+// units after the small path (which recorded no partition stages) or the fused path, to be made again with tile-granular ones.
+enum { RUN_WIDE = 3, TILED_PLANNED, TILED_AFTER_SMALL, TILED_AFTER_FUSED };
+
+static uint32_t sm_tiles(uint64_t n) { return (uint32_t)((n + SM_TILE - 1) / SM_TILE); }
+
+static int join_setup(const JoinReq &q, bool force_wide, JoinSetup &s)
+{
+    const uint64_t nR = q.nR, nS = q.nS;
+    const int bits = s.bits = q.bits;
+    const uint32_t bins = s.bins = 1u << bits;
+    PartState &ps = s.ps;
     if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple))) return -1;
-    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
-    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
-    const bool ranged = g.range_span != 0;                // a rank's share of a sharded join: the partition drops the other buckets
-    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; }
+    ps.r[0] = RelArgs{q.R, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
+    ps.r[1] = RelArgs{q.S, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = q.range_lo; ps.r[i].range_span = q.range_span; }   // a rank's share of a sharded join: the partition drops the other buckets
     ps.tmp[0] = ps.tmp[1] = nullptr;
+    ps.cols_input = q.cols_input;
     if (bits > PT_MAX_BITS) {
         if (ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple))) return -1;
         ps.tmp[0] = (rhj_tuple *)g.tmpR.p; ps.tmp[1] = (rhj_tuple *)g.tmpS.p;
     }
-    // ---- plan arguments (the plan runs behind the partition; a small one-pass partition runs it in its scan launch)
-    const uint32_t build_chunk = 4096;
     // Thousands of buckets of a few hundred tuples: a fused unit costs ~15 us whatever its size (a dozen barriers and
     // dependent round trips, one unit per CU at a time), the tiled path's 256-thread probe units run eight to a CU —
     // 1M x 1M at 15 bits 2.2 ms fused, 0.88 ms tiled; from ~512 tuples per bucket on the fused path is ahead again
     // (tools/exp_twopass_sizes.py).  rhj_set_fused(2) keeps the fused path regardless.
     const bool tiny_buckets = bins >= 4096 && (nR > nS ? nR : nS) < (uint64_t)512 * bins;
-    const bool want_fused = !g.no_fused && !g.force_hbm && (g.force_fused || !tiny_buckets);
-    const uint32_t lds_max_slots = LDS_BUDGET / 4 / 4 * 4;                 // tiled path: k_build_lds owns the whole LDS
-    uint32_t lds_cap = (uint32_t)((uint64_t)lds_max_slots * 4 / 5);        // load factor <= 0.8
-    if (want_fused) lds_cap = (LDS_BUDGET - FJ_LDS_EXTRA - 128) * 2 / 9;   // fused: 4 B entry + >= 0.5 B of slot starts per build tuple
-    if (lds_cap > 65534) lds_cap = 65534;                                  // 16-bit position + 1
-    if (g.force_hbm) lds_cap = 0;
-    const uint64_t nmin = nR < nS ? nR : nS;
-    const uint64_t max_units = (uint64_t)bins + (nR + nS) / PR_UNIT + 2;
-    const uint64_t max_bunits = (uint64_t)bins + nmin / build_chunk + 2;
-    const uint64_t max_tab32 = nmin + nmin / 2 + (uint64_t)80 * bins + 64;
-    if (ensure(g.units, max_units * sizeof(Unit)) || ensure(g.bunits, max_bunits * sizeof(Unit)) ||
-        ensure(g.ldsb, (size_t)bins * 4) || ensure(g.meta, (size_t)bins * sizeof(BucketMeta)) ||
-        ensure(g.summary, sizeof(PlanSummary) + 64) || ensure(g.ucount, max_units * 8) || ensure(g.ubase, max_units * 8) ||
-        ensure(g.uflag, max_units * 4) || ensure(g.histpsum, (size_t)4 * bins * 8))
-        return -1;
-    PlanArgs pa;
-    pa.histR = (uint64_t *)g.histpsum.p; pa.histS = pa.histR + bins;
-    pa.units = (Unit *)g.units.p; pa.build_units = (Unit *)g.bunits.p; pa.lds_buckets = (uint32_t *)g.ldsb.p;
-    pa.meta = (BucketMeta *)g.meta.p; pa.summary = (PlanSummary *)g.summary.p;
-    pa.lds_cap = lds_cap; pa.lds_max_slots = lds_max_slots; pa.build_chunk = build_chunk;
-    pa.parent_mask = 0; pa.parent_flip = nullptr; pa.zero = nullptr; pa.zero_words = 0;
-    const bool sliced = ranged && (g.slice_skip != 0 || g.slice_end != 0);
-    if (sliced) {
-        if (g.slice_skip) { pa.slice_b0 = g.range_lo; pa.slice_o0 = g.slice_skip; }
-        if (g.slice_end) { pa.slice_b1 = g.range_lo + g.range_span - 1u; pa.slice_o1 = g.slice_end; }
-    }
+    s.want_fused = !g.no_fused && !g.force_hbm && (g.force_fused || !tiny_buckets);
+    // the fused path reads 12-byte partitioned tuples when the row ids fit 32 bits; the tiled path reads rhj_tuple
+    s.wide = force_wide || !s.want_fused;
+    s.nmin = nR < nS ? nR : nS;
     // probe tuples per fused unit: whole buckets when there are plenty of them, smaller spans (each unit
     // rebuilds its bucket's index) when a low radix would otherwise leave most CUs idle
     uint32_t fused_span = FJ_SPAN;
@@ -564,296 +719,225 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
         if (want < FJ_BATCH) want = FJ_BATCH;
         if (want < fused_span) fused_span = (uint32_t)want;
     }
-    pa.span_lds = want_fused ? fused_span : PR_UNIT;
-
-    // the fused path reads 12-byte partitioned tuples when the row ids fit 32 bits; the tiled path reads rhj_tuple
-    if (!want_fused) force_wide = true;
-    ps.plan = &pa;
+    const uint32_t lds_cap = s.want_fused ? FUSED_LDS_CAP : g.force_hbm ? 0 : LDS_MAX_SLOTS * 4 / 5;     // tiled: load factor <= 0.8
+    if (plan_args(nR, nS, bits, g.histpsum, lds_cap, s.want_fused ? fused_span : PR_UNIT, 0, nullptr, s.pa, s.ja)) return -1;
+    // the plan runs behind the partition (a small one-pass partition runs it in its scan launch)
     ps.hist = (uint64_t *)g.histpsum.p;
     ps.psum = ps.hist + 2 * bins;
-    PlanSummary *hs = (PlanSummary *)g.pin;
+    ps.plan = &s.pa;
+    if (q.slice_skip) { s.pa.slice_b0 = q.range_lo; s.pa.slice_o0 = q.slice_skip; }      // (a slice is always a share: join_range)
+    if (q.slice_end) { s.pa.slice_b1 = q.range_lo + q.range_span - 1u; s.pa.slice_o1 = q.slice_end; }
+    s.unit_bound = (uint64_t)bins + (nR + nS) / fused_span + 2;
+    s.status_bytes = (s.unit_bound + 1) * 8 + 64;
+    s.small = s.want_fused && bits <= PT_MAX_BITS && !g.no_small && !q.range_span && sm_tiles(nR) <= g.small_tiles &&
+              sm_tiles(nS) <= g.small_tiles && !g.stamps;
+    return 0;
+}
+
+// ---- small joins (rhj_small.hip.h): two launches for the partition — the plan rides in the second — and the fused join
+// third; no host memset, no total kernel, no read-back copy.
+static int join_small(const JoinReq &q, JoinSetup &s)
+{
+    const int bits = s.bits;
+    const uint64_t status_words = s.unit_bound + 1 + 8;                 // 8 ticket words in front
+    RelArgs a0 = s.ps.r[0], a1 = s.ps.r[1];
+    a0.tiles = sm_tiles(q.nR); a1.tiles = sm_tiles(q.nS);
+    FusedArgs fa;
+    if (ensure(g.cntR, (size_t)a0.tiles * 256 * 4) || ensure(g.cntS, (size_t)a1.tiles * 256 * 4) ||
+        fused_args(q.nR, q.nS, bits, s.unit_bound, status_words * 8 + 64, 0, (uint64_t *)&g.pin->summary, fa))
+        return -1;
+    a0.cnt = (uint32_t *)g.cntR.p; a1.cnt = (uint32_t *)g.cntS.p;
+    rhj_result_tuple *out;
+    uint64_t cap;
+    if (out_guess(q, out, cap)) return -1;
+    const uint32_t max_tiles = a0.tiles > a1.tiles ? a0.tiles : a1.tiles;
+    const unsigned fgrid = fused_grid(s.unit_bound);
+    // relations of one or two tiles: the scatter workgroups count the digits themselves, two launches in all
+    const int self_hist = max_tiles <= SM_SELF_TILES;
     PlanSummary plan;
-
-    JoinArgs ja;
-    ja.partR = (const rhj_tuple *)g.partR.p; ja.partS = (const rhj_tuple *)g.partS.p;
-    ja.histR = ps.hist; ja.histS = ps.hist + bins; ja.psumR = ps.psum; ja.psumS = ps.psum + bins;
-    ja.units = (const Unit *)g.units.p; ja.meta = (const BucketMeta *)g.meta.p;
-    ja.summary = (const PlanSummary *)g.summary.p;
-    ja.tab32 = nullptr; ja.tab64 = nullptr;
-    ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p;
-    ja.unit_flag = (uint32_t *)g.uflag.p;
-    ja.out = nullptr; ja.out_capacity = 0;
-    ja.parent_mask = 0; ja.parent_flip = nullptr;
-    ja.stash_cnt = nullptr; ja.stash_row = nullptr; ja.stash_nR = nR;
-
-    // ---- small joins: two launches for the partition (the plan rides in the second), the fused join third, and
-    // no host memset, no total kernel, no read-back copy (rhj_small.hip.h)
-    bool partitioned = false;      // the small path partitioned and planned, but some bucket needs the tiled path
-    const uint32_t stilesR = (uint32_t)((nR + SM_TILE - 1) / SM_TILE), stilesS = (uint32_t)((nS + SM_TILE - 1) / SM_TILE);
-    if (want_fused && bits <= PT_MAX_BITS && !g.no_small && !ranged && stilesR <= g.small_tiles && stilesS <= g.small_tiles &&
-        !g.stamps) {
-        const uint64_t unit_bound = (uint64_t)bins + (nR + nS) / fused_span + 2;
-        const uint64_t status_words = unit_bound + 1 + 8;                 // 8 ticket words in front
-        RelArgs a0 = ps.r[0], a1 = ps.r[1];
-        a0.tiles = stilesR; a1.tiles = stilesS;
-        if (ensure(g.cntR, (size_t)a0.tiles * 256 * 4) || ensure(g.cntS, (size_t)a1.tiles * 256 * 4) ||
-            ensure(g.stash_cnt, nR + nS + 64) || ensure(g.stash_row, (nR + nS + 8) * 8) ||
-            ensure(g.status, status_words * 8 + 64) ||
-            ensure(g.ovf, fj_ovf_bytes((size_t)g.cus)) || ensure(g.ovf_base, (size_t)g.cus * 2 * FJ_GROUPS * 16 * 4) ||
-            ensure(g.walk, (unit_bound + 1) * sizeof(FjWalkItem)))
-            return -1;
-        a0.cnt = (uint32_t *)g.cntR.p; a1.cnt = (uint32_t *)g.cntS.p;
-        FusedArgs fa;
-        fa.stash_cnt = (uint8_t *)g.stash_cnt.p; fa.stash_row = (uint64_t *)g.stash_row.p;
-        fa.status = (uint64_t *)g.status.p + 8;
-        fa.ticket = (uint32_t *)g.status.p;
-        fa.nR = nR;
-        fa.allow_resident = !g.no_resident; fa.radix_bits = (uint32_t)bits; fa.lr_mode = 0; fa.spec = 0; fa.xrows = nullptr;
-        fa.unit_bound = unit_bound;
-        fa.host_summary = (uint64_t *)g.pin;
-        fa.dbg = nullptr;
-        fa.ovf = (uint64_t *)g.ovf.p; fa.ovf_base = (uint32_t *)g.ovf_base.p; fa.walk = (FjWalkItem *)g.walk.p;
-        const uint32_t fused_lds = LDS_BUDGET - FJ_LDS_EXTRA;
-        if (use_ctx_out) {
-            const uint64_t guess = (nR > nS ? nR : nS) + 1024;
-            if (g.out.cap < guess * sizeof(rhj_result_tuple) && ensure(g.out, guess * sizeof(rhj_result_tuple))) return -1;
-            out = (rhj_result_tuple *)g.out.p;
-            out_capacity = g.out.cap / sizeof(rhj_result_tuple);
-        }
-        const uint32_t max_tiles = a0.tiles > a1.tiles ? a0.tiles : a1.tiles;
-        const unsigned fgrid = (unsigned)(unit_bound < (uint64_t)g.cus ? unit_bound : (uint64_t)g.cus);
-        bool small_done = false;
-        uint64_t M = 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            ja.out = out; ja.out_capacity = out ? out_capacity : 0;
-            fa.j = ja;
-            RHJ_STAGE(ST_HIST);
-            // relations of one or two tiles: the scatter workgroups count the digits themselves, two launches in all
-            const int self_hist = max_tiles <= SM_SELF_TILES;
-            if (!self_hist)
-                RHJ_LAUNCH(k_small_hist, dim3(max_tiles, 2), dim3(SM_BLOCK), 0, g.stream, a0, a1, bits, (uint64_t *)g.status.p, status_words);
-            RHJ_STAGE(ST_SCATTER);
-            RHJ_LAUNCH(k_small_scatter, dim3(max_tiles + 1, 2), dim3(SM_BLOCK), small_lds_bytes(bits), g.stream, a0, a1, bits, ps.hist,
-                       ps.psum, pa, self_hist, (uint64_t *)g.status.p, status_words);
-            RHJ_STAGE(ST_PROBE);
-            if (nmin / bins <= 7000 && !g.no_resident)
-                RHJ_LAUNCH((k_join_fused<true, false>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-            else
-                RHJ_LAUNCH((k_join_fused<false, false>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-            RHJ_STAGE(ST_END);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            plan = *hs;                                // written by the join kernel's last workgroup (system-scope stores)
-            if (plan.fused_ok && out && ((const uint64_t *)g.pin)[sizeof(PlanSummary) / 8] != 0) {
-                // some unit's pairs need the index walked again (a probe tuple with more than 16 matches, ...): the host is
-                // waiting on this stream anyway, so the second kernel is launched only now — a launch that returns at once
-                // costs a 0.08 ms join 5 % (the two-pass path, whose joins are milliseconds, always enqueues it)
-                RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-                RHJ_STAGE(ST_END);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipStreamSynchronize(g.stream));
-            }
-            if (plan.fused_ok && plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
-            if (!plan.fused_ok) { partitioned = true; break; }
-            small_done = true;
-            M = plan.matches;
-            if (!use_ctx_out || M <= out_capacity) break;
-            if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;    // rare: fan-out above the guess
-            out = (rhj_result_tuple *)g.out.p;
-            out_capacity = M;
-        }
-        if (small_done) {
-            *overflow = false;
-            st.units = plan.units; st.hbm_units = 0; st.max_build = plan.max_build;
-            st.reserved = 3;
-            *matches = M;
-            st.matches = M;
-            if (ctx_out) *ctx_out = out;
-            st.ms_hist = stage_ms(ST_HIST, ST_SCATTER);
-            st.ms_scan = 0.f;                          // no scan launch: every scatter workgroup sums the columns it needs
-            st.ms_scatter = stage_ms(ST_SCATTER, ST_PROBE);
-            st.ms_probe = stage_ms(ST_PROBE, ST_END);
-            st.ms_total = stage_ms(ST_HIST, ST_END);
-            return (!use_ctx_out && out && M > out_capacity) ? 1 : 0;
-        }
-        if (use_ctx_out) { out = nullptr; out_capacity = 0; }
-    }
-
-    const uint64_t unit_bound = (uint64_t)bins + (nR + nS) / fused_span + 2;      // fused path: the host-side bound on the unit count
-    if (!partitioned) {
-        if (run_partition(ps, bits, 2, force_wide, want_fused && !force_wide)) return -1;
-        RHJ_STAGE(ST_PLAN);
-        if (want_fused) {                             // the plan clears the fused kernel's ticket and status words
-            if (ensure(g.status, (unit_bound + 1) * 8 + 64)) return -1;
-            pa.zero = (uint32_t *)g.status.p; pa.zero_words = (uint32_t)(((unit_bound + 1) * 8 + 64) / 4);
-        }
-        if (!ps.plan_done) RHJ_LAUNCH(k_plan, dim3(bits >= 11 ? 8 : 1), dim3(1024), 0, g.stream, pa, bits);
-        else if (want_fused) HIP_TRY(hipMemsetAsync(g.status.p, 0, (unit_bound + 1) * 8 + 64, g.stream));
-        pa.zero = nullptr; pa.zero_words = 0;
-    } else {
+    uint64_t M = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        s.ja.out = out; s.ja.out_capacity = out ? cap : 0;
+        fa.j = s.ja;
         RHJ_STAGE(ST_HIST);
-        RHJ_STAGE(ST_SCAN);
+        if (!self_hist)
+            RHJ_LAUNCH(k_small_hist, dim3(max_tiles, 2), dim3(SM_BLOCK), 0, g.stream, a0, a1, bits, (uint64_t *)g.status.p, status_words);
         RHJ_STAGE(ST_SCATTER);
-        RHJ_STAGE(ST_PLAN);
-        pa.span_lds = PR_UNIT;                         // plan again with tile-granular units
-        RHJ_LAUNCH(k_plan, dim3(1), dim3(1024), 0, g.stream, pa, bits);
-    }
-
-    if (want_fused && !partitioned) {
-        // ---- fused LDS path: build + probe + emit in one kernel, chained output offsets.  Launched
-        // without waiting for the plan: the grid is the host-side upper bound on the unit count, the
-        // LDS allocation the maximum, and the kernel itself returns when the plan found a bucket that
-        // does not fit LDS (then the tiled path below takes over).  One host sync per join.
-        if (ensure(g.stash_cnt, nR + nS + 64) || ensure(g.stash_row, (nR + nS + 8) * 8) ||
-            ensure(g.status, (unit_bound + 1) * 8 + 64) ||
-            ensure(g.ovf, fj_ovf_bytes((size_t)g.cus)) || ensure(g.ovf_base, (size_t)g.cus * 2 * FJ_GROUPS * 16 * 4) ||
-            ensure(g.walk, (unit_bound + 1) * sizeof(FjWalkItem)))
-            return -1;
-        FusedArgs fa;
-        fa.stash_cnt = (uint8_t *)g.stash_cnt.p; fa.stash_row = (uint64_t *)g.stash_row.p;
-        fa.status = (uint64_t *)g.status.p + 8;               // words 0..7 hold the ticket
-        fa.ticket = (uint32_t *)g.status.p;
-        fa.nR = nR;
-        fa.allow_resident = !g.no_resident; fa.radix_bits = (uint32_t)bits; fa.lr_mode = 0; fa.spec = 0; fa.xrows = nullptr;
-        fa.unit_bound = unit_bound;
-        fa.host_summary = nullptr;
-        fa.dbg = nullptr;
-        fa.ovf = (uint64_t *)g.ovf.p; fa.ovf_base = (uint32_t *)g.ovf_base.p; fa.walk = (FjWalkItem *)g.walk.p;
-        if (g.stamps) {                                       // diagnostic runs only
-            if (ensure(g.dbg, (unit_bound + 1) * 64)) return -1;
-            fa.dbg = (uint64_t *)g.dbg.p;
-        }
-        uint64_t M = 0;
-        const uint32_t fused_lds = LDS_BUDGET - FJ_LDS_EXTRA;
-        if (use_ctx_out) {
-            const uint64_t guess = (nR > nS ? nR : nS) + 1024;
-            if (g.out.cap < guess * sizeof(rhj_result_tuple) && ensure(g.out, guess * sizeof(rhj_result_tuple))) return -1;
-            out = (rhj_result_tuple *)g.out.p;
-            out_capacity = g.out.cap / sizeof(rhj_result_tuple);
-        }
-        RHJ_STAGE(ST_PROBE);                          // (no separate build / count / offsets stages on this path)
-        bool fused_done = false;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            ja.out = out; ja.out_capacity = out ? out_capacity : 0;
-            fa.j = ja;
-            if (attempt) HIP_TRY(hipMemsetAsync(g.status.p, 0, (unit_bound + 1) * 8 + 64, g.stream));   // (first: cleared by the plan)
-            // workgroups are persistent (ticket loop) and the LDS request leaves room for one per CU
-            const unsigned fgrid = (unsigned)(unit_bound < (uint64_t)g.cus ? unit_bound : (uint64_t)g.cus);
-            // the resident variant only when an average bucket could fit beside the index (~7.4 K tuples)
-            // The stash width follows the partition's row-id decision (summary->wide_row_ids, known only on the device):
-            // the instantiation that does not match returns at once, and the 16-byte one is launched only when the
-            // partition's 16-byte kernels were (one-pass partitions, forced-wide runs, a process that has seen wide row ids).
-            const bool maybe_narrow = bits > PT_MAX_BITS && !force_wide;
-            const bool maybe_wide = !maybe_narrow || ps.launch_wide;
-            // The foreign-key speculation (k_join_spec): the bigger relation's tuples have one match each?  Then nothing is
-            // stashed for the units that relation probes and nothing is chained.  Tried while it keeps holding; a failed try
-            // costs the time to the first unit that notices (tens of microseconds), so after failures only every 16th join tries.
-            // (A buffer below the relation's size is no obstacle: pairs beyond it are dropped as on every path and the caller hears
-            // the count.  A rank's share of a sharded join — rhj_join_device_range — has a buffer for its share and buckets of the
-            // whole join's size: the per-bucket rule is the same.)
-            // (Not on a slice: a bucket cut between two devices has units that start inside it, and the last workgroup's check
-            // adds up to the whole relation.)
-            bool try_spec = attempt == 0 && maybe_narrow && out != nullptr && g.no_spec <= 0 && !sliced &&
-                            (nS >= nR ? nS : nR) / bins >= 4096;     // (units of 2.4 K tuples: 10M x 10M at 12 bits lost 7 % to its per-unit extras)
-            if (try_spec && g.spec_score <= 0 && g.no_spec >= 0 && ++g.spec_skipped < 16) try_spec = false;   // (RHJ_NO_SPEC=-1: always try — to time a failing one)
-            fa.spec = try_spec ? (nS >= nR ? 1u : 2u) : 0u;
-            // k_join_exact (rhj_join_exact.hip.h) runs the speculation over an index that needs no verifying gather: build sides
-            // the gather kernels would take (beyond the LDS-resident ones), enough radix bits for its slots to make the 40 stored
-            // hash bits exact.  It hands over (ticket[4], reason in ticket[5]) what it does not take; a join it handed back for
-            // its INPUT (row ids that do not increase, a bucket beyond its index) makes the next eligible joins skip it.
-            bool try_exact = try_spec && g.no_exact <= 0 && !(nmin / bins <= 7000 && !g.no_resident) && bits >= 10 &&
-                             nmin / bins <= XJ_MAX_BUILD;
-            if (try_exact && g.exact_score <= 0 && g.no_exact >= 0 && ++g.exact_skipped < 16) try_exact = false;
-            if (try_exact) {
-                if (ensure(g.xrows, (size_t)g.cus * XJ_SCRATCH * 4)) return -1;
-                fa.xrows = (uint32_t *)g.xrows.p;
-                g.exact_skipped = 0;
-            }
-            if (try_spec) {
-                g.spec_skipped = 0;
-                if (try_exact)
-                    RHJ_LAUNCH(k_join_exact, dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-                else if (nmin / bins <= 7000 && !g.no_resident)
-                    RHJ_LAUNCH((k_join_spec<true>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-                else
-                    RHJ_LAUNCH((k_join_spec<false>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-            }
-            if (nmin / bins <= 7000 && !g.no_resident) {
-                if (maybe_narrow)
-                    RHJ_LAUNCH((k_join_fused<true, true>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-                if (maybe_wide)
-                    RHJ_LAUNCH((k_join_fused<true, false>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-            } else {
-                if (maybe_narrow)
-                    RHJ_LAUNCH((k_join_fused<false, true>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-                if (maybe_wide)
-                    RHJ_LAUNCH((k_join_fused<false, false>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-            }
-            RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);   // returns at once when no unit needs it
+        RHJ_LAUNCH(k_small_scatter, dim3(max_tiles + 1, 2), dim3(SM_BLOCK), small_lds_bytes(bits), g.stream, a0, a1, bits, s.ps.hist,
+                   s.ps.psum, s.pa, self_hist, (uint64_t *)g.status.p, status_words);
+        RHJ_STAGE(ST_PROBE);
+        if (resident(s.nmin, s.bins))
+            RHJ_LAUNCH((k_join_fused<true, false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        else
+            RHJ_LAUNCH((k_join_fused<false, false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        RHJ_STAGE(ST_END);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        plan = g.pin->summary;                         // written by the join kernel's last workgroup (system-scope stores)
+        if (plan.fused_ok && out && g.pin->walk_units != 0) {
+            // some unit's pairs need the index walked again (a probe tuple with more than 16 matches, ...): the host is
+            // waiting on this stream anyway, so the second kernel is launched only now — a launch that returns at once
+            // costs a 0.08 ms join 5 % (the fused path, whose joins are milliseconds, always enqueues it)
+            RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
             RHJ_STAGE(ST_END);
-            HIP_TRY(hipMemcpyAsync(hs, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
-            uint32_t *spec_words = (uint32_t *)((char *)g.pin + 512);       // the ticket words: word 4 = the speculation failed
-            if (try_spec) HIP_TRY(hipMemcpyAsync(spec_words, g.status.p, 32, hipMemcpyDeviceToHost, g.stream));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(g.stream));
-            plan = *hs;
-            g.last_spec = 0;
-            g.last_exact = 0;
-            if (try_spec) {
-                const bool held = spec_words[4] == 0;
-                const bool not_taken = try_exact && !held && spec_words[5] == 2;     // k_join_exact's input, not the hypothesis
-                g.last_spec = held ? 1 : 2;
-                if (try_exact) {
-                    g.last_exact = held ? 1 : 2;
-                    g.exact_score = not_taken ? g.exact_score - 2 : (g.exact_score < 4 ? g.exact_score + 1 : 4);
-                    if (g.exact_score < -2) g.exact_score = -2;
-                }
-                if (!not_taken) {
-                    g.spec_score = held ? (g.spec_score < 4 ? g.spec_score + 1 : 4) : g.spec_score - 2;
-                    if (g.spec_score < -2) g.spec_score = -2;
-                }
-            }
-            if (plan.row_id_overflow) { *overflow = true; return 0; }     // (also: wide row ids met the 12-byte kernels alone)
-            if (plan.fused_ok && plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
-            if (!plan.fused_ok) {
-                // a bucket needs the tiled path, which reads 16-byte tuples: partition again wide if this one was narrow
-                if (bits > PT_MAX_BITS && !force_wide && !plan.wide_row_ids) { *overflow = true; return 0; }
-                break;
-            }
-            fused_done = true;
-            M = plan.matches;
-            if (!use_ctx_out || M <= out_capacity) break;
-            if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;    // rare: fan-out above the guess
-            out = (rhj_result_tuple *)g.out.p;
-            out_capacity = M;
         }
-        if (fused_done) {
-            *overflow = plan.row_id_overflow != 0;
-            st.units = plan.units; st.hbm_units = 0; st.max_build = plan.max_build;
-            st.reserved = 1;
-            *matches = M;
-            st.matches = M;
-            if (ctx_out) *ctx_out = out;
-            st.ms_hist = stage_ms(ST_HIST, ST_SCAN);
-            st.ms_scan = stage_ms(ST_SCAN, ST_SCATTER);
-            st.ms_scatter = stage_ms(ST_SCATTER, ST_PLAN);
-            st.ms_plan = stage_ms(ST_PLAN, ST_PROBE);
-            st.ms_probe = stage_ms(ST_PROBE, ST_END);
-            st.ms_total = stage_ms(ST_HIST, ST_END);
-            return (!use_ctx_out && out && M > out_capacity) ? 1 : 0;
-        }
-        // some bucket needs an HBM table: plan again with tile-granular units
-        pa.span_lds = PR_UNIT;
-        RHJ_LAUNCH(k_plan, dim3(1), dim3(1024), 0, g.stream, pa, bits);
-        if (use_ctx_out) { out = nullptr; out_capacity = 0; }
+        if (plan.fused_ok && plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
+        if (!plan.fused_ok) return TILED_AFTER_SMALL;  // partitioned and planned, but some bucket needs the tiled path
+        M = plan.matches;
+        const int again = out_grow(q, M, out, cap);
+        if (again < 0) return -1;
+        if (!again) break;
     }
+    return fused_epilogue(q, plan, M, out, cap, 3);
+}
+
+// The partition of both relations and the plan behind it, which clears the fused path's ticket and status words on the way
+// (a memset does when a small one-pass partition ran the plan in its scan launch).
+static int partition_plan(JoinSetup &s)
+{
+    if (run_partition(s.ps, s.bits, 2, s.wide, s.want_fused && !s.wide)) return -1;
+    RHJ_STAGE(ST_PLAN);
+    PlanArgs pa = s.pa;
+    if (s.want_fused) {
+        if (ensure(g.status, s.status_bytes)) return -1;
+        pa.zero = (uint32_t *)g.status.p; pa.zero_words = (uint32_t)(s.status_bytes / 4);
+    }
+    if (!s.ps.plan_done) RHJ_LAUNCH(k_plan, dim3(s.bits >= 11 ? 8 : 1), dim3(1024), 0, g.stream, pa, s.bits);
+    else if (s.want_fused) HIP_TRY(hipMemsetAsync(g.status.p, 0, s.status_bytes, g.stream));
+    return 0;
+}
+
+// ---- fused LDS path: build + probe + emit in one kernel, chained output offsets.  Launched without waiting for the plan:
+// the grid is the host-side upper bound on the unit count, the LDS allocation the maximum, and the kernel itself returns when
+// the plan found a bucket that does not fit LDS (then the tiled path takes over).  One host sync per join.
+static int join_fused(const JoinReq &q, JoinSetup &s)
+{
+    const uint64_t nR = q.nR, nS = q.nS;
+    const int bits = s.bits;
+    FusedArgs fa;
+    if (fused_args(nR, nS, bits, s.unit_bound, s.status_bytes, 0, nullptr, fa)) return -1;
+    if (g.stamps) {                                       // diagnostic runs only
+        if (ensure(g.dbg, (s.unit_bound + 1) * 64)) return -1;
+        fa.dbg = (uint64_t *)g.dbg.p;
+    }
+    rhj_result_tuple *out;
+    uint64_t cap;
+    if (out_guess(q, out, cap)) return -1;
+    RHJ_STAGE(ST_PROBE);                          // (no separate build / count / offsets stages on this path)
+    const unsigned fgrid = fused_grid(s.unit_bound);
+    const bool res = resident(s.nmin, s.bins);
+    // The stash width follows the partition's row-id decision (summary->wide_row_ids, known only on the device):
+    // the instantiation that does not match returns at once, and the 16-byte one is launched only when the
+    // partition's 16-byte kernels were (one-pass partitions, forced-wide runs, a process that has seen wide row ids).
+    const bool maybe_narrow = bits > PT_MAX_BITS && !s.wide;
+    const bool maybe_wide = !maybe_narrow || s.ps.launch_wide;
+    PlanSummary plan;
+    uint64_t M = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        s.ja.out = out; s.ja.out_capacity = out ? cap : 0;
+        fa.j = s.ja;
+        if (attempt) HIP_TRY(hipMemsetAsync(g.status.p, 0, s.status_bytes, g.stream));   // (first: cleared by the plan)
+        // The foreign-key speculation (k_join_spec): the bigger relation's tuples have one match each?  Then nothing is
+        // stashed for the units that relation probes and nothing is chained.  Tried while it keeps holding; a failed try
+        // costs the time to the first unit that notices (tens of microseconds), so after failures only every 16th join tries.
+        // (A buffer below the relation's size is no obstacle: pairs beyond it are dropped as on every path and the caller hears
+        // the count.  A rank's share of a sharded join — rhj_join_device_range — has a buffer for its share and buckets of the
+        // whole join's size: the per-bucket rule is the same.)
+        // (Not on a slice: a bucket cut between two devices has units that start inside it, and the last workgroup's check
+        // adds up to the whole relation.)
+        bool try_spec = attempt == 0 && maybe_narrow && out != nullptr && g.no_spec <= 0 && !q.slice_skip && !q.slice_end &&
+                        (nS >= nR ? nS : nR) / s.bins >= 4096;     // (units of 2.4 K tuples: 10M x 10M at 12 bits lost 7 % to its per-unit extras)
+        if (try_spec && g.spec_score <= 0 && g.no_spec >= 0 && ++g.spec_skipped < 16) try_spec = false;   // (RHJ_NO_SPEC=-1: always try — to time a failing one)
+        fa.spec = try_spec ? (nS >= nR ? 1u : 2u) : 0u;
+        // k_join_exact (rhj_join_exact.hip.h) runs the speculation over an index that needs no verifying gather: build sides
+        // the gather kernels would take (beyond the LDS-resident ones), enough radix bits for its slots to make the 40 stored
+        // hash bits exact.  It hands over (ticket[4], reason in ticket[5]) what it does not take; a join it handed back for
+        // its INPUT (row ids that do not increase, a bucket beyond its index) makes the next eligible joins skip it.
+        bool try_exact = try_spec && g.no_exact <= 0 && !res && bits >= 10 && s.nmin / s.bins <= XJ_MAX_BUILD;
+        if (try_exact && g.exact_score <= 0 && g.no_exact >= 0 && ++g.exact_skipped < 16) try_exact = false;
+        if (try_exact) {
+            if (ensure(g.xrows, (size_t)g.cus * XJ_SCRATCH * 4)) return -1;
+            fa.xrows = (uint32_t *)g.xrows.p;
+            g.exact_skipped = 0;
+        }
+        if (try_spec) {
+            g.spec_skipped = 0;
+            if (try_exact)
+                RHJ_LAUNCH(k_join_exact, dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+            else if (res)
+                RHJ_LAUNCH((k_join_spec<true>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+            else
+                RHJ_LAUNCH((k_join_spec<false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        }
+        if (res) {
+            if (maybe_narrow)
+                RHJ_LAUNCH((k_join_fused<true, true>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+            if (maybe_wide)
+                RHJ_LAUNCH((k_join_fused<true, false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        } else {
+            if (maybe_narrow)
+                RHJ_LAUNCH((k_join_fused<false, true>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+            if (maybe_wide)
+                RHJ_LAUNCH((k_join_fused<false, false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        }
+        RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);   // returns at once when no unit needs it
+        RHJ_STAGE(ST_END);
+        HIP_TRY(hipMemcpyAsync(&g.pin->summary, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
+        if (try_spec) HIP_TRY(hipMemcpyAsync(g.pin->ticket, g.status.p, sizeof(g.pin->ticket), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        plan = g.pin->summary;
+        g.last_spec = 0;
+        g.last_exact = 0;
+        if (try_spec) {
+            const bool held = g.pin->ticket[4] == 0;                          // word 4: the speculation failed
+            const bool not_taken = try_exact && !held && g.pin->ticket[5] == 2;   // k_join_exact's input, not the hypothesis
+            g.last_spec = held ? 1 : 2;
+            if (try_exact) {
+                g.last_exact = held ? 1 : 2;
+                g.exact_score = not_taken ? g.exact_score - 2 : (g.exact_score < 4 ? g.exact_score + 1 : 4);
+                if (g.exact_score < -2) g.exact_score = -2;
+            }
+            if (!not_taken) {
+                g.spec_score = held ? (g.spec_score < 4 ? g.spec_score + 1 : 4) : g.spec_score - 2;
+                if (g.spec_score < -2) g.spec_score = -2;
+            }
+        }
+        if (plan.row_id_overflow) return RUN_WIDE;     // (also: wide row ids met the 12-byte kernels alone)
+        if (plan.fused_ok && plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: fused join left no match total (chained scan incomplete)\n"); return -1; }
+        // a bucket needs the tiled path, which reads 16-byte tuples: partition again wide if this one was narrow
+        if (!plan.fused_ok) return bits > PT_MAX_BITS && !s.wide && !plan.wide_row_ids ? RUN_WIDE : TILED_AFTER_FUSED;
+        M = plan.matches;
+        const int again = out_grow(q, M, out, cap);
+        if (again < 0) return -1;
+        if (!again) break;
+    }
+    return fused_epilogue(q, plan, M, out, cap, 1);
+}
+
+// ---- tiled path: the tables (LDS- or HBM-built), a count pass, the output offsets, the emit pass.  `from`: how the plan
+// stands (the outcomes above).
+static int join_tiled(const JoinReq &q, JoinSetup &s, int from)
+{
+    if (from == TILED_AFTER_SMALL)
+        for (int e = ST_HIST; e <= ST_PLAN; ++e) RHJ_STAGE(e);
+    if (from != TILED_PLANNED) {
+        s.pa.span_lds = PR_UNIT;                       // plan again with tile-granular units
+        RHJ_LAUNCH(k_plan, dim3(1), dim3(1024), 0, g.stream, s.pa, s.bits);
+    }
+    rhj_stats &st = g.stats;
+    PlanSummary *hs = &g.pin->summary;
     HIP_TRY(hipMemcpyAsync(hs, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));                  // tiled path: launch geometry
-    plan = *hs;
+    HIP_TRY(hipStreamSynchronize(g.stream));                  // launch geometry
+    const PlanSummary plan = *hs;
     st.units = plan.units; st.hbm_units = plan.build_units; st.max_build = plan.max_build;
     st.table_slots = plan.hbm_slots + plan.tab32_slots;
 
-    if (ensure(g.tab32, max_tab32 * 4) || ensure(g.stash_cnt, nR + nS + 64) || ensure(g.stash_row, (nR + nS + 8) * 8)) return -1;
+    JoinArgs &ja = s.ja;
+    const uint64_t max_tab32 = s.nmin + s.nmin / 2 + (uint64_t)80 * s.bins + 64;
+    if (ensure(g.tab32, max_tab32 * 4) || ensure(g.stash_cnt, q.nR + q.nS + 64) || ensure(g.stash_row, (q.nR + q.nS + 8) * 8)) return -1;
     ja.tab32 = (uint32_t *)g.tab32.p;
     ja.stash_cnt = (uint8_t *)g.stash_cnt.p; ja.stash_row = (uint64_t *)g.stash_row.p;
     RHJ_STAGE(ST_BUILD);
@@ -861,42 +945,34 @@ int join_device_once(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint
         if (ensure(g.tab64, plan.hbm_slots * 8)) return -1;
         ja.tab64 = (uint64_t *)g.tab64.p;
         HIP_TRY(hipMemsetAsync(g.tab64.p, 0, plan.hbm_slots * 8, g.stream));
-        RHJ_LAUNCH(k_build_hbm, dim3((unsigned)plan.build_units), dim3(256), 0, g.stream, ja,
-                           (const Unit *)g.bunits.p);
+        RHJ_LAUNCH(k_build_hbm, dim3((unsigned)plan.build_units), dim3(256), 0, g.stream, ja, (const Unit *)g.bunits.p);
     }
     if (plan.lds_buckets)
         RHJ_LAUNCH(k_build_lds, dim3((unsigned)plan.lds_buckets), dim3(BL_BLOCK), (size_t)plan.max_lds_slots * 4,
-                           g.stream, ja, (const uint32_t *)g.ldsb.p);
+                   g.stream, ja, (const uint32_t *)g.ldsb.p);
 
     const unsigned probe_grid = (unsigned)((plan.units + 7) / 8 * 8);
     RHJ_STAGE(ST_COUNT);
     if (plan.units)
         RHJ_LAUNCH((k_probe<false>), dim3(probe_grid), dim3(PR_BLOCK), 0, g.stream, ja);
     RHJ_STAGE(ST_OFFSETS);
-    if (launch_offsets((const uint64_t *)g.ucount.p, (uint64_t *)g.ubase.p,
-                       (const uint64_t *)&((PlanSummary *)g.summary.p)->units, 0, plan.units,
-                       &((PlanSummary *)g.summary.p)->matches))
+    if (launch_offsets((const uint64_t *)g.ucount.p, (uint64_t *)g.ubase.p, (const uint64_t *)&((PlanSummary *)g.summary.p)->units, 0,
+                       plan.units, &((PlanSummary *)g.summary.p)->matches))
         return -1;
     HIP_TRY(hipMemcpyAsync(hs, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));                  // sync #2: match count -> output size
-    *overflow = hs->row_id_overflow != 0;
-    if (*overflow) return 0;                                  // the caller runs the join again with wide intermediates
+    if (hs->row_id_overflow) return RUN_WIDE;
     const uint64_t M = hs->matches;
-    *matches = M;
+    *q.matches = M;
     st.matches = M;
 
-    int rc = 0;
-    if (use_ctx_out) {
-        if (ensure(g.out, (M ? M : 1) * sizeof(rhj_result_tuple))) return -1;
-        out = (rhj_result_tuple *)g.out.p;
-        out_capacity = M;
-        if (ctx_out) *ctx_out = out;
-    } else if (M > out_capacity) {
-        rc = 1;
-    }
+    rhj_result_tuple *out;
+    uint64_t cap;
+    int rc;
+    if (out_exact(q, M, out, cap, rc)) return -1;
     RHJ_STAGE(ST_PROBE);
-    if (plan.units && M && out && out_capacity) {
-        ja.out = out; ja.out_capacity = out_capacity;
+    if (plan.units && M && out && cap) {
+        ja.out = out; ja.out_capacity = cap;
         RHJ_LAUNCH((k_probe<true>), dim3(probe_grid), dim3(PR_BLOCK), 0, g.stream, ja);
     }
     RHJ_STAGE(ST_END);
@@ -928,59 +1004,45 @@ static int lowradix_sub_bits(int r, uint64_t nR, uint64_t nS)
     return k;
 }
 
+// The split width k a join takes (0: none): few radix bits over big inputs, canonical order wanted — run on finer buckets,
+// emit in the caller's order.  Also for a rank's share of a sharded join (the partition's first pass, on the caller's bits,
+// drops the other buckets), but not for a share cut inside a bucket: that is a matter of the plan's units, and these are
+// sub-buckets.
+static int split_bits(const JoinReq &q)
+{
+    if (g.no_lowradix || g.no_fused || g.force_hbm || g.wide_row_ids || q.slice_skip || q.slice_end || q.nR >= (1ull << 32) ||
+        q.nS >= (1ull << 32))
+        return 0;
+    return lowradix_sub_bits(q.bits, q.nR, q.nS);
+}
+
 // The part both paths share: the caller's r-bit buckets split into 2^kb sub-buckets each, hist / psum of the r + kb-bit layout
-// (sub-bucket s of bucket b at (s << r) | b) and the partitioned relations in partR / partS.  Chooses every caller's bucket's
+// in hb (sub-bucket s of bucket b at (s << r) | b) and the partitioned relations in partR / partS.  Chooses every caller's bucket's
 // probe side (k_lr_parent), plans and runs the fused kernel in its low-radix form: the pairs go to lr_tmp, every probe tuple's
 // count and stash row to stash_cnt / stash_row.  Returns 2 for what these paths refuse — wide row ids, a build side beyond the
 // LDS index, a unit that needed the index walk (its tuples' pairs are not where their stash rows say), a pass-2 tile of
-// several batches (words[0]), 2^32 pairs or more — and fills ja (out = lr_tmp) and *M otherwise.
-static int lr_internal_join(uint64_t nR, uint64_t nS, int r, int kb, const uint64_t *hist, const uint64_t *psum, uint32_t *words,
-                            bool count_only, const char *path, JoinArgs &ja, uint64_t *M_out)
+// several batches (words[0]), 2^32 pairs or more — and otherwise fills ja (out = lr_tmp), *M and the path's (4 / 5) stats.
+static int lr_internal_join(const JoinReq &q, int kb, Buf &hb, uint32_t *words, int path, JoinArgs &ja, uint64_t *M_out)
 {
     rhj_stats &st = g.stats;
-    const int T = r + kb;
+    const uint64_t nR = q.nR, nS = q.nS;
+    const int r = q.bits, T = r + kb;
     const uint32_t bins = 1u << T;
+    const bool count_only = q.count_only();
     uint8_t *parent_flip = (uint8_t *)(words + 16);            // [2 << r]
-    RHJ_LAUNCH(k_lr_parent, dim3(1u << r), dim3(256), 0, g.stream, hist, hist + bins, r, kb, parent_flip);
+    RHJ_LAUNCH(k_lr_parent, dim3(1u << r), dim3(256), 0, g.stream, (const uint64_t *)hb.p, (const uint64_t *)hb.p + bins, r, kb, parent_flip);
 
-    const uint32_t build_chunk = 4096;
-    uint32_t lds_cap = (LDS_BUDGET - FJ_LDS_EXTRA - 128) * 2 / 9;
-    if (lds_cap > 65534) lds_cap = 65534;
-    const uint64_t nmin = nR < nS ? nR : nS;
-    const uint64_t max_units = (uint64_t)bins + (nR + nS) / PR_UNIT + 2;
-    const uint64_t max_bunits = (uint64_t)bins + nmin / build_chunk + 2;
     const uint64_t unit_bound = (uint64_t)bins + (nR + nS) / FJ_SPAN + 2;
-    if (ensure(g.units, max_units * sizeof(Unit)) || ensure(g.bunits, max_bunits * sizeof(Unit)) || ensure(g.ldsb, (size_t)bins * 4) ||
-        ensure(g.meta, (size_t)bins * sizeof(BucketMeta)) || ensure(g.summary, sizeof(PlanSummary) + 64) ||
-        ensure(g.ucount, max_units * 8) || ensure(g.ubase, max_units * 8) || ensure(g.uflag, max_units * 4) ||
-        ensure(g.stash_cnt, nR + nS + 64) || ensure(g.stash_row, (nR + nS + 8) * 8) || ensure(g.status, (unit_bound + 1) * 8 + 64) ||
-        ensure(g.ovf, fj_ovf_bytes((size_t)g.cus)) || ensure(g.ovf_base, (size_t)g.cus * 2 * FJ_GROUPS * 16 * 4) ||
-        ensure(g.walk, (unit_bound + 1) * sizeof(FjWalkItem)))
-        return -1;
+    const uint64_t status_bytes = (unit_bound + 1) * 8 + 64;
     PlanArgs pa;
-    pa.histR = (uint64_t *)hist; pa.histS = (uint64_t *)hist + bins;
-    pa.units = (Unit *)g.units.p; pa.build_units = (Unit *)g.bunits.p; pa.lds_buckets = (uint32_t *)g.ldsb.p;
-    pa.meta = (BucketMeta *)g.meta.p; pa.summary = (PlanSummary *)g.summary.p;
-    pa.lds_cap = lds_cap; pa.lds_max_slots = LDS_BUDGET / 4 / 4 * 4; pa.build_chunk = build_chunk; pa.span_lds = FJ_SPAN;
-    pa.parent_mask = (1u << r) - 1u; pa.parent_flip = parent_flip; pa.zero = nullptr; pa.zero_words = 0;
+    FusedArgs fa;
+    if (plan_args(nR, nS, T, hb, FUSED_LDS_CAP, FJ_SPAN, (1u << r) - 1u, parent_flip, pa, ja) ||
+        fused_args(nR, nS, T, unit_bound, status_bytes, 1, nullptr, fa))
+        return -1;
     RHJ_LAUNCH(k_plan, dim3(T >= 11 ? 8 : 1), dim3(1024), 0, g.stream, pa, T);
 
-    ja.partR = (const rhj_tuple *)g.partR.p; ja.partS = (const rhj_tuple *)g.partS.p;
-    ja.histR = hist; ja.histS = hist + bins; ja.psumR = psum; ja.psumS = psum + bins;
-    ja.units = (const Unit *)g.units.p; ja.meta = (const BucketMeta *)g.meta.p; ja.summary = (const PlanSummary *)g.summary.p;
-    ja.tab32 = nullptr; ja.tab64 = nullptr;
-    ja.unit_count = (uint64_t *)g.ucount.p; ja.unit_base = (const uint64_t *)g.ubase.p; ja.unit_flag = (uint32_t *)g.uflag.p;
-    ja.parent_mask = (1u << r) - 1u; ja.parent_flip = parent_flip;
-    ja.stash_cnt = nullptr; ja.stash_row = nullptr; ja.stash_nR = nR;
-    FusedArgs fa;
-    fa.stash_cnt = (uint8_t *)g.stash_cnt.p; fa.stash_row = (uint64_t *)g.stash_row.p;
-    fa.status = (uint64_t *)g.status.p + 8; fa.ticket = (uint32_t *)g.status.p;
-    fa.nR = nR; fa.allow_resident = 0; fa.radix_bits = (uint32_t)T; fa.lr_mode = 1; fa.spec = 0; fa.xrows = nullptr;
-    fa.unit_bound = unit_bound; fa.host_summary = nullptr; fa.dbg = nullptr;
-    fa.ovf = (uint64_t *)g.ovf.p; fa.ovf_base = (uint32_t *)g.ovf_base.p; fa.walk = (FjWalkItem *)g.walk.p;
-    const uint32_t fused_lds = LDS_BUDGET - FJ_LDS_EXTRA;
-    const unsigned fgrid = (unsigned)(unit_bound < (uint64_t)g.cus ? unit_bound : (uint64_t)g.cus);
-    struct Back { PlanSummary p; uint32_t ticket[4]; uint32_t words[4]; } *hb = (Back *)g.pin;
+    const unsigned fgrid = fused_grid(unit_bound);
+    const Pinned &hp = *g.pin;
     uint64_t M = 0;
     RHJ_STAGE(ST_PROBE);
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -992,78 +1054,65 @@ static int lr_internal_join(uint64_t nR, uint64_t nS, int r, int kb, const uint6
         ja.out = count_only ? nullptr : (rhj_result_tuple *)g.lr_tmp.p;
         ja.out_capacity = count_only ? 0 : g.lr_tmp.cap / sizeof(rhj_result_tuple);
         fa.j = ja;
-        HIP_TRY(hipMemsetAsync(g.status.p, 0, (unit_bound + 1) * 8 + 64, g.stream));
+        HIP_TRY(hipMemsetAsync(g.status.p, 0, status_bytes, g.stream));
         HIP_TRY(hipMemsetAsync(g.stash_cnt.p, 0, nR + nS, g.stream));      // probe tuples of sub-buckets without a build side match nothing
-        RHJ_LAUNCH((k_join_fused<false, true>), dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-        RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), fused_lds, g.stream, fa, fused_lds);
-        HIP_TRY(hipMemcpyAsync(&hb->p, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(hb->ticket, g.status.p, 16, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(hb->words, words, 16, hipMemcpyDeviceToHost, g.stream));
+        RHJ_LAUNCH((k_join_fused<false, true>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
+        HIP_TRY(hipMemcpyAsync(&g.pin->summary, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(g.pin->ticket, g.status.p, 16, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(g.pin->lr_words, words, 16, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hb->p.wide_row_ids || hb->p.row_id_overflow || !hb->p.fused_ok || hb->ticket[2] != 0 || hb->words[0] != 0 ||
-            hb->p.matches == FJ_NO_TOTAL || hb->p.matches >= (1ull << 32)) {
+        const PlanSummary &p = hp.summary;
+        if (p.wide_row_ids || p.row_id_overflow || !p.fused_ok || hp.ticket[2] != 0 || hp.lr_words[0] != 0 ||
+            p.matches == FJ_NO_TOTAL || p.matches >= (1ull << 32)) {
             static const bool trace = getenv("RHJ_TRACE") != nullptr;
             if (trace) fprintf(stderr, "rhj-trace:   %s path gives up: wide ids %u/%u, fused_ok %llu, walk units %u, big tile %u, matches %llu\n",
-                               path, hb->p.wide_row_ids, hb->p.row_id_overflow, (unsigned long long)hb->p.fused_ok, hb->ticket[2], hb->words[0],
-                               (unsigned long long)hb->p.matches);
+                               path == 4 ? "low-radix" : "sub-bucket", p.wide_row_ids, p.row_id_overflow, (unsigned long long)p.fused_ok,
+                               hp.ticket[2], hp.lr_words[0],
+                               (unsigned long long)p.matches);
             return 2;
         }
-        M = hb->p.matches;
+        M = p.matches;
         if (count_only || M * sizeof(rhj_result_tuple) <= g.lr_tmp.cap) break;
     }
-    st.units = hb->p.units; st.hbm_units = 0; st.max_build = hb->p.max_build;
+    st.units = hp.summary.units; st.hbm_units = 0; st.max_build = hp.summary.max_build;
+    st.reserved = path;                                        // path id: 4 low-radix, 5 sub-bucket
+    *q.matches = M;
+    st.matches = M;
     *M_out = M;
     return 0;
 }
 
-// the caller's buffer for M pairs: the context's own (grown) one, or out when it holds them all (else rc 1: the first
-// out_capacity pairs are written)
-static int lr_out_buffer(uint64_t M, bool use_ctx_out, rhj_result_tuple **ctx_out, rhj_result_tuple *&out, uint64_t &out_capacity, int &rc)
-{
-    rc = 0;
-    if (use_ctx_out) {
-        if (ensure(g.out, M * sizeof(rhj_result_tuple))) return -1;
-        out = (rhj_result_tuple *)g.out.p;
-        out_capacity = M;
-        if (ctx_out) *ctx_out = out;
-    } else if (M > out_capacity) {
-        rc = 1;
-    }
-    return 0;
-}
-
-int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                   uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches, int kb)
+static int join_lowradix(const JoinReq &q, int kb)
 {
     rhj_stats &st = g.stats;
-    const int r = g.bits, T = r + kb;
+    const uint64_t nR = q.nR, nS = q.nS;
+    const int r = q.bits, T = r + kb;
     PartState ps;
     if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple)) ||
         ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple)) || ensure(g.lr_words, 64 + ((size_t)2 << r) + 4096))
         return -1;
-    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
-    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
+    ps.r[0] = RelArgs{q.R, (rhj_tuple *)g.partR.p, nullptr, nR, 0, 0, nullptr, nullptr};
+    ps.r[1] = RelArgs{q.S, (rhj_tuple *)g.partS.p, nullptr, nS, 0, 0, nullptr, nullptr};
     ps.tmp[0] = (rhj_tuple *)g.tmpR.p; ps.tmp[1] = (rhj_tuple *)g.tmpS.p;
-    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; ps.r[i].range_bits = (uint32_t)r; }   // (a share: the CALLER's buckets)
+    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = q.range_lo; ps.r[i].range_span = q.range_span; ps.r[i].range_bits = (uint32_t)r; }   // (a share: the CALLER's buckets)
     ps.lo_bits = r;                                            // pass 1 on exactly the caller's bits: pass 2 reads in canonical order
     uint32_t *words = (uint32_t *)g.lr_words.p;                // word 0: a pass-2 tile / chunk beyond one batch; word 1: k_lr_emit's ticket
     HIP_TRY(hipMemsetAsync(words, 0, 64, g.stream));
     if (run_partition(ps, T, 2, false, true)) return -1;
     RHJ_STAGE(ST_PLAN);
-    const bool count_only = !use_ctx_out && out == nullptr;
     JoinArgs ja;
     uint64_t M = 0;
-    const int rj = lr_internal_join(nR, nS, r, kb, ps.hist, ps.psum, words, count_only, "low-radix", ja, &M);
+    const int rj = lr_internal_join(q, kb, g.histpsum, words, 4, ja, &M);
     if (rj) return rj;
-    st.reserved = 4;                                           // path id: low-radix
-    *matches = M;
-    st.matches = M;
     int rc = 0;
-    if (!count_only && M) {
-        if (lr_out_buffer(M, use_ctx_out, ctx_out, out, out_capacity, rc)) return -1;
+    if (!q.count_only() && M) {
+        rhj_result_tuple *out;
+        uint64_t cap;
+        if (out_exact(q, M, out, cap, rc)) return -1;
         LrArgs la;
-        la.j = ja; la.j.out = out; la.j.out_capacity = out_capacity;
+        la.j = ja; la.j.out = out; la.j.out_capacity = cap;
         la.p2R = ps.p2[0]; la.p2S = ps.p2[1];
         la.stash_cnt = (const uint8_t *)g.stash_cnt.p; la.stash_row = (const uint2 *)g.stash_row.p;
         la.tmp = (const uint4 *)g.lr_tmp.p;
@@ -1083,16 +1132,14 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         const unsigned egrid = (unsigned)(nslots < (uint32_t)g.cus * 8u ? nslots : (uint32_t)g.cus * 8u);
         RHJ_LAUNCH(k_lr_emit, dim3(egrid), dim3(LR_BLOCK), lr_lds_bytes(kb), g.stream, la, nslots);
         RHJ_STAGE(ST_END);
-        uint32_t *hw = (uint32_t *)g.pin + 256;
-        HIP_TRY(hipMemcpyAsync(hw, words, 16, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(g.pin->lr_words, words, 16, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hw[0] != 0) return 2;
+        if (g.pin->lr_words[0] != 0) return 2;
     } else {
         RHJ_STAGE(ST_END);
         HIP_TRY(hipStreamSynchronize(g.stream));
     }
-    st.radix_bits = r;
     st.ms_hist = stage_ms(ST_HIST, ST_SCAN);
     st.ms_scan = stage_ms(ST_SCAN, ST_SCATTER);
     st.ms_scatter = stage_ms(ST_SCATTER, ST_PLAN);
@@ -1106,21 +1153,21 @@ int join_device_lr(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
 // partR / partS), pass B splits it into partR / partS on the next kb bits; the internal join is the low-radix path's.
 // Stage times: ms_hist / ms_scan / ms_scatter the r-bit partition's, ms_build pass B, ms_plan parent choice + plan, ms_probe the
 // internal join, ms_offsets the emit.
-int join_device_sb(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                   uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches, int kb)
+static int join_subbucket(const JoinReq &q, int kb)
 {
     rhj_stats &st = g.stats;
-    const int r = g.bits, T = r + kb;
+    const uint64_t nR = q.nR, nS = q.nS;
+    const int r = q.bits, T = r + kb;
     if (kb > SB_MAX_K || nR >= (1ull << 31) || nS >= (1ull << 31)) return 2;      // (the emit map keeps 31-bit positions)
     const uint32_t bins_r = 1u << r, binsT = 1u << T, digits = 1u << kb;
     PartState ps;
     if (ensure(g.partR, nR * sizeof(rhj_tuple)) || ensure(g.partS, nS * sizeof(rhj_tuple)) ||
         ensure(g.tmpR, nR * sizeof(rhj_tuple)) || ensure(g.tmpS, nS * sizeof(rhj_tuple)) || ensure(g.lr_words, 64 + ((size_t)2 << r) + 4096))
         return -1;
-    ps.r[0] = RelArgs{dR, (rhj_tuple *)g.tmpR.p, nullptr, nR, 0, 0, nullptr, nullptr};
-    ps.r[1] = RelArgs{dS, (rhj_tuple *)g.tmpS.p, nullptr, nS, 0, 0, nullptr, nullptr};
+    ps.r[0] = RelArgs{q.R, (rhj_tuple *)g.tmpR.p, nullptr, nR, 0, 0, nullptr, nullptr};
+    ps.r[1] = RelArgs{q.S, (rhj_tuple *)g.tmpS.p, nullptr, nS, 0, 0, nullptr, nullptr};
     ps.tmp[0] = (rhj_tuple *)g.partR.p; ps.tmp[1] = (rhj_tuple *)g.partS.p;
-    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = g.range_lo; ps.r[i].range_span = g.range_span; ps.r[i].range_bits = (uint32_t)r; }
+    for (int i = 0; i < 2; ++i) { ps.r[i].range_lo = q.range_lo; ps.r[i].range_span = q.range_span; ps.r[i].range_bits = (uint32_t)r; }
     uint32_t *words = (uint32_t *)g.lr_words.p;                // word 0: (nothing raises it on this path); words 4..5: the emit scan's total
     HIP_TRY(hipMemsetAsync(words, 0, 64, g.stream));
     if (run_partition(ps, r, 2, false, true)) return -1;
@@ -1149,23 +1196,21 @@ int join_device_sb(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
     RHJ_LAUNCH(k_sb_hist, dim3((binsT + 255) / 256, 2), dim3(256), 0, g.stream, sa);
     RHJ_LAUNCH(k_scan_psum, dim3(2), dim3(1024), 0, g.stream, T, (const uint64_t *)histT, psumT);
     RHJ_LAUNCH(k_sb_scatter, dim3(rowlen, 2), dim3(SB_BLOCK), 0, g.stream, sa);
-    uint64_t *hE = (uint64_t *)g.pin + 256;                    // the emit sequence's length, read back with the join's summary
-    HIP_TRY(hipMemcpyAsync(hE, sa.ebase + bins_r, 8, hipMemcpyDeviceToHost, g.stream));
+    // the emit sequence's length, read back with the join's summary
+    HIP_TRY(hipMemcpyAsync(&g.pin->emit_len, sa.ebase + bins_r, 8, hipMemcpyDeviceToHost, g.stream));
     RHJ_STAGE(ST_PLAN);
 
-    const bool count_only = !use_ctx_out && out == nullptr;
     JoinArgs ja;
     uint64_t M = 0;
-    const int rj = lr_internal_join(nR, nS, r, kb, histT, psumT, words, count_only, "sub-bucket", ja, &M);
+    const int rj = lr_internal_join(q, kb, g.sb_meta, words, 5, ja, &M);
     if (rj) return rj;
-    st.reserved = 5;                                           // path id: sub-bucket
-    *matches = M;
-    st.matches = M;
     int rc = 0;
     RHJ_STAGE(ST_OFFSETS);
-    if (!count_only && M) {
-        if (lr_out_buffer(M, use_ctx_out, ctx_out, out, out_capacity, rc)) return -1;
-        const uint64_t E = *hE;
+    if (!q.count_only() && M) {
+        rhj_result_tuple *out;
+        uint64_t cap;
+        if (out_exact(q, M, out, cap, rc)) return -1;
+        const uint64_t E = g.pin->emit_len;
         const uint64_t nslots = (E + SB_CHUNK - 1) / SB_CHUNK;
         if (ensure(g.lr_status, (size_t)nslots * 8 + 64)) return -1;
         SbEmitArgs ea;
@@ -1173,7 +1218,7 @@ int join_device_sb(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
         ea.stash_cnt = (const uint8_t *)g.stash_cnt.p; ea.stash_row = (const uint2 *)g.stash_row.p;
         ea.tmp = (const uint4 *)g.lr_tmp.p; ea.nR = nR;
         ea.ctotal = (uint64_t *)g.lr_status.p;
-        ea.out = (uint4 *)out; ea.out_capacity = out_capacity;
+        ea.out = (uint4 *)out; ea.out_capacity = cap;
         RHJ_LAUNCH(k_sb_totals, dim3((unsigned)nslots), dim3(SB_BLOCK), 0, g.stream, ea);
         if (launch_offsets(ea.ctotal, ea.ctotal, nullptr, nslots, nslots, (uint64_t *)(words + 4))) return -1;
         RHJ_LAUNCH(k_sb_emit, dim3((unsigned)nslots), dim3(SB_BLOCK), 0, g.stream, ea);
@@ -1183,8 +1228,7 @@ int join_device_sb(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64
     HIP_TRY(hipStreamSynchronize(g.stream));
     static const bool trace = getenv("RHJ_TRACE") != nullptr;
     if (trace) fprintf(stderr, "rhj-trace:   sub-bucket path: %d + %d bits, %llu pairs, emit sequence %llu\n", r, kb,
-                       (unsigned long long)M, (unsigned long long)*hE);
-    st.radix_bits = r;
+                       (unsigned long long)M, (unsigned long long)g.pin->emit_len);
     st.ms_hist = stage_ms(ST_HIST, ST_SCAN);
     st.ms_scan = stage_ms(ST_SCAN, ST_SCATTER);
     st.ms_scatter = stage_ms(ST_SCATTER, ST_BUILD);
@@ -1210,49 +1254,37 @@ static int auto_radix_bits(uint64_t nR, uint64_t nS)
     return b < 1 ? 1 : b;
 }
 
-static int join_device_radix(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                             uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches);
-
-int join_device(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches)
+// The device-side join.  A split path goes first where it applies (r <= 8 the low-radix path, 9..13 the sub-bucket path) and
+// hands back 2 when it refuses.  Then the small path, or the partition and plan followed by the fused path; the tiled path
+// where either hands over, and behind the plan when the fused path is not wanted.  A narrow partition that met wide row ids
+// makes the whole join run again wide.
+static int join_device(JoinReq q)
 {
-    if (!g.order_any || nR == 0 || nS == 0) return join_device_radix(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches);
-    const int callers = g.bits;
-    g.bits = auto_radix_bits(nR, nS);
-    const int rc = join_device_radix(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches);
-    g.bits = callers;
-    return rc;
-}
-
-static int join_device_radix(const rhj_tuple *dR, uint64_t nR, const rhj_tuple *dS, uint64_t nS, rhj_result_tuple *out,
-                             uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches)
-{
-    bool overflow = false;
-    {
-        // few radix bits over big inputs, canonical order wanted: run on finer buckets, emit in the caller's order (r <= 8: the
-        // low-radix path, 9..13: the sub-bucket path)
-        // (also for a rank's share of a sharded join — the partition's first pass, on the caller's bits, drops the other buckets —
-        // but not for a share cut inside a bucket: that is a matter of the plan's units, and these are sub-buckets)
-        const int kb = (!g.no_lowradix && !g.no_fused && !g.force_hbm && !g.wide_row_ids && !g.slice_skip && !g.slice_end && nR < (1ull << 32) && nS < (1ull << 32))
-                           ? lowradix_sub_bits(g.bits, nR, nS) : 0;
-        if (kb) {
-            if (ctx_init()) return -1;
-            const float keep_h2d = g.stats.ms_h2d;
-            memset(&g.stats, 0, sizeof(g.stats));
-            g.stats.ms_h2d = keep_h2d;
-            g.stats.n_r = nR; g.stats.n_s = nS; g.stats.radix_bits = g.bits;
-            *matches = 0;
-            if (ctx_out) *ctx_out = nullptr;
-            const int rc3 = g.bits <= PT_MAX_BITS ? join_device_lr(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, kb)
-                                                  : join_device_sb(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, kb);
-            if (rc3 != 2) return rc3;
-        }
+    if (g.order_any && q.nR && q.nS) q.bits = auto_radix_bits(q.nR, q.nS);    // RHJ_ORDER=any: the library picks the radix
+    if (const int kb = split_bits(q)) {
+        if (begin_join(q)) return -1;
+        const int rc = q.bits <= PT_MAX_BITS ? join_lowradix(q, kb) : join_subbucket(q, kb);
+        if (rc != 2) return rc;
     }
-    int rc = join_device_once(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, g.wide_row_ids != 0, &overflow);
-    if (rc >= 0 && overflow) g.seen_wide = 1;
-    if (rc >= 0 && overflow)
-        rc = join_device_once(dR, nR, dS, nS, out, out_capacity, use_ctx_out, ctx_out, matches, true, &overflow);
-    return rc;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (begin_join(q)) return -1;
+        if (q.nR == 0 || q.nS == 0) return 0;                         // rhjoin.c:15-16
+        if (q.nR >= (1ull << 32) || q.nS >= (1ull << 32)) {
+            fprintf(stderr, "rhj: relations of 2^32 tuples or more are not supported (offsets are 32-bit; the reference "
+                            "itself is limited to 2^31-1, SURVEY.md finding 9)\n");
+            return -2;
+        }
+        JoinSetup s;
+        if (join_setup(q, attempt > 0 || g.wide_row_ids, s)) return -1;
+        int rc = TILED_PLANNED;
+        if (s.small) rc = join_small(q, s);
+        else if (partition_plan(s)) return -1;
+        else if (s.want_fused) rc = join_fused(q, s);
+        if (rc >= TILED_PLANNED) rc = join_tiled(q, s, rc);
+        if (rc != RUN_WIDE) return rc;
+        g.seen_wide = 1;                                              // from now on the 16-byte kernels are launched as well
+    }
+    return 0;
 }
 
 // k_filter_write is grid-stride, one wave per two tiles: enough workgroups to fill the chip a few times over
@@ -1272,18 +1304,18 @@ int filter_write_out(uint64_t n, uint64_t tiles, uint64_t *total, uint64_t *d_ou
 {
     if (tiles <= FILTER_SELF_TILES) {                  // the write waves sum the tile counts themselves, the total lands in pinned memory:
         RHJ_LAUNCH((k_filter_write<true>), dim3(filter_write_grid(tiles)), dim3(256), 0, g.stream, n, (const uint64_t *)g.fmask.p,   // no scan
-                   (const uint64_t *)g.ftile.p, d_out, (unsigned long long *)g.pin);                                                  // launches, no copy
+                   (const uint64_t *)g.ftile.p, d_out, (unsigned long long *)&g.pin->hits);                                           // launches, no copy
         RHJ_STAGE(ST_END);
     } else {
         if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
         RHJ_LAUNCH((k_filter_write<false>), dim3(filter_write_grid(tiles)), dim3(256), 0, g.stream, n, (const uint64_t *)g.fmask.p,
                    (const uint64_t *)g.fbase.p, d_out, (unsigned long long *)nullptr);
         RHJ_STAGE(ST_END);
-        HIP_TRY(hipMemcpyAsync(g.pin, total, 8, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
-    *hits = *(volatile uint64_t *)g.pin;
+    *hits = *(volatile uint64_t *)&g.pin->hits;
     return 0;
 }
 
@@ -1354,31 +1386,31 @@ static int select_range(const rhj_tuple *d_in, uint64_t n, uint32_t bucket_lo, u
     if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
     RHJ_LAUNCH(k_select_write, dim3((unsigned)tiles), dim3(SH_BLOCK), 0, g.stream, d_in, n, mask, bucket_lo, bucket_hi,
                (const uint64_t *)g.fbase.p, d_out, capacity);
-    HIP_TRY(hipMemcpyAsync(g.pin, total, 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
-    *count = *(uint64_t *)g.pin;
+    *count = g.pin->hits;
     return *count > capacity ? 1 : 0;
 }
 
-// (on the calling thread's context, without the API lock: the public entry below, and the per-device workers of a multi-device join)
-static int join_range(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, uint32_t bucket_lo, uint32_t bucket_hi,
-                      rhj_result_tuple *d_out, uint64_t out_capacity, bool use_ctx_out, rhj_result_tuple **ctx_out, uint64_t *matches,
-                      uint64_t first_skip = 0, uint64_t last_end = 0)
+// (on the calling thread's context, without the API lock: the public entries below, and the per-device workers of a
+// multi-device join; q.matches may be null)
+static int join_range(JoinReq q, uint32_t bucket_lo, uint32_t bucket_hi, uint64_t first_skip = 0, uint64_t last_end = 0)
 {
+    uint64_t *const matches = q.matches;
+    uint64_t m = 0;
+    q.matches = &m;
     if (matches) *matches = 0;
-    if (ctx_out) *ctx_out = nullptr;
+    if (q.ctx_out) *q.ctx_out = nullptr;
     if (g.order_any) { fprintf(stderr, "rhj_join_device_range: bucket numbers belong to the caller's radix; not with RHJ_ORDER=any\n"); return -3; }
-    const uint32_t bins = 1u << g.bits;
+    const uint32_t bins = 1u << q.bits;
     if (bucket_hi > bins) bucket_hi = bins;
     if (bucket_lo >= bucket_hi) return 0;                     // an empty range joins nothing
-    uint64_t m = 0;
     const bool whole = bucket_lo == 0 && bucket_hi == bins && !first_skip && !last_end;
-    g.range_lo = bucket_lo;
-    g.range_span = whole ? 0u : bucket_hi - bucket_lo;        // the whole radix is the ordinary join (small path and all)
-    g.slice_skip = first_skip; g.slice_end = last_end;
-    const int rc = join_device(d_R, nR, d_S, nS, d_out, out_capacity, use_ctx_out, ctx_out, &m);
-    g.range_lo = 0; g.range_span = 0; g.slice_skip = 0; g.slice_end = 0;
+    q.range_lo = bucket_lo;
+    q.range_span = whole ? 0u : bucket_hi - bucket_lo;        // the whole radix is the ordinary join (small path and all)
+    q.slice_skip = first_skip; q.slice_end = last_end;
+    const int rc = join_device(q);
     if (matches) *matches = m;
     return rc;
 }
@@ -1544,7 +1576,7 @@ int rhj_join_device(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uin
 {
     RhjApiLock api_lock;
     uint64_t m = 0;
-    const int rc = join_device(d_R, nR, d_S, nS, d_out, out_capacity, false, nullptr, &m);
+    const int rc = join_device({d_R, nR, d_S, nS, d_out, out_capacity, false, nullptr, &m, g.bits});
     if (matches) *matches = m;
     return rc;
 }
@@ -1561,17 +1593,14 @@ int rhj_join_keys_device(const uint64_t *d_keysR, uint64_t nR, const uint64_t *d
     uint64_t m = 0;
     if (matches) *matches = 0;
     if (nR >= (1ull << 32) || nS >= (1ull << 32)) return -2;
-    int rc;
-    const bool lowradix = !g.no_lowradix && lowradix_sub_bits(g.bits, nR, nS) != 0;
-    if (!g.order_any && g.bits > PT_MAX_BITS && !lowradix && !g.wide_row_ids && !g.no_fused && !g.force_hbm && nR && nS) {
-        g.cols_input = 1;
-        rc = join_device((const rhj_tuple *)d_keysR, nR, (const rhj_tuple *)d_keysS, nS, d_out, out_capacity, false, nullptr, &m);
-        g.cols_input = 0;
-    } else {
+    JoinReq q = {(const rhj_tuple *)d_keysR, nR, (const rhj_tuple *)d_keysS, nS, d_out, out_capacity, false, nullptr, &m, g.bits};
+    q.cols_input = !g.order_any && q.bits > PT_MAX_BITS && !split_bits(q) && !g.wide_row_ids && !g.no_fused && !g.force_hbm && nR && nS;
+    if (!q.cols_input) {
         if (ctx_init() || ensure(g.inR, (nR ? nR : 1) * sizeof(rhj_tuple)) || ensure(g.inS, (nS ? nS : 1) * sizeof(rhj_tuple))) return -1;
         if (rhj_build_relation_device(d_keysR, nullptr, nR, (rhj_tuple *)g.inR.p) || rhj_build_relation_device(d_keysS, nullptr, nS, (rhj_tuple *)g.inS.p)) return -1;
-        rc = join_device((const rhj_tuple *)g.inR.p, nR, (const rhj_tuple *)g.inS.p, nS, d_out, out_capacity, false, nullptr, &m);
+        q.R = (const rhj_tuple *)g.inR.p; q.S = (const rhj_tuple *)g.inS.p;
     }
+    const int rc = join_device(q);
     if (matches) *matches = m;
     return rc;
 }
@@ -1584,7 +1613,7 @@ int rhj_join_device_range(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_
                           rhj_result_tuple *d_out, uint64_t out_capacity, uint64_t *matches)
 {
     RhjApiLock api_lock;
-    return join_range(d_R, nR, d_S, nS, bucket_lo, bucket_hi, d_out, out_capacity, false, nullptr, matches);
+    return join_range({d_R, nR, d_S, nS, d_out, out_capacity, false, nullptr, matches, g.bits}, bucket_lo, bucket_hi);
 }
 
 /* A share cut INSIDE buckets (a hot bucket joined by several devices): the buckets [bucket_lo, bucket_hi) as above, but of the
@@ -1597,7 +1626,7 @@ int rhj_join_device_slice(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_
                           uint64_t first_skip, uint64_t last_end, rhj_result_tuple *d_out, uint64_t out_capacity, uint64_t *matches)
 {
     RhjApiLock api_lock;
-    return join_range(d_R, nR, d_S, nS, bucket_lo, bucket_hi, d_out, out_capacity, false, nullptr, matches, first_skip, last_end);
+    return join_range({d_R, nR, d_S, nS, d_out, out_capacity, false, nullptr, matches, g.bits}, bucket_lo, bucket_hi, first_skip, last_end);
 }
 
 int rhj_set_devices(int n) { RhjApiLock api_lock; g_ndev_env = 0; return set_devices(n); }
@@ -1711,7 +1740,7 @@ int rhj_join_devices(const rhj_tuple *const *d_R, uint64_t nR, const rhj_tuple *
             uint32_t lo, hi;
             uint64_t skip, end;
             rhj_cut_to_slice(cuts[d], offs[d], cuts[d + 1], offs[d + 1], &lo, &hi, &skip, &end);
-            rcs[d] = join_range(d_R[d], nR, d_S[d], nS, lo, hi, out[d], capacity[d], false, nullptr, &matches[d], skip, end);
+            rcs[d] = join_range({d_R[d], nR, d_S[d], nS, out[d], capacity[d], false, nullptr, &matches[d], g.bits}, lo, hi, skip, end);
         });
     } catch (...) { return -1; }
     int rc = 0;
@@ -1765,7 +1794,7 @@ int rhj_partition_device(const rhj_tuple *d_in, uint64_t n, rhj_tuple *d_out, ui
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (run_partition(ps, bits, 1, attempt == 1 || g.wide_row_ids != 0, false)) { free(hh); return -1; }
         RHJ_STAGE(ST_PLAN);
-        PlanSummary *hs = (PlanSummary *)g.pin;
+        PlanSummary *hs = &g.pin->summary;
         HIP_TRY(hipMemcpyAsync(hh, ps.hist, (size_t)bins * 8, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipMemcpyAsync(hh + bins, ps.psum, (size_t)bins * 8, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipMemcpyAsync(hs, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
@@ -1827,10 +1856,9 @@ static void release_current()
     if (!g.ready) return;
     (void)hipSetDevice(g.device);
     (void)hipStreamSynchronize(g.stream);
-    Buf *all[] = {&g.partR, &g.partS, &g.tmpR, &g.tmpS, &g.cntR, &g.cntS, &g.chunk, &g.histpsum, &g.passhp,
-                  &g.units, &g.bunits, &g.ldsb, &g.meta, &g.summary, &g.ucount, &g.ubase, &g.uflag, &g.bsum, &g.digR, &g.digS, &g.ovf, &g.ovf_base, &g.walk, &g.xrows, &g.lr_tmp, &g.lr_words, &g.lr_status, &g.runR, &g.runS, &g.stripR, &g.stripS, &g.slice_tot, &g.sbase, &g.sb_cnt, &g.sb_meta, &g.sb_map, &g.stash_cnt, &g.stash_row, &g.status, &g.tab32,
-                  &g.tab64, &g.inR, &g.inS, &g.out, &g.fcol, &g.fcol_sel, &g.fmask, &g.ftile, &g.fbase, &g.fout};
-    for (Buf *b : all) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+#define RHJ_FREE(name) { if (g.name.p) (void)hipFree(g.name.p); g.name = Buf{}; }
+    RHJ_WORKSPACE(RHJ_FREE)
+#undef RHJ_FREE
     for (auto &kv : g.columns) (void)hipFree(kv.second.dev);
     g.columns.clear();
     for (auto &kv : g.pinned) (void)hipHostUnregister((void *)kv.first);
@@ -1919,9 +1947,8 @@ int rhj_host_join(const rhj_tuple *R, uint64_t nR, const rhj_tuple *S, uint64_t 
             hipMemcpyAsync(g.inR.p, R, nR * sizeof(rhj_tuple), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
             hipMemcpyAsync(g.inS.p, S, nS * sizeof(rhj_tuple), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
             hipEventRecord(g.ev_x[1], g.stream) != hipSuccess) return;
-        if (n == 1) rcs[d] = join_device((const rhj_tuple *)g.inR.p, nR, (const rhj_tuple *)g.inS.p, nS, nullptr, 0, true, &d_outs[d], &Ms[d]);
-        else        rcs[d] = join_range((const rhj_tuple *)g.inR.p, nR, (const rhj_tuple *)g.inS.p, nS, range_cut(bins, n, d), range_cut(bins, n, d + 1),
-                                        nullptr, 0, true, &d_outs[d], &Ms[d]);
+        const JoinReq q = {(const rhj_tuple *)g.inR.p, nR, (const rhj_tuple *)g.inS.p, nS, nullptr, 0, true, &d_outs[d], &Ms[d], g.bits};
+        rcs[d] = n == 1 ? join_device(q) : join_range(q, range_cut(bins, n, d), range_cut(bins, n, d + 1));
         if (rcs[d] >= 0) g.stats.ms_h2d = ev_ms(g.ev_x[0], g.ev_x[1]);
     };
     try { on_devices(n, upload_and_join); } catch (...) { return -1; }
@@ -2194,7 +2221,7 @@ int rhj_dev_join(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64
 {
     RhjApiLock api_lock;
     *out = nullptr; *matches = 0;
-    return join_device(d_R, nR, d_S, nS, nullptr, 0, true, out, matches);
+    return join_device({d_R, nR, d_S, nS, nullptr, 0, true, out, matches, g.bits});
 }
 int rhj_filter_eq2_device(const uint64_t *d_colA, const uint64_t *d_selA, const uint64_t *d_colB, const uint64_t *d_selB,
                           uint64_t n, uint64_t *d_out, uint64_t *hits)

@@ -3,7 +3,7 @@ included.  Ordinary random relations carry one planted bucket whose keys share a
 share their low 32 bits, or collide in k_join_exact's stored bits.  Every case also asserts the path it meant to reach
 (stats()["path"], rhj_last_spec / rhj_last_exact, hbm_units), so a fall-through to another kernel cannot pass.
 
-Path rules (sigmod-2018_amd/csrc/rhj_device.hip, join_device_once):
+Path rules (sigmod-2018_amd/csrc/rhj_device.hip: join_setup, join_small, join_fused, join_tiled):
   small      bits <= PT_MAX_BITS and both relations within small_tiles tiles of SM_TILE tuples, unless rhj_set_small(0)
   resident   k_join_fused<true>: nmin / bins <= 7000 and resident allowed (H32, FjHashT<true>)
   gather     k_join_fused<false>: rhj_set_resident(0) (mix64, FjHashT<false>)

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M64 = (1 << 64) - 1
 CHUNK = 4096                      # SB_CHUNK: pass B's chunk and the emit sequence's slot (rhj_subbucket.hip.h)
-LDS_CAP = (160 * 1024 - 2048 - 128) * 2 // 9     # lr_internal_join: the largest build side the fused kernel's LDS index takes
+LDS_CAP = (160 * 1024 - 2048 - 128) * 2 // 9     # FUSED_LDS_CAP (rhj_device.hip): the largest build side the fused kernel's LDS index takes
 
 
 def split_path(r):
