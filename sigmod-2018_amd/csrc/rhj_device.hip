@@ -540,6 +540,7 @@ static int begin_join(const JoinReq &q)
     memset(&st, 0, sizeof(st));
     st.ms_h2d = keep_h2d;
     st.n_r = q.nR; st.n_s = q.nS; st.radix_bits = q.bits;
+    g.last_spec = g.last_exact = 0;                    // (only the fused path tries them: a join on another path says "not tried")
     *q.matches = 0;
     if (q.ctx_out) *q.ctx_out = nullptr;
     return 0;

@@ -131,3 +131,106 @@ def column_stats_model(col):
     if hi - lo + 1 >= STATS_CAP:
         x = x % np.uint64(STATS_FOLD)
     return lo, hi, float(len(np.unique(x)))
+
+
+# ---- pair buffers between sentinel rows (tests/test_gpu_out_bounds.py) --------------------------------------------------
+GUARD_ROWS = 4096                        # 64 KiB of 16-byte rows on either side: row 0 keeps a fresh allocation's alignment
+SENTINEL = -0x5A5A5A5A5A5A5A5B           # 0xA5A5A5A5A5A5A5A5 as int64: no row id or key of the tests (all below 2^48)
+
+
+class GuardedRows:
+    """`rows` 16-byte rows on the device (row 0 is what an entry point gets) with GUARD_ROWS rows in front of and behind them,
+    every word SENTINEL: what a kernel writes outside [0, capacity) lands in this tensor and is found."""
+
+    def __init__(self, torch, dev, rows):
+        self.rows = int(rows)
+        self.t = torch.full((GUARD_ROWS + self.rows + GUARD_ROWS, 2), SENTINEL, dtype=torch.int64, device=dev)
+
+    @property
+    def ptr(self):
+        return self.t[GUARD_ROWS:].data_ptr()
+
+    def body(self, lo, hi):
+        return self.t[GUARD_ROWS + lo:GUARD_ROWS + hi]
+
+    def touched(self, lo, hi):
+        """rows of [lo, hi) (lo may be negative: the front guard) that no longer hold the sentinel, counted on the device"""
+        return int((self.body(lo, hi) != SENTINEL).any(dim=1).sum().item())
+
+    def assert_untouched(self, lo, hi, what):
+        part = self.body(lo, hi)
+        bad = part != SENTINEL
+        words = int(bad.sum().item())
+        if words:
+            row = int(bad.any(dim=1).nonzero()[0].item())
+            a, b = (int(x) for x in part[row].cpu().numpy().view(np.uint64))
+            raise AssertionError("%s: %d words written outside the buffer, the first in row %d: (%d, %d)" % (what, words, lo + row, a, b))
+
+
+def pairs_to_device(rhj, pairs):
+    a = np.ascontiguousarray(pairs).view(np.int64).reshape(-1, 2)
+    return rhj.torch.from_numpy(a.copy()).to(rhj.dev)
+
+
+def guarded_join(rhj, call, dR, dS, cap, want):
+    """One raw join entry point on a sentinel-guarded buffer.  call(out_ptr, cap, matches_ref) -> rc invokes it; want: the
+    oracle's pairs (PAIR array or [M, 2] device tensor).  Asserts the capacity contract of include/rhj.h: rc 1 iff M > cap,
+    *matches == M, rows [0, min(cap, M)) the oracle's, nothing written in front of row 0 or from row cap on, the relations
+    unchanged.  The buffer spans max(M, cap) rows, so a store whose guard is wrong stays inside it.  Rows [M, cap) are left
+    open by the header; returns how many of them were written."""
+    import ctypes as C
+    torch = rhj.torch
+    want_t = want if torch.is_tensor(want) else pairs_to_device(rhj, want)
+    M = want_t.shape[0]
+    g = GuardedRows(torch, rhj.dev, max(M, cap))
+    keepR, keepS = dR.clone(), dS.clone()
+    m = C.c_uint64(0xDEAD)
+    rc = call(g.ptr, cap, C.byref(m))
+    torch.cuda.synchronize()
+    what = "capacity %d, %d pairs" % (cap, M)
+    assert rc == (1 if M > cap else 0), "%s: return code %d" % (what, rc)
+    assert m.value == M, "%s: *matches = %d" % (what, m.value)
+    g.assert_untouched(-GUARD_ROWS, 0, what + ", in front of the buffer")
+    g.assert_untouched(cap, max(M, cap) + GUARD_ROWS, what + ", behind the capacity (row 0 = d_out)")
+    n = min(cap, M)
+    got = g.body(0, n)
+    if not torch.equal(got, want_t[:n]):
+        i = int((got != want_t[:n]).any(dim=1).nonzero()[0].item())
+        raise AssertionError("%s: pair %d is %r, expected %r" % (what, i, got[i].tolist(), want_t[i].tolist()))
+    assert torch.equal(dR, keepR) and torch.equal(dS, keepS), "%s: an input relation was written" % what
+    return g.touched(M, cap) if cap > M else 0
+
+
+def _keys_of(rel, ids):
+    if np.array_equal(rel["row_id"], np.arange(len(rel), dtype=np.uint64)):
+        return rel["value"][ids]
+    order = np.argsort(rel["row_id"], kind="stable")
+    return rel["value"][order[np.searchsorted(rel["row_id"][order], ids)]]
+
+
+def pair_layout(R, S, want, bits):
+    """Of every wanted pair: its bucket, and a number that names its probe tuple (R's where cR >= cS, rhjoin.c:86).
+    Row ids must be unique in R."""
+    mask = np.uint64((1 << bits) - 1)
+    b = (_keys_of(R, want["row_idR"]) & mask).astype(np.int64)
+    cR = np.bincount((R["value"] & mask).astype(np.int64), minlength=1 << bits)
+    cS = np.bincount((S["value"] & mask).astype(np.int64), minlength=1 << bits)
+    probe = np.where((cR >= cS)[b], want["row_idR"] * np.uint64(2) + np.uint64(1), want["row_idS"] * np.uint64(2))
+    return b, probe
+
+
+def guard_capacities(b, probe):
+    """The capacities a guarded case runs, from the wanted list alone: 0, 1, the first bucket edge and one near the middle
+    with their neighbours, a position inside the longest run of pairs of one probe tuple, M - 1, M, M + 1."""
+    M = len(b)
+    caps = {0, 1, M - 1, M, M + 1}
+    edge = np.nonzero(np.diff(b))[0] + 1
+    for e in ((edge[0], edge[len(edge) // 2]) if len(edge) else ()):
+        caps |= {int(e) - 1, int(e), int(e) + 1}
+    if M > 1:
+        starts = np.concatenate([[0], np.nonzero(np.diff(probe))[0] + 1, [M]])
+        lens = np.diff(starts)
+        i = int(np.argmax(lens))
+        if lens[i] > 1:
+            caps.add(int(starts[i] + lens[i] // 2))
+    return sorted(c for c in caps if 0 <= c <= M + 1)
