@@ -258,7 +258,7 @@ typedef struct rhj_stats {
     uint64_t n_r, n_s, matches;
     uint64_t units, hbm_units, max_build, table_slots;
     int radix_bits;
-    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit) */
+    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit), 6 a batch (rhj_join_batch_device) */
 } rhj_stats;
 
 /* Join two device-resident AoS relations (rhj_tuple[nR], rhj_tuple[nS]).
@@ -271,6 +271,31 @@ int rhj_join_device(const rhj_tuple *d_R, uint64_t nR,
                     const rhj_tuple *d_S, uint64_t nS,
                     rhj_result_tuple *d_out, uint64_t out_capacity,
                     uint64_t *matches);
+
+/* Many independent joins in one call (csrc/rhj_batch.hip.h).  Every join follows the contract of rhj_join_device(): the
+ * canonical order of the radix width in force (order mode "any": rhj_auto_radix_bits() of ITS sizes), the exact match count,
+ * nothing written at or beyond out_capacity.  Inputs may be shared between joins; outputs must not overlap.  The joins that
+ * rhj_batch_takes() names run together in three launches (histograms where a relation has more than two tiles, scatter +
+ * plan, fused join) and one stream synchronisation per chunk, whatever their number; every other join, and a taken join whose
+ * plan finds a bucket beyond the LDS index, is run by the single-join code inside the same call.  A join with an empty side
+ * launches nothing.  Per join: matches (exact, also beyond out_capacity), rc (0; 1 the buffer was short and holds exactly
+ * the first out_capacity pairs — never when d_out is NULL; <0 an error) and path (6: the batched launches; otherwise the path the join took on its own,
+ * as in rhj_stats::reserved).  Returns 0, 1 when some rc is 1, <0 on a HIP error.  rhj_last_stats() afterwards: n_r, n_s,
+ * matches and units summed over the joins, ms_total of the whole call (timing level >= 1), path 6. */
+typedef struct rhj_join_desc {
+    const rhj_tuple  *d_R; uint64_t nR;
+    const rhj_tuple  *d_S; uint64_t nS;
+    rhj_result_tuple *d_out; uint64_t out_capacity;   /* NULL / 0: count only */
+    uint64_t matches;   /* out */
+    int      rc;        /* out */
+    int      path;      /* out */
+} rhj_join_desc;
+int rhj_join_batch_device(rhj_join_desc *joins, uint64_t n);
+/* 1 when a join of these sizes on `bits` radix bits goes into the batched launches: 1..8 bits, both relations non-empty and of
+ * at most 65 536 tuples (8 tiles), and nothing set that keeps a single join off the small path — rhj_set_small(0),
+ * rhj_set_fused(0), rhj_set_force_hbm_table(1), the stamps build (pure function of its arguments and those settings: needs
+ * no device) */
+int rhj_batch_takes(int bits, uint64_t nR, uint64_t nS);
 
 /* The join of two relations given as KEY COLUMNS: tuple i of a relation is {keys[i], i} — what GetRelation makes of a base
  * relation (inter_res.c:199-204, :223-227: row_id = i).  On the two-pass partition (9..15 radix bits) its first pass reads the

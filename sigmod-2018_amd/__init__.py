@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "RadixHashJoin", "Filter", "InsertResult", "InsertRowIdResult", "GetResultNum", "FindResultRowId",
     "FindResultTuples", "FreeResult", "PrintResult", "FreeRelation", "SchedulerInit", "SchedulerDestroy",
     "rhj_set_radix_bits", "rhj_get_radix_bits", "rhj_set_empty_mode", "rhj_set_node_pairs", "rhj_set_device", "rhj_get_device",
-    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device",
+    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device",
     "rhj_register_relation_map", "rhj_unregister_relation_map", "rhj_registered_columns", "rhj_pinned_ranges",
     "rhj_bucket_histogram_device", "rhj_select_bucket_range_device", "rhj_join_device_range", "rhj_join_device_slice", "rhj_pin_refusals",
     "rhj_release", "rhj_last_stats", "rhj_version",
@@ -77,6 +77,12 @@ class FilterPred(C.Structure):
     _fields_ = [("relation", C.c_int), ("column", C.c_int), ("value", C.c_int), ("comperator", C.c_char)]
 
 
+class JoinDesc(C.Structure):
+    """rhj_join_desc (include/rhj.h): one join of rhj_join_batch_device"""
+    _fields_ = [("d_R", C.c_void_p), ("nR", C.c_uint64), ("d_S", C.c_void_p), ("nS", C.c_uint64),
+                ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("matches", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ms_hist", "ms_scan", "ms_scatter", "ms_plan", "ms_build", "ms_count",
                                          "ms_offsets", "ms_probe", "ms_total", "ms_h2d", "ms_d2h")] + \
@@ -86,7 +92,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -157,6 +163,10 @@ def load_library(path=None):
     L.rhj_sub_bits.restype = C.c_int
     L.rhj_set_timing.argtypes = [C.c_int]
     L.rhj_join_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+    if hasattr(L, "rhj_join_batch_device"):       # (A/B runs load earlier builds through this module too)
+        L.rhj_join_batch_device.argtypes = [C.POINTER(JoinDesc), C.c_uint64]
+        L.rhj_batch_takes.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
+        L.rhj_batch_takes.restype = C.c_int
     if hasattr(L, "rhj_join_keys_device"):
         L.rhj_join_keys_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
     L.rhj_partition_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -239,6 +249,49 @@ class RHJ:
         out = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.dev)
         call(out.data_ptr(), capacity)
         return out[:min(m.value, capacity)], m.value
+
+    def join_batch_device(self, pairs_of_tensors, capacities=None, count_only=False, with_info=False):
+        """Many independent joins in one call (rhj_join_batch_device): pairs_of_tensors = [(dR, dS), ...], int64 tensors [n,2]
+        as for join_device; inputs may be shared between joins.  Returns [(pairs tensor [M,2], matches), ...] with join_device's
+        conventions: count_only gives (None, matches); capacities[i] given: at most that many pairs of join i are written and
+        returned; capacities None: every join gets room for max(nR, nS) pairs, and the joins that needed more run again, with
+        room for their count, in a second batched call.  with_info: also the list of the joins' path ids (6: batched)."""
+        torch = self.torch
+        n = len(pairs_of_tensors)
+        descs = (JoinDesc * max(n, 1))()
+        outs = [None] * n
+
+        def call(which, caps):
+            arr = (JoinDesc * max(len(which), 1))()
+            for k, i in enumerate(which):
+                dR, dS = pairs_of_tensors[i]
+                d = arr[k]
+                d.d_R, d.nR, d.d_S, d.nS = dR.data_ptr(), dR.shape[0], dS.data_ptr(), dS.shape[0]
+                if caps is not None:
+                    outs[i] = torch.empty((max(int(caps[k]), 1), 2), dtype=torch.int64, device=self.dev)
+                    d.d_out, d.out_capacity = outs[i].data_ptr(), int(caps[k])
+            rc = self.lib.rhj_join_batch_device(arr, len(which))
+            if rc < 0:
+                raise RuntimeError("rhj_join_batch_device failed (%d)" % rc)
+            for k, i in enumerate(which):
+                descs[i] = arr[k]
+            return rc
+
+        everything = list(range(n))
+        if count_only:
+            call(everything, None)
+        elif capacities is not None:
+            call(everything, [int(c) for c in capacities])
+        else:
+            call(everything, [max(dR.shape[0], dS.shape[0]) for dR, dS in pairs_of_tensors])
+            short = [i for i in everything if descs[i].rc == 1]
+            if short:                               # fan-out above the guess: the counts are known now
+                call(short, [descs[i].matches for i in short])
+        res = []
+        for i in everything:
+            d = descs[i]
+            res.append((None, d.matches) if count_only else (outs[i][:min(d.matches, d.out_capacity)], d.matches))
+        return (res, [descs[i].path for i in everything]) if with_info else res
 
     def partition_device(self, d_in, bits=None):
         torch = self.torch

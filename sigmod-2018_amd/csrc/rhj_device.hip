@@ -77,7 +77,7 @@ enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSE
     X(partR) X(partS) X(tmpR) X(tmpS) X(cntR) X(cntS) X(chunk) X(histpsum) X(passhp) X(units) X(bunits) X(ldsb) X(meta)   \
     X(summary) X(ucount) X(ubase) X(uflag) X(tab32) X(tab64) X(stash_cnt) X(stash_row) X(status) X(dbg) X(bsum) X(digR)  \
     X(digS) X(ovf) X(ovf_base) X(runR) X(runS) X(walk) X(xrows) X(lr_tmp) X(lr_words) X(lr_status) X(stripR) X(stripS)   \
-    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map)                                                                   \
+    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc)                                      \
     X(inR) X(inS) X(out) X(fcol_sel) X(fmask) X(ftile) X(fbase) X(fout)                                                    \
     X(fcol)                                                      /* staging of an unregistered column (host Filter()) */
 
@@ -127,6 +127,9 @@ struct Ctx {
     uint64_t    node_pairs = 65535;
     hipEvent_t  ev[ST_N + 1] = {};
     hipEvent_t  ev_x[4] = {};
+    hipEvent_t  ev_batch[2] = {};    // rhj_join_batch_device: the whole call (the joins it runs alone record the stage events)
+    void       *batch_pin = nullptr; // rhj_join_batch_device: pinned host block of a chunk's summaries, descriptors and join lists
+    size_t      batch_pin_cap = 0;
 #define RHJ_BUF(name) Buf name;
     RHJ_WORKSPACE(RHJ_BUF)
 #undef RHJ_BUF
@@ -230,6 +233,7 @@ int ctx_init()
     if (!g.stream_set) { HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking)); g.own_stream = true; }
     for (auto &ev : g.ev) HIP_TRY(hipEventCreate(&ev));
     for (auto &ev : g.ev_x) HIP_TRY(hipEventCreate(&ev));
+    for (auto &ev : g.ev_batch) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipHostMalloc((void **)&g.pin, 4096, hipHostMallocDefault));
     // dynamic LDS above 64 KiB has to be requested per kernel
     HIP_TRY(hipFuncSetAttribute((const void *)k_build_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
@@ -243,6 +247,9 @@ int ctx_init()
         HIP_TRY(hipFuncSetAttribute((const void *)k_join_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - FJ_LDS_EXTRA)));
     }
     HIP_TRY(hipFuncSetAttribute((const void *)k_small_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_batch_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_batch_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - FJ_LDS_EXTRA)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_batch_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - FJ_LDS_EXTRA)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_bucket_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4u << MAX_BITS)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_bucket_psum<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8u << 14)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_scatter_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
@@ -687,6 +694,19 @@ enum { RUN_WIDE = 3, TILED_PLANNED, TILED_AFTER_SMALL, TILED_AFTER_FUSED };
 
 static uint32_t sm_tiles(uint64_t n) { return (uint32_t)((n + SM_TILE - 1) / SM_TILE); }
 
+// probe tuples per fused unit: whole buckets when there are plenty of them, smaller spans (each unit
+// rebuilds its bucket's index) when a low radix would otherwise leave most CUs idle
+static uint32_t fused_span_for(uint32_t bins, uint64_t nR, uint64_t nS)
+{
+    uint32_t fused_span = FJ_SPAN;
+    if (bins < 256) {                                         // fewer buckets than CUs
+        uint64_t want = ((nR > nS ? nR : nS) / 512 + FJ_BATCH - 1) / FJ_BATCH * FJ_BATCH;
+        if (want < FJ_BATCH) want = FJ_BATCH;
+        if (want < fused_span) fused_span = (uint32_t)want;
+    }
+    return fused_span;
+}
+
 static int join_setup(const JoinReq &q, bool force_wide, JoinSetup &s)
 {
     const uint64_t nR = q.nR, nS = q.nS;
@@ -712,14 +732,7 @@ static int join_setup(const JoinReq &q, bool force_wide, JoinSetup &s)
     // the fused path reads 12-byte partitioned tuples when the row ids fit 32 bits; the tiled path reads rhj_tuple
     s.wide = force_wide || !s.want_fused;
     s.nmin = nR < nS ? nR : nS;
-    // probe tuples per fused unit: whole buckets when there are plenty of them, smaller spans (each unit
-    // rebuilds its bucket's index) when a low radix would otherwise leave most CUs idle
-    uint32_t fused_span = FJ_SPAN;
-    if (bins < 256) {                                         // fewer buckets than CUs
-        uint64_t want = ((nR > nS ? nR : nS) / 512 + FJ_BATCH - 1) / FJ_BATCH * FJ_BATCH;
-        if (want < FJ_BATCH) want = FJ_BATCH;
-        if (want < fused_span) fused_span = (uint32_t)want;
-    }
+    const uint32_t fused_span = fused_span_for(bins, nR, nS);
     const uint32_t lds_cap = s.want_fused ? FUSED_LDS_CAP : g.force_hbm ? 0 : LDS_MAX_SLOTS * 4 / 5;     // tiled: load factor <= 0.8
     if (plan_args(nR, nS, bits, g.histpsum, lds_cap, s.want_fused ? fused_span : PR_UNIT, 0, nullptr, s.pa, s.ja)) return -1;
     // the plan runs behind the partition (a small one-pass partition runs it in its scan launch)
@@ -1288,6 +1301,234 @@ static int join_device(JoinReq q)
     return 0;
 }
 
+// ---- batched small joins (rhj_batch.hip.h) -------------------------------------------------------------------------------
+// rhj_join_batch_device: the joins batch_takes() names run as chunks of three launches and one stream synchronisation each;
+// the others, and the taken ones whose plan found a bucket beyond the LDS index, go through join_device one by one.
+//
+// A chunk's joins live side by side in ONE arena (every join its partitioned relations, tile counts, histograms and offsets,
+// units and their totals, summary, ticket and status words, stash, overflow regions for BJ_WGS workgroups and walk list:
+// 2.7 MB + 25 bytes a tuple), which never exceeds BATCH_ARENA_BUDGET: a batch whose joins need more is cut into chunks that
+// fit, in call order.
+constexpr size_t BATCH_ARENA_BUDGET = (size_t)1 << 30;
+constexpr uint64_t BATCH_MAX_JOINS = 65535;               // grid y / z of one chunk
+constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join's slot in the pinned block: PlanSummary, walk count
+static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
+
+static int batch_takes(int bits, uint64_t nR, uint64_t nS)
+{
+    if (bits < 1 || bits > PT_MAX_BITS || nR == 0 || nS == 0) return 0;
+    if (nR > (uint64_t)BJ_MAX_TILES * SM_TILE || nS > (uint64_t)BJ_MAX_TILES * SM_TILE) return 0;
+    if (sm_tiles(nR) > g.small_tiles || sm_tiles(nS) > g.small_tiles) return 0;
+    return !g.no_small && !g.no_fused && !g.force_hbm && !g.stamps;
+}
+
+struct BatchPlace {                                       // byte offsets of one join's buffers in the arena
+    size_t partR, partS, cntR, cntS, hp, units, ucount, summary, status, stash_cnt, stash_row, ovf, ovf_base, walk, end;
+    uint64_t unit_bound, status_words;
+    uint32_t span;
+};
+
+static void batch_place(int bits, uint64_t nR, uint64_t nS, size_t at, BatchPlace &L)
+{
+    const uint32_t bins = 1u << bits;
+    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    L.span = fused_span_for(bins, nR, nS);
+    L.unit_bound = (uint64_t)bins + (nR + nS) / L.span + 2;
+    L.status_words = L.unit_bound + 1 + 8;                // 8 ticket words in front
+    L.partR = take(nR * sizeof(rhj_tuple));
+    L.partS = take(nS * sizeof(rhj_tuple));
+    L.cntR = take((size_t)sm_tiles(nR) * 256 * 4);
+    L.cntS = take((size_t)sm_tiles(nS) * 256 * 4);
+    L.hp = take((size_t)4 * bins * 8);
+    L.units = take(L.unit_bound * sizeof(Unit));
+    L.ucount = take(L.unit_bound * 8);                    // JoinArgs::unit_count: the fused kernel leaves every unit's total there
+    L.summary = take(sizeof(PlanSummary) + 64);
+    L.status = take(L.status_words * 8 + 64);
+    L.stash_cnt = take(nR + nS + 64);
+    L.stash_row = take((nR + nS + 8) * 8);
+    L.ovf = take(fj_ovf_bytes(BJ_WGS));
+    L.ovf_base = take((size_t)BJ_WGS * 2 * FJ_GROUPS * 16 * 4);
+    L.walk = take((L.unit_bound + 1) * sizeof(FjWalkItem));
+    L.end = at;
+}
+
+// the arena grows to what a chunk needs, at least doubling, and never beyond the budget (ensure() adds slack of its own)
+static int batch_arena(size_t bytes)
+{
+    Buf &b = g.batch_arena;
+    if (bytes <= b.cap) return 0;
+    size_t want = 2 * b.cap > bytes ? 2 * b.cap : bytes;
+    if (want > BATCH_ARENA_BUDGET) want = BATCH_ARENA_BUDGET;
+    if (want < bytes) want = bytes;                       // (one join alone never needs more than a few MB)
+    if (b.p) HIP_TRY(hipFree(b.p));
+    b.p = nullptr; b.cap = 0;
+    HIP_TRY(hipMalloc(&b.p, want));
+    b.cap = want;
+    return 0;
+}
+
+struct BatchItem {
+    uint64_t   idx;                                       // the join's place in the caller's array
+    int        bits;
+    BatchPlace L;
+};
+
+// One chunk: items[lo, hi).  Joins whose plan refused the fused path are appended to `alone`.
+static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items, size_t lo, size_t hi, std::vector<uint64_t> &alone,
+                       uint64_t &units)
+{
+    const size_t n = hi - lo;
+    if (batch_arena(items[hi - 1].L.end)) return -1;
+    // pinned block: [n summary slots][n descriptors][3 lists of n join numbers]; descriptors and lists are uploaded in one copy
+    const size_t slots_bytes = n * BATCH_SLOT_WORDS * 8, desc_bytes = n * sizeof(BatchJoin), up_bytes = desc_bytes + 3 * n * 4;
+    if (slots_bytes + up_bytes > g.batch_pin_cap) {
+        if (g.batch_pin) HIP_TRY(hipHostFree(g.batch_pin));
+        g.batch_pin = nullptr; g.batch_pin_cap = 0;
+        const size_t want = 2 * (slots_bytes + up_bytes);
+        HIP_TRY(hipHostMalloc(&g.batch_pin, want, hipHostMallocDefault));
+        g.batch_pin_cap = want;
+    }
+    if (ensure(g.batch_desc, up_bytes)) return -1;
+    uint64_t *slots = (uint64_t *)g.batch_pin;
+    BatchJoin *hd = (BatchJoin *)((char *)g.batch_pin + slots_bytes);
+    uint32_t *hl = (uint32_t *)((char *)hd + desc_bytes);             // [0, n) histogram, [n, 2n) resident, [2n, 3n) gathering
+    const BatchJoin *dd = (const BatchJoin *)g.batch_desc.p;
+    const uint32_t *dl = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes);
+    memset(slots, 0xff, slots_bytes);                                 // (a slot nobody wrote reads as "no match total": an error, not an answer)
+    char *A = (char *)g.batch_arena.p;
+    uint32_t n_hist = 0, n_res = 0, n_gat = 0;
+    int max_bits = 1;
+    for (size_t k = 0; k < n; ++k) {
+        const BatchItem &it = items[lo + k];
+        const rhj_join_desc &q = joins[it.idx];
+        const BatchPlace &L = it.L;
+        const uint32_t bins = 1u << it.bits;
+        BatchJoin d;
+        memset((void *)&d, 0, sizeof(d));
+        d.r0 = RelArgs{q.d_R, (rhj_tuple *)(A + L.partR), (uint32_t *)(A + L.cntR), q.nR, sm_tiles(q.nR), 0, nullptr, nullptr};
+        d.r1 = RelArgs{q.d_S, (rhj_tuple *)(A + L.partS), (uint32_t *)(A + L.cntS), q.nS, sm_tiles(q.nS), 0, nullptr, nullptr};
+        uint64_t *hist = (uint64_t *)(A + L.hp), *psum = hist + 2 * bins;
+        d.hist = hist; d.psum = psum;
+        PlanArgs pa;
+        memset((void *)&pa, 0, sizeof(pa));
+        pa.histR = hist; pa.histS = hist + bins;
+        pa.units = (Unit *)(A + L.units); pa.summary = (PlanSummary *)(A + L.summary);
+        pa.lds_cap = FUSED_LDS_CAP; pa.lds_max_slots = LDS_MAX_SLOTS; pa.build_chunk = BUILD_CHUNK; pa.span_lds = L.span;
+        pa.slice_b0 = pa.slice_b1 = 0xffffffffu;
+        d.plan = pa;
+        FusedArgs &fa = d.f;
+        JoinArgs &ja = fa.j;
+        ja.partR = d.r0.out; ja.partS = d.r1.out;
+        ja.histR = hist; ja.histS = hist + bins; ja.psumR = psum; ja.psumS = psum + bins;
+        ja.units = pa.units; ja.summary = pa.summary; ja.unit_count = (uint64_t *)(A + L.ucount);
+        ja.out = q.d_out; ja.out_capacity = q.d_out ? q.out_capacity : 0;
+        ja.stash_nR = q.nR;
+        fa.stash_cnt = (uint8_t *)(A + L.stash_cnt); fa.stash_row = (uint64_t *)(A + L.stash_row);
+        fa.ticket = (uint32_t *)(A + L.status); fa.status = (uint64_t *)(A + L.status) + 8;
+        fa.nR = q.nR; fa.allow_resident = !g.no_resident; fa.radix_bits = (uint32_t)it.bits;
+        fa.unit_bound = L.unit_bound; fa.host_summary = slots + k * BATCH_SLOT_WORDS;
+        fa.ovf = (uint64_t *)(A + L.ovf); fa.ovf_base = (uint32_t *)(A + L.ovf_base); fa.walk = (FjWalkItem *)(A + L.walk);
+        d.zero_words = (uint64_t *)(A + L.status); d.n_zero = L.status_words;
+        d.bits = it.bits;
+        const uint32_t max_tiles = d.r0.tiles > d.r1.tiles ? d.r0.tiles : d.r1.tiles;
+        d.self_hist = max_tiles <= SM_SELF_TILES;
+        if (!d.self_hist) hl[n_hist++] = (uint32_t)k;
+        if (resident(q.nR < q.nS ? q.nR : q.nS, bins)) hl[n + n_res++] = (uint32_t)k;
+        else hl[2 * n + n_gat++] = (uint32_t)k;
+        if (it.bits > max_bits) max_bits = it.bits;
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+    }
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    if (n_hist) RHJ_LAUNCH(k_batch_hist, dim3(BJ_MAX_TILES, 2, n_hist), dim3(SM_BLOCK), 0, g.stream, dd, dl);
+    RHJ_LAUNCH(k_batch_scatter, dim3(BJ_MAX_TILES + 1, 2, (unsigned)n), dim3(SM_BLOCK), small_lds_bytes(max_bits), g.stream, dd);
+    if (n_res) RHJ_LAUNCH((k_batch_fused<true>), dim3(BJ_WGS, n_res), dim3(FJ_BLOCK), FUSED_LDS, g.stream, dd, dl + n, FUSED_LDS);
+    if (n_gat) RHJ_LAUNCH((k_batch_fused<false>), dim3(BJ_WGS, n_gat), dim3(FJ_BLOCK), FUSED_LDS, g.stream, dd, dl + 2 * n, FUSED_LDS);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    bool walked = false;
+    for (size_t k = 0; k < n; ++k) {
+        rhj_join_desc &q = joins[items[lo + k].idx];
+        PlanSummary plan;
+        memcpy(&plan, slots + k * BATCH_SLOT_WORDS, sizeof(plan));    // written by the join's last workgroup out (system-scope stores)
+        const uint64_t walk_units = slots[k * BATCH_SLOT_WORDS + sizeof(PlanSummary) / 8];
+        if (!plan.fused_ok) { alone.push_back(items[lo + k].idx); continue; }   // a bucket's build side beyond the LDS index
+        if (plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: batched join %zu left no match total (chained scan incomplete)\n", (size_t)items[lo + k].idx); return -1; }
+        if (q.d_out && walk_units != 0) {
+            // rare (a probe tuple with more than 16 matches, ...): this join's listed units, with its own arguments
+            RHJ_LAUNCH(k_join_walk, dim3(BJ_WGS), dim3(FJ_BLOCK), FUSED_LDS, g.stream, hd[k].f, FUSED_LDS);
+            walked = true;
+        }
+        q.matches = plan.matches;
+        q.rc = q.d_out && plan.matches > q.out_capacity ? 1 : 0;
+        q.path = 6;
+        units += plan.units;
+    }
+    if (walked) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+static int join_batch(rhj_join_desc *joins, uint64_t n)
+{
+    if (n == 0) return 0;
+    if (!joins) return -1;
+    if (ctx_init()) return -1;
+    const bool timed = g.timing >= 1;
+    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    std::vector<BatchItem> items;
+    std::vector<uint64_t> alone;
+    uint64_t sum_r = 0, sum_s = 0, sum_m = 0, units = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_join_desc &q = joins[i];
+        q.matches = 0; q.rc = 0; q.path = 0;
+        sum_r += q.nR; sum_s += q.nS;
+        if (q.nR == 0 || q.nS == 0) continue;                         // rhjoin.c:15-16: nothing to launch
+        const int bits = g.order_any ? auto_radix_bits(q.nR, q.nS) : g.bits;
+        if (!batch_takes(bits, q.nR, q.nS)) { alone.push_back(i); continue; }
+        BatchItem it;
+        it.idx = i; it.bits = bits;
+        items.push_back(it);
+    }
+    for (size_t lo = 0; lo < items.size();) {
+        size_t hi = lo, at = 0;
+        while (hi < items.size() && hi - lo < BATCH_MAX_JOINS) {
+            BatchPlace L;
+            batch_place(items[hi].bits, joins[items[hi].idx].nR, joins[items[hi].idx].nS, at, L);
+            if (hi > lo && L.end > BATCH_ARENA_BUDGET) break;
+            items[hi].L = L;
+            at = L.end;
+            ++hi;
+        }
+        if (batch_chunk(joins, items, lo, hi, alone, units)) return -1;
+        lo = hi;
+    }
+    // the joins that run alone, through the single-join code (which keeps its own stats: summed up below)
+    for (const uint64_t i : alone) {
+        rhj_join_desc &q = joins[i];
+        uint64_t m = 0;
+        const int rc = join_device({q.d_R, q.nR, q.d_S, q.nS, q.d_out, q.d_out ? q.out_capacity : 0, false, nullptr, &m, g.bits});
+        // (counting only, nothing was short: the tiled path says 1 whenever M passes the capacity, the small and fused paths
+        // only when there is a buffer — a batch says the latter for every join)
+        q.matches = m; q.rc = rc == 1 && !q.d_out ? 0 : rc; q.path = g.stats.reserved & 0xff;
+        if (rc < 0) return rc;
+        units += g.stats.units;
+    }
+    int any_short = 0;
+    for (uint64_t i = 0; i < n; ++i) { sum_m += joins[i].matches; any_short |= joins[i].rc == 1; }
+    rhj_stats &st = g.stats;
+    memset(&st, 0, sizeof(st));
+    st.n_r = sum_r; st.n_s = sum_s; st.matches = sum_m; st.units = units; st.radix_bits = g.bits;
+    st.reserved = 6;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
+        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
+    return any_short;
+}
+
 // k_filter_write is grid-stride, one wave per two tiles: enough workgroups to fill the chip a few times over
 unsigned filter_write_grid(uint64_t tiles)
 {
@@ -1582,6 +1823,14 @@ int rhj_join_device(const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uin
     return rc;
 }
 
+/* Many independent joins in one call (include/rhj.h; join_batch above) */
+int rhj_join_batch_device(rhj_join_desc *joins, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return join_batch(joins, n);
+}
+int rhj_batch_takes(int bits, uint64_t nR, uint64_t nS) { return batch_takes(bits, nR, nS); }
+
 /* The join of two relations given as KEY COLUMNS: tuple i of a relation is {keys[i], i} — what GetRelation makes of a base
  * relation (inter_res.c:199-204, :223-227: row_id = i) — without materialising the 16-byte tuples: on the two-pass partition
  * (9..15 radix bits) pass 1 reads the columns themselves, 8 bytes a tuple instead of 16 (the north_star's "coalesced uint64
@@ -1860,6 +2109,7 @@ static void release_current()
 #define RHJ_FREE(name) { if (g.name.p) (void)hipFree(g.name.p); g.name = Buf{}; }
     RHJ_WORKSPACE(RHJ_FREE)
 #undef RHJ_FREE
+    if (g.batch_pin) { (void)hipHostFree(g.batch_pin); g.batch_pin = nullptr; g.batch_pin_cap = 0; }
     for (auto &kv : g.columns) (void)hipFree(kv.second.dev);
     g.columns.clear();
     for (auto &kv : g.pinned) (void)hipHostUnregister((void *)kv.first);

@@ -1149,6 +1149,8 @@ __device__ __forceinline__ uint32_t fj_group_direct(const IX &X, const FjGather<
 // one unit).  Any check that fails raises ticket[4], the workgroups stop, and the ordinary kernel, always enqueued behind
 // this one, does the join (it returns at once when the speculation held).  The last workgroup out also checks that the
 // predicted totals add up to the relation's size (a bucket without partners has no unit to notice it).
+// The workgroups that share f (its ticket, its overflow regions) are those of one row of the grid: workgroup blockIdx.x of
+// gridDim.x, in a single join's launch (one row) as in a batched one (rhj_batch.hip.h: a row per join, blockIdx.y picks f).
 template <bool MAYRES, bool N32, bool SPEC = false>
 __device__ __forceinline__ void fj_body(const FusedArgs &f, uint32_t lds_bytes)
 {
@@ -1471,8 +1473,10 @@ __global__ __launch_bounds__(FJ_BLOCK) void k_join_spec(FusedArgs f, uint32_t ld
     }
 }
 
+// The fused join of one set of arguments by the workgroups of one row of the grid (k_join_fused: the whole launch;
+// k_batch_fused, rhj_batch.hip.h: one join's row).
 template <bool MAYRES, bool N32>
-__global__ __launch_bounds__(FJ_BLOCK) void k_join_fused(FusedArgs f, uint32_t lds_bytes)
+__device__ __forceinline__ void fj_join(const FusedArgs &f, uint32_t lds_bytes)
 {
     // behind k_join_spec: nothing to do when its speculation held (every workgroup reads the same word: all leave or none)
     if (f.spec && __hip_atomic_load(f.ticket + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -1511,6 +1515,12 @@ __global__ __launch_bounds__(FJ_BLOCK) void k_join_fused(FusedArgs f, uint32_t l
             }
         }
     }
+}
+
+template <bool MAYRES, bool N32>
+__global__ __launch_bounds__(FJ_BLOCK) void k_join_fused(FusedArgs f, uint32_t lds_bytes)
+{
+    fj_join<MAYRES, N32>(f, lds_bytes);
 }
 
 // ---- k_join_walk: the pairs of the units k_join_fused left on the walk list.  ALWAYS enqueued behind k_join_fused and

@@ -36,6 +36,7 @@
 //   rhj_subbucket.hip.h    the same on 9..13 radix bits: the r-bit partition, a stable split of every bucket on the next k bits
 //                          (pass B, which records where the probe side's tuples went), the low-radix path's internal join, an
 //                          emit that walks the canonical positions.
+//   rhj_batch.hip.h        many small joins in the launches of one: the small path's kernel bodies over a third grid dimension.
 //   rhj_filter.hip.h       predicate -> ballot masks -> ascending index list.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
@@ -51,5 +52,6 @@
 #include "rhj_lowradix.hip.h"
 #include "rhj_subbucket.hip.h"
 #include "rhj_small.hip.h"
+#include "rhj_batch.hip.h"
 #include "rhj_filter.hip.h"
 #include "rhj_diag.hip.h"

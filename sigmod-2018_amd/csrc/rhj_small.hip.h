@@ -46,18 +46,22 @@ __host__ __device__ constexpr size_t small_lds_bytes(int bits)
     return (size_t)SM_TILE * 16 + ((size_t)SM_WAVES + 3) * ((size_t)1 << bits) * 4;
 }
 
-__global__ __launch_bounds__(SM_BLOCK) void k_small_hist(RelArgs r0, RelArgs r1, int bits, uint64_t *zero_words, uint64_t n_zero)
+// The kernels' bodies are device functions that take the workgroup's coordinates (bx, by) in a grid of (gx, gy) as arguments: the
+// single-join kernels below hand in those of their own launch, the batched ones (rhj_batch.hip.h) those of one join's plane
+// of a three-dimensional grid.
+__device__ __forceinline__ void small_hist_body(const RelArgs &r0, const RelArgs &r1, int bits, uint64_t *zero_words, uint64_t n_zero,
+                                                uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
 {
     __shared__ uint32_t tile_h[1u << PT_MAX_BITS];
     const uint32_t tid = threadIdx.x;
     const uint32_t bins = 1u << bits, mask = bins - 1u;
     SM_STAMP(0, 0);
     {
-        const uint64_t wgs = (uint64_t)gridDim.x * gridDim.y, me = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        const uint64_t wgs = (uint64_t)gx * gy, me = (uint64_t)by * gx + bx;
         for (uint64_t i = me * SM_BLOCK + tid; i < n_zero; i += wgs * SM_BLOCK) zero_words[i] = 0;
     }
-    const RelArgs &r = blockIdx.y ? r1 : r0;
-    const uint32_t t = blockIdx.x;
+    const RelArgs &r = by ? r1 : r0;
+    const uint32_t t = bx;
     if (t >= r.tiles) return;
     if (tid < bins) tile_h[tid] = 0;
     __syncthreads();
@@ -71,6 +75,11 @@ __global__ __launch_bounds__(SM_BLOCK) void k_small_hist(RelArgs r0, RelArgs r1,
     __syncthreads();
     if (tid < bins) r.cnt[(size_t)t * bins + tid] = tile_h[tid];
     SM_STAMP(0, 1);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_small_hist(RelArgs r0, RelArgs r1, int bits, uint64_t *zero_words, uint64_t n_zero)
+{
+    small_hist_body(r0, r1, bits, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // Sums of a relation's digit columns: for digit d (threads 0..bins-1 get the result) the tuples of digit d in the
@@ -165,8 +174,9 @@ __device__ __forceinline__ void small_selfhist(const RelArgs &r, uint32_t t, int
 // grid (max tiles + 1, 2): workgroup (x, rel) scatters tile x of relation rel; workgroup (max tiles, 0) is the plan's.
 // self_hist: no k_small_hist launch went before (both relations have at most SM_SELF_TILES tiles): the digit counts are
 // taken from the tuples, and this launch clears the join kernel's words.
-__global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs r1, int bits, uint64_t *hist, uint64_t *psum, PlanArgs plan,
-                                                            int self_hist, uint64_t *zero_words, uint64_t n_zero)
+__device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelArgs &r1, int bits, uint64_t *hist, uint64_t *psum,
+                                                   const PlanArgs &plan, int self_hist, uint64_t *zero_words, uint64_t n_zero,
+                                                   uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint64_t sm[SM_BLOCK / 64 + 1];
@@ -181,16 +191,16 @@ __global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     SM_STAMP(1, 0);
     if (self_hist) {
-        const uint64_t wgs = (uint64_t)gridDim.x * gridDim.y, me = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        const uint64_t wgs = (uint64_t)gx * gy, me = (uint64_t)by * gx + bx;
         for (uint64_t i = me * SM_BLOCK + tid; i < n_zero; i += wgs * SM_BLOCK) zero_words[i] = 0;
     }
 
-    if (blockIdx.x == gridDim.x - 1u) {
+    if (bx == gx - 1u) {
         // ---- the plan's workgroup: bucket sizes and starts of both relations, then the fused path's plan over them:
         // one unit per span_lds probe tuples of every bucket both sides are present in, probe side = R when
         // cR >= cS (rhjoin.c:86); fused_ok only if every such bucket's build side fits the LDS index (otherwise the
         // host plans again for the tiled path, k_plan)
-        if (blockIdx.y != 0) return;
+        if (by != 0) return;
         uint64_t c[2] = {0, 0};
         if (self_hist) {
             for (int rel = 0; rel < 2; ++rel) {
@@ -283,8 +293,8 @@ __global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs 
         return;
     }
 
-    const RelArgs &r = blockIdx.y ? r1 : r0;
-    const uint32_t t = blockIdx.x;
+    const RelArgs &r = by ? r1 : r0;
+    const uint32_t t = bx;
     if (t >= r.tiles) return;
     const uint64_t lt = lanemask_lt();
     const uint64_t beg = (uint64_t)t * SM_TILE;
@@ -367,6 +377,12 @@ __global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs 
     }
     SM_FINE(6);
     SM_STAMP(1, 1);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs r1, int bits, uint64_t *hist, uint64_t *psum, PlanArgs plan,
+                                                            int self_hist, uint64_t *zero_words, uint64_t n_zero)
+{
+    small_scatter_body(r0, r1, bits, hist, psum, plan, self_hist, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 }  // namespace rhj

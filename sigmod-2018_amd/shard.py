@@ -6,7 +6,8 @@ a single join:
 
 * across joins — independent joins of a plan (best_tree.c starts a new inter_res node for
   predicates that share no relation, inter_res.c:147-150) are dealt to ranks, largest first
-  (`assign_joins`, `run_independent_joins`); each rank runs whole joins on its own GPU;
+  (`assign_joins`, `run_independent_joins`); each rank runs whole joins on its own GPU, the ones it
+  owns in one batched call where the ops object has `join_many`;
 * inside one join — bucket b of R only ever meets bucket b of S (rhjoin.c:42-57), so ranks
   take contiguous BUCKET RANGES (equal width, or balanced by histR+histS: `bucket_ranges`) and
   join them with ONE call each — `rhj_join_device_range`: the join's own first partition pass
@@ -156,6 +157,14 @@ class RhjOps:
             pairs, m = self.rhj.join_device(R, S, capacity=m, bucket_range=bucket_range)
         return pairs
 
+    def join_many(self, joins, bits):
+        """the canonical pair lists of independent joins [(R, S), ...] in one call (rhj_join_batch_device: the small ones
+        share three launches and one stream synchronisation); list i is what join(R_i, S_i, bits) returns"""
+        self.rhj.set_bits(bits)
+        if self.rhj.lib.rhj_get_order():
+            raise RuntimeError("sharded joins need the canonical order mode (rhj_set_order(0) / RHJ_ORDER unset)")
+        return [pairs for pairs, _ in self.rhj.join_batch_device(joins)]
+
 
 # ------------------------------------------------------------------ the exchange step
 
@@ -247,9 +256,13 @@ def run_independent_joins(ops, joins, bits, group=None, gather=True, consumers=N
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     owner = assign_joins([int(r.shape[0]) + int(s.shape[0]) for r, s in joins], world)
     results = [None] * len(joins)
-    for i, (R, S) in enumerate(joins):
-        if owner[i] == rank:
-            results[i] = ops.join(R, S, bits)
+    mine = [i for i in range(len(joins)) if owner[i] == rank]
+    if hasattr(ops, "join_many"):                       # the joins this rank owns in one call (RhjOps: batched launches)
+        for i, pairs in zip(mine, ops.join_many([joins[i] for i in mine], bits)):
+            results[i] = pairs
+    else:
+        for i in mine:
+            results[i] = ops.join(joins[i][0], joins[i][1], bits)
     if consumers is None:
         consumers = ["all" if gather else None] * len(joins)
     if not dist.is_initialized() or world == 1 or not joins:
