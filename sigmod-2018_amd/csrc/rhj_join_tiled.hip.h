@@ -10,7 +10,7 @@ namespace rhj {
 
 constexpr int PR_BLOCK = 256;                     // probe workgroup
 constexpr int PR_V = 4;                           // probe tuples per thread
-constexpr int PR_UNIT = PR_BLOCK * PR_V;          // 2048 probe tuples per unit
+constexpr int PR_UNIT = PR_BLOCK * PR_V;          // 1024 probe tuples per unit
 constexpr int PR_MINW = 5;                        // waves per SIMD the probe kernels are compiled for (96 VGPRs)
 
 struct PlanArgs {
