@@ -258,7 +258,7 @@ typedef struct rhj_stats {
     uint64_t n_r, n_s, matches;
     uint64_t units, hbm_units, max_build, table_slots;
     int radix_bits;
-    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit), 6 a batch (rhj_join_batch_device) */
+    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit), 6 a batch (rhj_join_batch_device), 7 a batch of filters (rhj_filter_batch_device) */
 } rhj_stats;
 
 /* Join two device-resident AoS relations (rhj_tuple[nR], rhj_tuple[nS]).
@@ -318,6 +318,39 @@ int rhj_partition_device(const rhj_tuple *d_in, uint64_t n, rhj_tuple *d_out,
  * 8-byte alignment (a view such as col + 1 is fine).  */
 int rhj_filter_device(const uint64_t *d_col, const uint64_t *d_sel, uint64_t n,
                       char op, uint64_t value, uint64_t *d_out, uint64_t *hits);
+
+/* Many independent filters in one call (csrc/rhj_filter_batch.hip.h), each a conjunction of 1..RHJ_FILTER_MAX_TERMS predicates
+ * over columns of one relation: d_out[0..hits) gets the ascending i in [0, n) for which EVERY term holds on
+ * col_t[d_sel ? d_sel[i] : i] (unsigned compare, value already converted as for rhj_filter_device); nothing at or beyond
+ * d_out[hits] is written; hits is exact, also with d_out == NULL (count only).  A one-term filter returns bit for bit what
+ * rhj_filter_device returns.  Columns and row-id vectors may be shared between filters and between terms; outputs must not
+ * overlap; every pointer needs only 8-byte alignment (a filter takes the 16-byte loads only when the scanned vector of every
+ * term - d_sel, or every term's column without one - starts on a 16-byte boundary).  The filters rhj_filter_batch_takes() names
+ * run together in two launches (masks, index lists) and one stream synchronisation per chunk of at most 4096 filters and 1 GiB
+ * of masks, whatever their number; a larger filter is run alone inside the same call (path 0).  n == 0: rc 0, hits 0, nothing
+ * launched.  The whole batch is validated before anything is launched: an unknown operator, nterms outside
+ * 1..RHJ_FILTER_MAX_TERMS or a NULL column with n > 0 give that filter rc -3, nothing runs and the call returns -3.  Otherwise
+ * returns 0, <0 on a HIP error.  rhj_last_stats() afterwards: n_r the rows and matches the hits summed over the filters, units
+ * the filters that went through the batched launches, ms_total of the whole call (timing level >= 1), path 7. */
+#define RHJ_FILTER_MAX_TERMS 4
+typedef struct rhj_filter_term {
+    const uint64_t *d_col;
+    uint64_t        value;
+    char            op;          /* '<', '>' or '=' */
+} rhj_filter_term;
+typedef struct rhj_filter_desc {
+    const uint64_t *d_sel; uint64_t n;   /* as rhj_filter_device: d_sel NULL scans col[0..n) of every term */
+    int             nterms;
+    rhj_filter_term terms[RHJ_FILTER_MAX_TERMS];
+    uint64_t       *d_out;      /* capacity n; NULL: count only */
+    uint64_t        hits;       /* out */
+    int             rc;         /* out */
+    int             path;       /* out: 7 the batched launches, 0 run alone inside the call */
+} rhj_filter_desc;
+int rhj_filter_batch_device(rhj_filter_desc *filters, uint64_t n);
+/* 1 when a filter of this many rows goes into the batched launches: 1..4 194 304 rows, the class whose write pass sums its
+ * tile counts itself (pure function: needs no device) */
+int rhj_filter_batch_takes(uint64_t rows);
 
 /* Bucket-range sharding of ONE join over the GPUs of a node (bucket b of R only meets
  * bucket b of S, rhjoin.c:42-57): the bucket histogram of a device-resident relation on the current

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "RadixHashJoin", "Filter", "InsertResult", "InsertRowIdResult", "GetResultNum", "FindResultRowId",
     "FindResultTuples", "FreeResult", "PrintResult", "FreeRelation", "SchedulerInit", "SchedulerDestroy",
     "rhj_set_radix_bits", "rhj_get_radix_bits", "rhj_set_empty_mode", "rhj_set_node_pairs", "rhj_set_device", "rhj_get_device",
-    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device",
+    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device", "rhj_filter_batch_device", "rhj_filter_batch_takes",
     "rhj_register_relation_map", "rhj_unregister_relation_map", "rhj_registered_columns", "rhj_pinned_ranges",
     "rhj_bucket_histogram_device", "rhj_select_bucket_range_device", "rhj_join_device_range", "rhj_join_device_slice", "rhj_pin_refusals",
     "rhj_release", "rhj_last_stats", "rhj_version",
@@ -83,6 +83,20 @@ class JoinDesc(C.Structure):
                 ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("matches", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
 
 
+FILTER_MAX_TERMS = 4                     # RHJ_FILTER_MAX_TERMS
+
+
+class FilterTerm(C.Structure):
+    """rhj_filter_term (include/rhj.h): one predicate of a batched filter"""
+    _fields_ = [("d_col", C.c_void_p), ("value", C.c_uint64), ("op", C.c_char)]
+
+
+class FilterDesc(C.Structure):
+    """rhj_filter_desc (include/rhj.h): one filter of rhj_filter_batch_device"""
+    _fields_ = [("d_sel", C.c_void_p), ("n", C.c_uint64), ("nterms", C.c_int), ("terms", FilterTerm * FILTER_MAX_TERMS),
+                ("d_out", C.c_void_p), ("hits", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ms_hist", "ms_scan", "ms_scatter", "ms_plan", "ms_build", "ms_count",
                                          "ms_offsets", "ms_probe", "ms_total", "ms_h2d", "ms_d2h")] + \
@@ -92,7 +106,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -171,6 +185,10 @@ def load_library(path=None):
         L.rhj_join_keys_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
     L.rhj_partition_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rhj_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char, C.c_uint64, C.c_void_p, u64p]
+    if hasattr(L, "rhj_filter_batch_device"):     # (A/B runs load earlier builds through this module too)
+        L.rhj_filter_batch_device.argtypes = [C.POINTER(FilterDesc), C.c_uint64]
+        L.rhj_filter_batch_takes.argtypes = [C.c_uint64]
+        L.rhj_filter_batch_takes.restype = C.c_int
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -317,6 +335,36 @@ class RHJ:
         if rc < 0:
             raise RuntimeError("rhj_filter_device failed (%d)" % rc)
         return out[:hits.value]
+
+    def filter_batch_device(self, filters, count_only=False, with_info=False):
+        """Many independent conjunctive filters in one call (rhj_filter_batch_device): filters = [(terms, d_sel), ...] with
+        terms = [(d_col, op, value), ...] (1..4 of them, columns of one relation; int64 tensors as for filter_device) and
+        d_sel a row-id vector or None.  Returns [(indices tensor, hits), ...], or (None, hits) with count_only; the index lists
+        are views of one allocation.  with_info: also the list of the filters' path ids (7: batched)."""
+        torch = self.torch
+        n = len(filters)
+        arr = (FilterDesc * max(n, 1))()
+        rows = []
+        for d, (terms, d_sel) in zip(arr, filters):
+            if not 1 <= len(terms) <= FILTER_MAX_TERMS:
+                raise ValueError("a filter has 1..%d terms, not %d" % (FILTER_MAX_TERMS, len(terms)))
+            d.d_sel = d_sel.data_ptr() if d_sel is not None else None
+            d.n = terms[0][0].shape[0] if d_sel is None else d_sel.shape[0]
+            d.nterms = len(terms)
+            for t, (d_col, op, value) in zip(d.terms, terms):
+                t.d_col, t.op, t.value = d_col.data_ptr(), op.encode(), int(value) & ((1 << 64) - 1)
+            rows.append(d.n)
+        out = None
+        if not count_only:
+            starts = np.concatenate([[0], np.cumsum([(r + 1) // 2 * 2 for r in rows])]).astype(np.int64)      # 16-byte aligned pieces
+            out = torch.empty(max(int(starts[-1]), 1), dtype=torch.int64, device=self.dev)
+            for i in range(n):
+                arr[i].d_out = out.data_ptr() + 8 * int(starts[i])
+        rc = self.lib.rhj_filter_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_filter_batch_device failed (%d)" % rc)
+        res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
 
     def pairs_to_numpy(self, t):
         a = t.cpu().numpy()

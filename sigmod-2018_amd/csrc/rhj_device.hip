@@ -77,7 +77,7 @@ enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSE
     X(partR) X(partS) X(tmpR) X(tmpS) X(cntR) X(cntS) X(chunk) X(histpsum) X(passhp) X(units) X(bunits) X(ldsb) X(meta)   \
     X(summary) X(ucount) X(ubase) X(uflag) X(tab32) X(tab64) X(stash_cnt) X(stash_row) X(status) X(dbg) X(bsum) X(digR)  \
     X(digS) X(ovf) X(ovf_base) X(runR) X(runS) X(walk) X(xrows) X(lr_tmp) X(lr_words) X(lr_status) X(stripR) X(stripS)   \
-    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc)                                      \
+    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc) X(fbatch_arena)                      \
     X(inR) X(inS) X(out) X(fcol_sel) X(fmask) X(ftile) X(fbase) X(fout)                                                    \
     X(fcol)                                                      /* staging of an unregistered column (host Filter()) */
 
@@ -127,8 +127,8 @@ struct Ctx {
     uint64_t    node_pairs = 65535;
     hipEvent_t  ev[ST_N + 1] = {};
     hipEvent_t  ev_x[4] = {};
-    hipEvent_t  ev_batch[2] = {};    // rhj_join_batch_device: the whole call (the joins it runs alone record the stage events)
-    void       *batch_pin = nullptr; // rhj_join_batch_device: pinned host block of a chunk's summaries, descriptors and join lists
+    hipEvent_t  ev_batch[2] = {};    // rhj_join_batch_device, rhj_filter_batch_device: the whole call (what they run alone records the stage events)
+    void       *batch_pin = nullptr; // the same two: pinned host block of a chunk's answers (summaries / hit totals) and of what is uploaded for it
     size_t      batch_pin_cap = 0;
 #define RHJ_BUF(name) Buf name;
     RHJ_WORKSPACE(RHJ_BUF)
@@ -1353,9 +1353,8 @@ static void batch_place(int bits, uint64_t nR, uint64_t nS, size_t at, BatchPlac
 }
 
 // the arena grows to what a chunk needs, at least doubling, and never beyond the budget (ensure() adds slack of its own)
-static int batch_arena(size_t bytes)
+static int batch_arena(Buf &b, size_t bytes)
 {
-    Buf &b = g.batch_arena;
     if (bytes <= b.cap) return 0;
     size_t want = 2 * b.cap > bytes ? 2 * b.cap : bytes;
     if (want > BATCH_ARENA_BUDGET) want = BATCH_ARENA_BUDGET;
@@ -1364,6 +1363,18 @@ static int batch_arena(size_t bytes)
     b.p = nullptr; b.cap = 0;
     HIP_TRY(hipMalloc(&b.p, want));
     b.cap = want;
+    return 0;
+}
+
+// the pinned host block of a chunk (both batched entry points; every chunk ends in a stream synchronisation before the next
+// one writes the block again)
+static int batch_pinned(size_t bytes)
+{
+    if (bytes <= g.batch_pin_cap) return 0;
+    if (g.batch_pin) HIP_TRY(hipHostFree(g.batch_pin));
+    g.batch_pin = nullptr; g.batch_pin_cap = 0;
+    HIP_TRY(hipHostMalloc(&g.batch_pin, 2 * bytes, hipHostMallocDefault));
+    g.batch_pin_cap = 2 * bytes;
     return 0;
 }
 
@@ -1378,17 +1389,10 @@ static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items
                        uint64_t &units)
 {
     const size_t n = hi - lo;
-    if (batch_arena(items[hi - 1].L.end)) return -1;
+    if (batch_arena(g.batch_arena, items[hi - 1].L.end)) return -1;
     // pinned block: [n summary slots][n descriptors][3 lists of n join numbers]; descriptors and lists are uploaded in one copy
     const size_t slots_bytes = n * BATCH_SLOT_WORDS * 8, desc_bytes = n * sizeof(BatchJoin), up_bytes = desc_bytes + 3 * n * 4;
-    if (slots_bytes + up_bytes > g.batch_pin_cap) {
-        if (g.batch_pin) HIP_TRY(hipHostFree(g.batch_pin));
-        g.batch_pin = nullptr; g.batch_pin_cap = 0;
-        const size_t want = 2 * (slots_bytes + up_bytes);
-        HIP_TRY(hipHostMalloc(&g.batch_pin, want, hipHostMallocDefault));
-        g.batch_pin_cap = want;
-    }
-    if (ensure(g.batch_desc, up_bytes)) return -1;
+    if (batch_pinned(slots_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
     uint64_t *slots = (uint64_t *)g.batch_pin;
     BatchJoin *hd = (BatchJoin *)((char *)g.batch_pin + slots_bytes);
     uint32_t *hl = (uint32_t *)((char *)hd + desc_bytes);             // [0, n) histogram, [n, 2n) resident, [2n, 3n) gathering
@@ -1609,6 +1613,172 @@ int filter_eq2_device(const uint64_t *colA, const uint64_t *selA, const uint64_t
     memset(&g.stats, 0, sizeof(g.stats));
     g.stats.n_r = n; g.stats.matches = *hits;
     g.stats.ms_total = g.stats.ms_probe = stage_ms(ST_HIST, ST_END);
+    return 0;
+}
+
+// ---- batched filters (rhj_filter_batch.hip.h) -----------------------------------------------------------------------------
+// rhj_filter_batch_device: the filters filter_batch_takes() names run as chunks of two launches and one stream synchronisation
+// each; a larger one is run alone, by the same mask kernel and the scan + write launches of a large single filter.
+//
+// A chunk's filters live side by side in ONE arena (every filter its mask words, 16 bytes per 128 rows, and its tile counts),
+// which never exceeds BATCH_ARENA_BUDGET, and a chunk never holds more than FBATCH_MAX_FILTERS filters: a batch beyond either is
+// cut into chunks, in call order.  The arena is the batch's own: g.fmask / g.ftile / g.fbase stay what the single calls made them.
+constexpr uint64_t FBATCH_MAX_ROWS = FILTER_SELF_TILES * FILTER_TILE;
+constexpr size_t FBATCH_MAX_FILTERS = 4096;
+
+static int filter_batch_takes(uint64_t rows) { return rows >= 1 && rows <= FBATCH_MAX_ROWS; }
+
+static size_t fbatch_mask_bytes(uint64_t n) { return (size_t)((n + 2 * WAVE - 1) / (2 * WAVE)) * 16; }
+
+struct FBatchItem {
+    uint64_t idx;                                         // the filter's place in the caller's array
+    size_t   masks, counts, end;                          // byte offsets in the arena
+};
+
+static void fbatch_desc(const rhj_filter_desc &q, uint64_t *masks, uint64_t *counts, uint64_t *h_total, FBatchDesc &d)
+{
+    memset((void *)&d, 0, sizeof(d));
+    d.sel = q.d_sel; d.n = q.n; d.out = q.d_out; d.masks = masks; d.tile_count = counts; d.h_total = (unsigned long long *)h_total;
+    d.nterms = q.nterms;
+    uintptr_t scanned = (uintptr_t)q.d_sel;               // the mask pass's 16-byte loads need every scanned vector's base aligned
+    for (int t = 0; t < q.nterms; ++t) {
+        d.t[t].col = q.terms[t].d_col; d.t[t].value = q.terms[t].value; d.t[t].op = op_code(q.terms[t].op);
+        if (!q.d_sel) scanned |= (uintptr_t)q.terms[t].d_col;
+    }
+    d.vec = (scanned & 15u) == 0;
+}
+
+// One chunk: items[lo, hi), every one with 1..FBATCH_MAX_ROWS rows.
+static int fbatch_chunk(rhj_filter_desc *filters, const std::vector<FBatchItem> &items, size_t lo, size_t hi)
+{
+    const size_t nf = hi - lo;
+    if (batch_arena(g.fbatch_arena, items[hi - 1].end)) return -1;
+    // pinned block: [nf hit totals][nf descriptors][nf + 1 tile starts][nf + 1 task starts]; all but the totals are uploaded in one copy
+    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(FBatchDesc), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
+    if (batch_pinned(totals_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
+    uint64_t *totals = (uint64_t *)g.batch_pin;
+    FBatchDesc *hd = (FBatchDesc *)((char *)g.batch_pin + totals_bytes);
+    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes), *task_start = tile_start + nf + 1;
+    const FBatchDesc *dd = (const FBatchDesc *)g.batch_desc.p;
+    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes), *d_task_start = d_tile_start + nf + 1;
+    memset(totals, 0xff, totals_bytes);                   // (a slot nobody wrote reads as "no total": an error, not an answer)
+    char *A = (char *)g.fbatch_arena.p;
+    uint32_t tiles = 0, tasks = 0;
+    for (size_t k = 0; k < nf; ++k) {
+        const FBatchItem &it = items[lo + k];
+        const rhj_filter_desc &q = filters[it.idx];
+        FBatchDesc d;
+        fbatch_desc(q, (uint64_t *)(A + it.masks), (uint64_t *)(A + it.counts), totals + k, d);
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        const uint32_t t = (uint32_t)((q.n + FILTER_TILE - 1) / FILTER_TILE);
+        tile_start[k] = tiles; task_start[k] = tasks;
+        tiles += t;
+        tasks += q.d_out ? (t + 1) / 2 : 1;               // count only: one wave sums the tile counts, nothing else to do
+    }
+    tile_start[nf] = tiles; task_start[nf] = tasks;
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    RHJ_LAUNCH(k_fbatch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)nf);
+    const uint32_t want = (tasks + 256 / WAVE - 1) / (256 / WAVE), cap = (uint32_t)g.cus * 32;      // grid-stride, as filter_write_grid
+    RHJ_LAUNCH(k_fbatch_write, dim3(want < cap ? want : cap), dim3(256), 0, g.stream, dd, d_task_start, (uint32_t)nf);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < nf; ++k) {
+        rhj_filter_desc &q = filters[items[lo + k].idx];
+        const uint64_t h = ((volatile uint64_t *)totals)[k];            // written by the wave of the filter's last task (system-scope store)
+        if (h > q.n) { fprintf(stderr, "rhj: batched filter %zu left no hit total\n", (size_t)items[lo + k].idx); return -1; }
+        q.hits = h; q.path = 7;
+    }
+    return 0;
+}
+
+// a filter beyond FBATCH_MAX_ROWS, alone: k_fbatch_mask over its one descriptor, then the scan and k_filter_write<false>
+static int fbatch_alone(rhj_filter_desc &q)
+{
+    const uint64_t n = q.n, tiles = (n + FILTER_TILE - 1) / FILTER_TILE;
+    if (tiles >= (1ull << 32)) return -2;
+    const size_t up_bytes = sizeof(FBatchDesc) + 2 * 4;
+    if (ensure(g.fmask, fbatch_mask_bytes(n)) || ensure(g.ftile, tiles * 8) || ensure(g.fbase, tiles * 8) ||
+        ensure(g.summary, sizeof(PlanSummary)) || batch_pinned(up_bytes) || ensure(g.batch_desc, up_bytes))
+        return -1;
+    FBatchDesc *hd = (FBatchDesc *)g.batch_pin;
+    uint32_t *tile_start = (uint32_t *)(hd + 1);
+    FBatchDesc d;
+    fbatch_desc(q, (uint64_t *)g.fmask.p, (uint64_t *)g.ftile.p, nullptr, d);
+    memcpy((void *)hd, (const void *)&d, sizeof(d));
+    tile_start[0] = 0; tile_start[1] = (uint32_t)tiles;
+    uint64_t *total = &((PlanSummary *)g.summary.p)->matches;
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    RHJ_LAUNCH(k_fbatch_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, (const FBatchDesc *)g.batch_desc.p,
+               (const uint32_t *)((const char *)g.batch_desc.p + sizeof(FBatchDesc)), 1u);
+    uint64_t h = 0;
+    if (q.d_out) {
+        if (filter_write_out(n, tiles, total, q.d_out, &h)) return -1;
+    } else {                                              // count only: the scan's total is all there is to fetch
+        if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
+        HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        h = *(volatile uint64_t *)&g.pin->hits;
+    }
+    q.hits = h; q.path = 0;
+    return 0;
+}
+
+static int filter_batch(rhj_filter_desc *filters, uint64_t n)
+{
+    if (n == 0) return 0;
+    if (!filters) return -1;
+    bool invalid = false;                                 // the whole batch is validated before anything is launched
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_filter_desc &q = filters[i];
+        q.hits = 0; q.rc = 0; q.path = 0;
+        bool ok = q.nterms >= 1 && q.nterms <= RHJ_FILTER_MAX_TERMS;
+        for (int t = 0; ok && t < q.nterms; ++t) ok = op_code(q.terms[t].op) >= 0 && (q.n == 0 || q.terms[t].d_col != nullptr);
+        if (!ok) { q.rc = -3; invalid = true; }
+    }
+    if (invalid) return -3;
+    if (ctx_init()) return -1;
+    const bool timed = g.timing >= 1;
+    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    std::vector<FBatchItem> items;
+    std::vector<uint64_t> alone;
+    uint64_t rows = 0, hits = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rows += filters[i].n;
+        if (filters[i].n == 0) continue;                  // nothing to launch
+        if (!filter_batch_takes(filters[i].n)) { alone.push_back(i); continue; }
+        FBatchItem it;
+        it.idx = i; it.masks = it.counts = it.end = 0;
+        items.push_back(it);
+    }
+    for (size_t lo = 0; lo < items.size();) {
+        size_t hi = lo, at = 0;
+        while (hi < items.size() && hi - lo < FBATCH_MAX_FILTERS) {
+            const uint64_t rows_hi = filters[items[hi].idx].n;
+            const size_t masks = at, counts = masks + ((fbatch_mask_bytes(rows_hi) + 255) & ~(size_t)255);
+            const size_t end = counts + (((size_t)((rows_hi + FILTER_TILE - 1) / FILTER_TILE) * 8 + 255) & ~(size_t)255);
+            if (hi > lo && end > BATCH_ARENA_BUDGET) break;
+            items[hi].masks = masks; items[hi].counts = counts; items[hi].end = end;
+            at = end;
+            ++hi;
+        }
+        if (fbatch_chunk(filters, items, lo, hi)) return -1;
+        lo = hi;
+    }
+    for (const uint64_t i : alone) {
+        const int rc = fbatch_alone(filters[i]);
+        if (rc < 0) { filters[i].rc = rc; return rc; }
+    }
+    for (uint64_t i = 0; i < n; ++i) hits += filters[i].hits;
+    rhj_stats &st = g.stats;
+    memset(&st, 0, sizeof(st));
+    st.n_r = rows; st.matches = hits; st.units = items.size();
+    st.reserved = 7;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
+        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
     return 0;
 }
 
@@ -2075,6 +2245,14 @@ int rhj_filter_device(const uint64_t *d_col, const uint64_t *d_sel, uint64_t n, 
     if (hits) *hits = h;
     return rc;
 }
+
+/* Many independent conjunctive filters in one call (include/rhj.h; filter_batch above) */
+int rhj_filter_batch_device(rhj_filter_desc *filters, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return filter_batch(filters, n);
+}
+int rhj_filter_batch_takes(uint64_t rows) { return filter_batch_takes(rows); }
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */
 

@@ -105,6 +105,68 @@ constexpr uint32_t FILTER_SPARSE = 1024;
 // every wave sums the counts in front of its tiles itself (L2-resident, sixteen loads a lane at most); the wave of the last
 // task leaves the hit total in pinned host memory: mask + write are the filter's two launches, nothing is copied back.
 constexpr uint64_t FILTER_SELF_TILES = 1024;
+
+// One task (a pair of tiles) of one wave: the body of k_filter_write, and of k_fbatch_write (rhj_filter_batch.hip.h), whose
+// tasks belong to many filters.
+template <bool SELF>
+__device__ __forceinline__ void filter_write_task(uint64_t n, uint64_t ntiles, uint64_t ntasks, uint64_t task, const uint64_t *masks,
+                                                  const uint64_t *tile_base, uint64_t *out, unsigned long long *h_total, uint32_t lane,
+                                                  uint64_t lt)
+{
+    const uint64_t tile = 2 * task + (lane >> 5);
+    const uint64_t ebase = tile * FILTER_TILE + (uint64_t)(lane & 31u) * (2 * WAVE);    // first element of this lane's round
+    uint64_t me = 0, mo = 0;
+    if (ebase < n) {
+        const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(masks + (ebase >> 6));
+        me = x.x; mo = x.y;
+    }
+    uint64_t tb = 0;
+    if (SELF) {
+        uint64_t front = 0;                       // hits of the tiles in front of this pair
+        for (uint64_t t = lane; t < 2 * task; t += WAVE) front += tile_base[t];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) front += __shfl_xor(front, d, 64);
+        const uint64_t c0 = 2 * task < ntiles ? tile_base[2 * task] : 0, c1 = 2 * task + 1 < ntiles ? tile_base[2 * task + 1] : 0;
+        tb = front + (lane >= 32 ? c0 : 0);
+        if (task == ntasks - 1 && lane == 0) __hip_atomic_store(h_total, front + c0 + c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else
+        tb = tile < ntiles ? tile_base[tile] : 0;
+    const uint32_t pc = (uint32_t)__popcll(me) + (uint32_t)__popcll(mo);
+    if (__ballot(pc != 0) == 0) return;
+    uint32_t incl = pc;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += y;
+    }
+    const uint32_t t0 = __shfl(incl, 31, 64), t2 = __shfl(incl, 63, 64);
+    if (t2 <= FILTER_SPARSE) {
+        uint64_t pos = tb + (incl - pc) - (lane >= 32 ? t0 : 0u);
+        while (me | mo) {                          // ascending: element 2b of the even word, 2b + 1 of the odd one
+            const uint32_t be = me ? (uint32_t)__builtin_ctzll(me) : 64u, bo = mo ? (uint32_t)__builtin_ctzll(mo) : 64u;
+            const bool odd = bo < be;
+            out[pos++] = ebase + 2u * (odd ? bo : be) + (odd ? 1u : 0u);
+            if (odd) mo &= mo - 1; else me &= me - 1;
+        }
+    } else {
+        // many hits: round by round (lane r's masks and start broadcast to the wave), coalesced stores
+        const uint64_t start = tb + (incl - pc) - (lane >= 32 ? t0 : 0u);
+        const uint32_t melo = (uint32_t)me, mehi = (uint32_t)(me >> 32), molo = (uint32_t)mo, mohi = (uint32_t)(mo >> 32);
+        const uint32_t stlo = (uint32_t)start, sthi = (uint32_t)(start >> 32);
+        for (uint32_t r = 0; r < WAVE; ++r) {
+            const uint64_t mer = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mehi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)melo, (int)r);
+            const uint64_t mor = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mohi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)molo, (int)r);
+            if ((mer | mor) == 0) continue;
+            const uint64_t st = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)sthi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)stlo, (int)r);
+            const uint32_t before = (uint32_t)__popcll(mer & lt) + (uint32_t)__popcll(mor & lt);
+            const uint64_t i = task * (2 * FILTER_TILE) + (uint64_t)r * (2 * WAVE) + 2 * lane;
+            const uint32_t e = (uint32_t)((mer >> lane) & 1ull);
+            if (e) out[st + before] = i;
+            if ((mor >> lane) & 1ull) out[st + before + e] = i + 1;
+        }
+    }
+}
+
 template <bool SELF>
 __global__ __launch_bounds__(256) void k_filter_write(uint64_t n, const uint64_t *masks, const uint64_t *tile_base,
                                                       uint64_t *out, unsigned long long *h_total)
@@ -114,60 +176,8 @@ __global__ __launch_bounds__(256) void k_filter_write(uint64_t n, const uint64_t
     const uint64_t ntasks = (ntiles + 1) / 2;
     const uint64_t stride = (uint64_t)gridDim.x * (256 / WAVE);
     const uint64_t lt = lanemask_lt();
-    for (uint64_t task = (uint64_t)blockIdx.x * (256 / WAVE) + (threadIdx.x >> 6); task < ntasks; task += stride) {
-        const uint64_t tile = 2 * task + (lane >> 5);
-        const uint64_t ebase = tile * FILTER_TILE + (uint64_t)(lane & 31u) * (2 * WAVE);    // first element of this lane's round
-        uint64_t me = 0, mo = 0;
-        if (ebase < n) {
-            const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(masks + (ebase >> 6));
-            me = x.x; mo = x.y;
-        }
-        uint64_t tb = 0;
-        if (SELF) {
-            uint64_t front = 0;                       // hits of the tiles in front of this pair
-            for (uint64_t t = lane; t < 2 * task; t += WAVE) front += tile_base[t];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) front += __shfl_xor(front, d, 64);
-            const uint64_t c0 = 2 * task < ntiles ? tile_base[2 * task] : 0, c1 = 2 * task + 1 < ntiles ? tile_base[2 * task + 1] : 0;
-            tb = front + (lane >= 32 ? c0 : 0);
-            if (task == ntasks - 1 && lane == 0) __hip_atomic_store(h_total, front + c0 + c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else
-            tb = tile < ntiles ? tile_base[tile] : 0;
-        const uint32_t pc = (uint32_t)__popcll(me) + (uint32_t)__popcll(mo);
-        if (__ballot(pc != 0) == 0) continue;
-        uint32_t incl = pc;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t y = __shfl_up(incl, d, 64);
-            if (lane >= (uint32_t)d) incl += y;
-        }
-        const uint32_t t0 = __shfl(incl, 31, 64), t2 = __shfl(incl, 63, 64);
-        if (t2 <= FILTER_SPARSE) {
-            uint64_t pos = tb + (incl - pc) - (lane >= 32 ? t0 : 0u);
-            while (me | mo) {                          // ascending: element 2b of the even word, 2b + 1 of the odd one
-                const uint32_t be = me ? (uint32_t)__builtin_ctzll(me) : 64u, bo = mo ? (uint32_t)__builtin_ctzll(mo) : 64u;
-                const bool odd = bo < be;
-                out[pos++] = ebase + 2u * (odd ? bo : be) + (odd ? 1u : 0u);
-                if (odd) mo &= mo - 1; else me &= me - 1;
-            }
-        } else {
-            // many hits: round by round (lane r's masks and start broadcast to the wave), coalesced stores
-            const uint64_t start = tb + (incl - pc) - (lane >= 32 ? t0 : 0u);
-            const uint32_t melo = (uint32_t)me, mehi = (uint32_t)(me >> 32), molo = (uint32_t)mo, mohi = (uint32_t)(mo >> 32);
-            const uint32_t stlo = (uint32_t)start, sthi = (uint32_t)(start >> 32);
-            for (uint32_t r = 0; r < WAVE; ++r) {
-                const uint64_t mer = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mehi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)melo, (int)r);
-                const uint64_t mor = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mohi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)molo, (int)r);
-                if ((mer | mor) == 0) continue;
-                const uint64_t st = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)sthi, (int)r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)stlo, (int)r);
-                const uint32_t before = (uint32_t)__popcll(mer & lt) + (uint32_t)__popcll(mor & lt);
-                const uint64_t i = task * (2 * FILTER_TILE) + (uint64_t)r * (2 * WAVE) + 2 * lane;
-                const uint32_t e = (uint32_t)((mer >> lane) & 1ull);
-                if (e) out[st + before] = i;
-                if ((mor >> lane) & 1ull) out[st + before + e] = i + 1;
-            }
-        }
-    }
+    for (uint64_t task = (uint64_t)blockIdx.x * (256 / WAVE) + (threadIdx.x >> 6); task < ntasks; task += stride)
+        filter_write_task<SELF>(n, ntiles, ntasks, task, masks, tile_base, out, h_total, lane, lt);
 }
 
 }  // namespace rhj

@@ -38,6 +38,8 @@
 //                          emit that walks the canonical positions.
 //   rhj_batch.hip.h        many small joins in the launches of one: the small path's kernel bodies over a third grid dimension.
 //   rhj_filter.hip.h       predicate -> ballot masks -> ascending index list.
+//   rhj_filter_batch.hip.h many conjunctive filters in the two launches of one: the same masks and write body, every
+//                          workgroup finding its filter in the chunk's array of tile starts.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -54,4 +56,5 @@
 #include "rhj_small.hip.h"
 #include "rhj_batch.hip.h"
 #include "rhj_filter.hip.h"
+#include "rhj_filter_batch.hip.h"
 #include "rhj_diag.hip.h"
