@@ -304,6 +304,38 @@ int rhj_batch_takes(int bits, uint64_t nR, uint64_t nS);
 int  rhj_join_keys_device(const uint64_t *d_keysR, uint64_t nR, const uint64_t *d_keysS, uint64_t nS, rhj_result_tuple *d_out,
                           uint64_t out_capacity, uint64_t *matches);
 
+/* Many independent joins in one call whose relations are KEY COLUMNS READ THROUGH ROW-ID VECTORS: tuple i of R is
+ * { d_colR[d_selR ? d_selR[i] : i], i }, and S likewise — what rhj_build_relation_device() (GetRelation, inter_res.c:199-204,
+ * :223-227) makes of a column and an intermediate result's row ids, without the relation being written.  The row-id vectors
+ * rhj_filter_batch_device() leaves are taken as they are.  Every join returns, bit for bit, what rhj_join_batch_device()
+ * returns on the materialised relations: the canonical order of the radix width in force (order mode "any":
+ * rhj_auto_radix_bits() of ITS sizes), the exact match count, nothing written at or beyond out_capacity; the pairs hold the
+ * positions i, not d_sel[i].  Columns and vectors may be shared between joins and between the two sides of one join; outputs
+ * must not overlap each other or any input; every pointer needs only 8-byte alignment; the caller guarantees that every
+ * d_sel[i] indexes its column.  The joins rhj_batch_takes() names run in the batched launches (path 6), whose partition
+ * kernels read the columns through the vectors (csrc/rhj_batch.hip.h: k_batch_hist_cols, k_batch_scatter_cols); every other
+ * join, and a taken join whose plan finds a bucket beyond the LDS index, is materialised into the library's own buffers and
+ * run by the single-join code inside the same call.  A join with an empty side launches nothing (rc 0, matches 0, path 0).
+ * The whole batch is validated before anything is launched: a NULL column with a non-zero size gives that join rc -3 and the
+ * call returns -3 with nothing run; n == 0 returns 0 without touching a device.  matches, rc, path, the return value and
+ * rhj_last_stats() afterwards are those of rhj_join_batch_device(). */
+typedef struct rhj_join_cols_desc {
+    const uint64_t *d_colR; const uint64_t *d_selR; uint64_t nR;   /* d_selR NULL: the column's first nR values */
+    const uint64_t *d_colS; const uint64_t *d_selS; uint64_t nS;
+    rhj_result_tuple *d_out; uint64_t out_capacity;   /* NULL / 0: count only */
+    uint64_t matches;   /* out */
+    int      rc;        /* out */
+    int      path;      /* out */
+} rhj_join_cols_desc;
+int rhj_join_cols_batch_device(rhj_join_cols_desc *joins, uint64_t n);
+/* One such join, with the contract of rhj_join_device().  Where the small path takes it (csrc/rhj_small.hip.h) the partition
+ * launches read the columns through the vectors; on every other route the relations are built first, as
+ * rhj_join_keys_device() builds them — to which two whole columns (both vectors NULL) on 9..15 radix bits are handed.  A NULL
+ * column with a non-zero size returns -3 with nothing run. */
+int rhj_join_cols_device(const uint64_t *d_colR, const uint64_t *d_selR, uint64_t nR,
+                         const uint64_t *d_colS, const uint64_t *d_selS, uint64_t nS,
+                         rhj_result_tuple *d_out, uint64_t out_capacity, uint64_t *matches);
+
 /* The stable radix partition alone (SerialReorderArray, preprocess.c:302-362):
  * d_out[n] partitioned tuples, h_hist[2^bits] counts, h_psum[2^bits] starts
  * (-1 for an empty bucket as preprocess.c:336-347 leaves it).  Host arrays may

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "RadixHashJoin", "Filter", "InsertResult", "InsertRowIdResult", "GetResultNum", "FindResultRowId",
     "FindResultTuples", "FreeResult", "PrintResult", "FreeRelation", "SchedulerInit", "SchedulerDestroy",
     "rhj_set_radix_bits", "rhj_get_radix_bits", "rhj_set_empty_mode", "rhj_set_node_pairs", "rhj_set_device", "rhj_get_device",
-    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device", "rhj_filter_batch_device", "rhj_filter_batch_takes",
+    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_cols_batch_device", "rhj_join_cols_device", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device", "rhj_filter_batch_device", "rhj_filter_batch_takes",
     "rhj_register_relation_map", "rhj_unregister_relation_map", "rhj_registered_columns", "rhj_pinned_ranges",
     "rhj_bucket_histogram_device", "rhj_select_bucket_range_device", "rhj_join_device_range", "rhj_join_device_slice", "rhj_pin_refusals",
     "rhj_release", "rhj_last_stats", "rhj_version",
@@ -80,6 +80,13 @@ class FilterPred(C.Structure):
 class JoinDesc(C.Structure):
     """rhj_join_desc (include/rhj.h): one join of rhj_join_batch_device"""
     _fields_ = [("d_R", C.c_void_p), ("nR", C.c_uint64), ("d_S", C.c_void_p), ("nS", C.c_uint64),
+                ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("matches", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
+
+
+class JoinColsDesc(C.Structure):
+    """rhj_join_cols_desc (include/rhj.h): one join of rhj_join_cols_batch_device"""
+    _fields_ = [("d_colR", C.c_void_p), ("d_selR", C.c_void_p), ("nR", C.c_uint64),
+                ("d_colS", C.c_void_p), ("d_selS", C.c_void_p), ("nS", C.c_uint64),
                 ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("matches", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
 
 
@@ -181,6 +188,10 @@ def load_library(path=None):
         L.rhj_join_batch_device.argtypes = [C.POINTER(JoinDesc), C.c_uint64]
         L.rhj_batch_takes.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
         L.rhj_batch_takes.restype = C.c_int
+    if hasattr(L, "rhj_join_cols_batch_device"):  # (A/B runs load earlier builds through this module too)
+        L.rhj_join_cols_batch_device.argtypes = [C.POINTER(JoinColsDesc), C.c_uint64]
+        L.rhj_join_cols_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+    L.rhj_build_relation_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     if hasattr(L, "rhj_join_keys_device"):
         L.rhj_join_keys_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
     L.rhj_partition_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -310,6 +321,80 @@ class RHJ:
             d = descs[i]
             res.append((None, d.matches) if count_only else (outs[i][:min(d.matches, d.out_capacity)], d.matches))
         return (res, [descs[i].path for i in everything]) if with_info else res
+
+    @staticmethod
+    def _cols_side(col, sel):
+        """(column pointer, vector pointer or None, tuples) of one side of a join on columns"""
+        return col.data_ptr(), (sel.data_ptr() if sel is not None else None), (col.shape[0] if sel is None else sel.shape[0])
+
+    def join_cols_batch_device(self, joins, capacities=None, count_only=False, with_info=False):
+        """Many independent joins on key columns read through row-id vectors (rhj_join_cols_batch_device): joins =
+        [(colR, selR, colS, selS), ...], int64 tensors [n]; a vector may be None (the whole column), and tuple i of a side is
+        (col[sel[i]], i).  Columns and vectors may be shared.  Returns what join_batch_device returns, by the same protocol:
+        count_only gives (None, matches); capacities[i] given: at most that many pairs of join i are written and returned;
+        capacities None: every join gets room for max(nR, nS) pairs, and the joins that needed more run again, with room for
+        their count, in a second batched call.  with_info: also the list of the joins' path ids (6: batched)."""
+        torch = self.torch
+        n = len(joins)
+        descs = (JoinColsDesc * max(n, 1))()
+        outs = [None] * n
+        sizes = [(self._cols_side(cR, sR)[2], self._cols_side(cS, sS)[2]) for cR, sR, cS, sS in joins]
+
+        def call(which, caps):
+            arr = (JoinColsDesc * max(len(which), 1))()
+            for k, i in enumerate(which):
+                cR, sR, cS, sS = joins[i]
+                d = arr[k]
+                d.d_colR, d.d_selR, d.nR = self._cols_side(cR, sR)
+                d.d_colS, d.d_selS, d.nS = self._cols_side(cS, sS)
+                if caps is not None:
+                    outs[i] = torch.empty((max(int(caps[k]), 1), 2), dtype=torch.int64, device=self.dev)
+                    d.d_out, d.out_capacity = outs[i].data_ptr(), int(caps[k])
+            rc = self.lib.rhj_join_cols_batch_device(arr, len(which))
+            if rc < 0:
+                raise RuntimeError("rhj_join_cols_batch_device failed (%d)" % rc)
+            for k, i in enumerate(which):
+                descs[i] = arr[k]
+            return rc
+
+        everything = list(range(n))
+        if count_only:
+            call(everything, None)
+        elif capacities is not None:
+            call(everything, [int(c) for c in capacities])
+        else:
+            call(everything, [max(nR, nS) for nR, nS in sizes])
+            short = [i for i in everything if descs[i].rc == 1]
+            if short:                               # fan-out above the guess: the counts are known now
+                call(short, [descs[i].matches for i in short])
+        res = []
+        for i in everything:
+            d = descs[i]
+            res.append((None, d.matches) if count_only else (outs[i][:min(d.matches, d.out_capacity)], d.matches))
+        return (res, [descs[i].path for i in everything]) if with_info else res
+
+    def join_cols_device(self, colR, selR, colS, selS, capacity=None, count_only=False):
+        """One join on key columns read through row-id vectors (rhj_join_cols_device); arguments as one entry of
+        join_cols_batch_device, result and capacity conventions as join_device."""
+        torch = self.torch
+        pR, vR, nR = self._cols_side(colR, selR)
+        pS, vS, nS = self._cols_side(colS, selS)
+        m = C.c_uint64(0)
+
+        def call(out_ptr, cap):
+            rc = self.lib.rhj_join_cols_device(pR, vR, nR, pS, vS, nS, out_ptr, cap, C.byref(m))
+            if rc < 0:
+                raise RuntimeError("rhj_join_cols_device failed (%d)" % rc)
+
+        if count_only:
+            call(None, 0)
+            return None, m.value
+        if capacity is None:
+            call(None, 0)
+            capacity = m.value
+        out = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.dev)
+        call(out.data_ptr(), capacity)
+        return out[:min(m.value, capacity)], m.value
 
     def partition_device(self, d_in, bits=None):
         torch = self.torch

@@ -7,6 +7,8 @@
 // and ONE fused-join launch per kernel variant, and waits for the stream once:
 //   k_batch_hist     grid (8, 2, joins with a relation of more than SM_SELF_TILES tiles)      small_hist_body
 //   k_batch_scatter  grid (8 + 1, 2, N): a join's tiles and its plan workgroup                 small_scatter_body
+//                    (k_batch_hist_cols, k_batch_scatter_cols: the same bodies reading {col[sel ? sel[i] : i], i} — ColSrc,
+//                    rhj_small.hip.h — for rhj_join_cols_batch_device; everything behind the scatter is shared)
 //   k_batch_fused    grid (BJ_WGS, joins of the variant): row j's workgroups share join j's     fj_join
 //                    ticket, and the last of them out leaves the join's summary and walk count
 //                    in slot j of a pinned host array
@@ -37,19 +39,33 @@ struct BatchJoin {
     uint64_t  n_zero;
     int       bits;
     int       self_hist;         // ... cleared by the scatter launch (1: no histogram launch covers this join) or by the histogram launch
+    ColSrc    c0, c1;            // rhj_join_cols_batch_device: where R and S are read (the _cols kernels; r0.in / r1.in are null then)
 };
 
 __global__ __launch_bounds__(SM_BLOCK) void k_batch_hist(const BatchJoin *__restrict__ joins, const uint32_t *__restrict__ list)
 {
     const BatchJoin &d = joins[list[blockIdx.z]];
-    small_hist_body(d.r0, d.r1, d.bits, d.zero_words, d.n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+    small_hist_body<false>(d.r0, d.r1, d.c0, d.c1, d.bits, d.zero_words, d.n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_batch_hist_cols(const BatchJoin *__restrict__ joins, const uint32_t *__restrict__ list)
+{
+    const BatchJoin &d = joins[list[blockIdx.z]];
+    small_hist_body<true>(d.r0, d.r1, d.c0, d.c1, d.bits, d.zero_words, d.n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 __global__ __launch_bounds__(SM_BLOCK) void k_batch_scatter(const BatchJoin *__restrict__ joins)
 {
     const BatchJoin &d = joins[blockIdx.z];
-    small_scatter_body(d.r0, d.r1, d.bits, d.hist, d.psum, d.plan, d.self_hist, d.zero_words, d.n_zero, blockIdx.x, blockIdx.y, gridDim.x,
-                       gridDim.y);
+    small_scatter_body<false>(d.r0, d.r1, d.c0, d.c1, d.bits, d.hist, d.psum, d.plan, d.self_hist, d.zero_words, d.n_zero, blockIdx.x,
+                              blockIdx.y, gridDim.x, gridDim.y);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_batch_scatter_cols(const BatchJoin *__restrict__ joins)
+{
+    const BatchJoin &d = joins[blockIdx.z];
+    small_scatter_body<true>(d.r0, d.r1, d.c0, d.c1, d.bits, d.hist, d.psum, d.plan, d.self_hist, d.zero_words, d.n_zero, blockIdx.x,
+                             blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // 16-byte tuples throughout, like every join of the small path (PlanSummary::wide_row_ids is 1 there)

@@ -10,6 +10,7 @@
 #include <mutex>
 #include <thread>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #include <stdio.h>
@@ -248,6 +249,8 @@ int ctx_init()
     }
     HIP_TRY(hipFuncSetAttribute((const void *)k_small_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_batch_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_small_scatter_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_batch_scatter_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes(PT_MAX_BITS)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_batch_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - FJ_LDS_EXTRA)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_batch_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - FJ_LDS_EXTRA)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_bucket_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4u << MAX_BITS)));
@@ -534,6 +537,8 @@ struct JoinReq {
     uint32_t           range_lo = 0, range_span = 0;   // rhj_join_device_range: the buckets this call joins (span 0: all of them)
     uint64_t           slice_skip = 0, slice_end = 0;  // rhj_join_device_slice: the first bucket's probe tuples from slice_skip on, the last bucket's before slice_end (0: all)
     int                cols_input = 0;                 // R and S are key columns (rhj_join_keys_device): pass 1 of the two-pass partition reads 8 bytes a tuple
+    bool               via_sel = false;                // R and S are not there yet (rhj_join_cols_device): tuple i is {col[sel ? sel[i] : i], i} of srcR / srcS, which the
+    ColSrc             srcR = {}, srcS = {};           // small path reads itself; every other path materialises them first (materialise)
 
     bool count_only() const { return !use_ctx_out && out == nullptr; }
 };
@@ -672,6 +677,20 @@ static int fused_epilogue(const JoinReq &q, const PlanSummary &plan, uint64_t M,
     return (!q.use_ctx_out && out && M > cap) ? 1 : 0;
 }
 
+// The relations of a join given by columns and row-id vectors, built in inR / inS as GetRelation builds them
+// (rhj_build_relation_device): from here on the join is one on rhj_tuple arrays.
+static int materialise(JoinReq &q)
+{
+    if (!q.via_sel) return 0;
+    if (ctx_init() || ensure(g.inR, (q.nR ? q.nR : 1) * sizeof(rhj_tuple)) || ensure(g.inS, (q.nS ? q.nS : 1) * sizeof(rhj_tuple))) return -1;
+    if (rhj_build_relation_device(q.srcR.col, q.srcR.sel, q.nR, (rhj_tuple *)g.inR.p) ||
+        rhj_build_relation_device(q.srcS.col, q.srcS.sel, q.nS, (rhj_tuple *)g.inS.p))
+        return -1;
+    q.R = (const rhj_tuple *)g.inR.p; q.S = (const rhj_tuple *)g.inS.p;
+    q.via_sel = false;
+    return 0;
+}
+
 // What the small, fused and tiled paths of one join share (join_setup): decisions on its sizes, partition state, kernel arguments
 struct JoinSetup {
     int       bits;
@@ -774,11 +793,20 @@ static int join_small(const JoinReq &q, JoinSetup &s)
         s.ja.out = out; s.ja.out_capacity = out ? cap : 0;
         fa.j = s.ja;
         RHJ_STAGE(ST_HIST);
-        if (!self_hist)
-            RHJ_LAUNCH(k_small_hist, dim3(max_tiles, 2), dim3(SM_BLOCK), 0, g.stream, a0, a1, bits, (uint64_t *)g.status.p, status_words);
+        if (!self_hist) {
+            if (q.via_sel)
+                RHJ_LAUNCH(k_small_hist_cols, dim3(max_tiles, 2), dim3(SM_BLOCK), 0, g.stream, a0, a1, q.srcR, q.srcS, bits,
+                           (uint64_t *)g.status.p, status_words);
+            else
+                RHJ_LAUNCH(k_small_hist, dim3(max_tiles, 2), dim3(SM_BLOCK), 0, g.stream, a0, a1, bits, (uint64_t *)g.status.p, status_words);
+        }
         RHJ_STAGE(ST_SCATTER);
-        RHJ_LAUNCH(k_small_scatter, dim3(max_tiles + 1, 2), dim3(SM_BLOCK), small_lds_bytes(bits), g.stream, a0, a1, bits, s.ps.hist,
-                   s.ps.psum, s.pa, self_hist, (uint64_t *)g.status.p, status_words);
+        if (q.via_sel)
+            RHJ_LAUNCH(k_small_scatter_cols, dim3(max_tiles + 1, 2), dim3(SM_BLOCK), small_lds_bytes(bits), g.stream, a0, a1, q.srcR, q.srcS,
+                       bits, s.ps.hist, s.ps.psum, s.pa, self_hist, (uint64_t *)g.status.p, status_words);
+        else
+            RHJ_LAUNCH(k_small_scatter, dim3(max_tiles + 1, 2), dim3(SM_BLOCK), small_lds_bytes(bits), g.stream, a0, a1, bits, s.ps.hist,
+                       s.ps.psum, s.pa, self_hist, (uint64_t *)g.status.p, status_words);
         RHJ_STAGE(ST_PROBE);
         if (resident(s.nmin, s.bins))
             RHJ_LAUNCH((k_join_fused<true, false>), dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);
@@ -1271,12 +1299,13 @@ static int auto_radix_bits(uint64_t nR, uint64_t nS)
 // The device-side join.  A split path goes first where it applies (r <= 8 the low-radix path, 9..13 the sub-bucket path) and
 // hands back 2 when it refuses.  Then the small path, or the partition and plan followed by the fused path; the tiled path
 // where either hands over, and behind the plan when the fused path is not wanted.  A narrow partition that met wide row ids
-// makes the whole join run again wide.
+// makes the whole join run again wide.  Relations still given by columns and row-id vectors (q.via_sel) are read as they
+// are by the small path alone: every other route materialises them first.
 static int join_device(JoinReq q)
 {
     if (g.order_any && q.nR && q.nS) q.bits = auto_radix_bits(q.nR, q.nS);    // RHJ_ORDER=any: the library picks the radix
     if (const int kb = split_bits(q)) {
-        if (begin_join(q)) return -1;
+        if (materialise(q) || begin_join(q)) return -1;
         const int rc = q.bits <= PT_MAX_BITS ? join_lowradix(q, kb) : join_subbucket(q, kb);
         if (rc != 2) return rc;
     }
@@ -1290,6 +1319,10 @@ static int join_device(JoinReq q)
         }
         JoinSetup s;
         if (join_setup(q, attempt > 0 || g.wide_row_ids, s)) return -1;
+        if (q.via_sel && !s.small) {                                  // only the small path reads columns through row-id vectors
+            if (materialise(q)) return -1;
+            s.ps.r[0].in = q.R; s.ps.r[1].in = q.S;
+        }
         int rc = TILED_PLANNED;
         if (s.small) rc = join_small(q, s);
         else if (partition_plan(s)) return -1;
@@ -1384,9 +1417,19 @@ struct BatchItem {
     BatchPlace L;
 };
 
+// What the batch code reads of a join's descriptor.  Both entry points share it (templates over the descriptor type):
+// rhj_join_desc names two rhj_tuple arrays, rhj_join_cols_desc two columns with optional row-id vectors (ColSrc).
+static inline const rhj_tuple *batch_in(const rhj_join_desc &q, int side) { return side ? q.d_S : q.d_R; }
+static inline const rhj_tuple *batch_in(const rhj_join_cols_desc &, int) { return nullptr; }
+static inline ColSrc batch_src(const rhj_join_desc &, int) { return ColSrc{nullptr, nullptr}; }
+static inline ColSrc batch_src(const rhj_join_cols_desc &q, int side) { return side ? ColSrc{q.d_colS, q.d_selS} : ColSrc{q.d_colR, q.d_selR}; }
+static inline bool batch_valid(const rhj_join_desc &) { return true; }
+static inline bool batch_valid(const rhj_join_cols_desc &q) { return (q.nR == 0 || q.d_colR) && (q.nS == 0 || q.d_colS); }
+template <class D> constexpr bool batch_cols = std::is_same<D, rhj_join_cols_desc>::value;
+
 // One chunk: items[lo, hi).  Joins whose plan refused the fused path are appended to `alone`.
-static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items, size_t lo, size_t hi, std::vector<uint64_t> &alone,
-                       uint64_t &units)
+template <class D>
+static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo, size_t hi, std::vector<uint64_t> &alone, uint64_t &units)
 {
     const size_t n = hi - lo;
     if (batch_arena(g.batch_arena, items[hi - 1].L.end)) return -1;
@@ -1404,13 +1447,14 @@ static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items
     int max_bits = 1;
     for (size_t k = 0; k < n; ++k) {
         const BatchItem &it = items[lo + k];
-        const rhj_join_desc &q = joins[it.idx];
+        const D &q = joins[it.idx];
         const BatchPlace &L = it.L;
         const uint32_t bins = 1u << it.bits;
         BatchJoin d;
         memset((void *)&d, 0, sizeof(d));
-        d.r0 = RelArgs{q.d_R, (rhj_tuple *)(A + L.partR), (uint32_t *)(A + L.cntR), q.nR, sm_tiles(q.nR), 0, nullptr, nullptr};
-        d.r1 = RelArgs{q.d_S, (rhj_tuple *)(A + L.partS), (uint32_t *)(A + L.cntS), q.nS, sm_tiles(q.nS), 0, nullptr, nullptr};
+        d.r0 = RelArgs{batch_in(q, 0), (rhj_tuple *)(A + L.partR), (uint32_t *)(A + L.cntR), q.nR, sm_tiles(q.nR), 0, nullptr, nullptr};
+        d.r1 = RelArgs{batch_in(q, 1), (rhj_tuple *)(A + L.partS), (uint32_t *)(A + L.cntS), q.nS, sm_tiles(q.nS), 0, nullptr, nullptr};
+        d.c0 = batch_src(q, 0); d.c1 = batch_src(q, 1);
         uint64_t *hist = (uint64_t *)(A + L.hp), *psum = hist + 2 * bins;
         d.hist = hist; d.psum = psum;
         PlanArgs pa;
@@ -1443,15 +1487,20 @@ static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
     }
     HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
-    if (n_hist) RHJ_LAUNCH(k_batch_hist, dim3(BJ_MAX_TILES, 2, n_hist), dim3(SM_BLOCK), 0, g.stream, dd, dl);
-    RHJ_LAUNCH(k_batch_scatter, dim3(BJ_MAX_TILES + 1, 2, (unsigned)n), dim3(SM_BLOCK), small_lds_bytes(max_bits), g.stream, dd);
+    if constexpr (batch_cols<D>) {
+        if (n_hist) RHJ_LAUNCH(k_batch_hist_cols, dim3(BJ_MAX_TILES, 2, n_hist), dim3(SM_BLOCK), 0, g.stream, dd, dl);
+        RHJ_LAUNCH(k_batch_scatter_cols, dim3(BJ_MAX_TILES + 1, 2, (unsigned)n), dim3(SM_BLOCK), small_lds_bytes(max_bits), g.stream, dd);
+    } else {
+        if (n_hist) RHJ_LAUNCH(k_batch_hist, dim3(BJ_MAX_TILES, 2, n_hist), dim3(SM_BLOCK), 0, g.stream, dd, dl);
+        RHJ_LAUNCH(k_batch_scatter, dim3(BJ_MAX_TILES + 1, 2, (unsigned)n), dim3(SM_BLOCK), small_lds_bytes(max_bits), g.stream, dd);
+    }
     if (n_res) RHJ_LAUNCH((k_batch_fused<true>), dim3(BJ_WGS, n_res), dim3(FJ_BLOCK), FUSED_LDS, g.stream, dd, dl + n, FUSED_LDS);
     if (n_gat) RHJ_LAUNCH((k_batch_fused<false>), dim3(BJ_WGS, n_gat), dim3(FJ_BLOCK), FUSED_LDS, g.stream, dd, dl + 2 * n, FUSED_LDS);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
     bool walked = false;
     for (size_t k = 0; k < n; ++k) {
-        rhj_join_desc &q = joins[items[lo + k].idx];
+        D &q = joins[items[lo + k].idx];
         PlanSummary plan;
         memcpy(&plan, slots + k * BATCH_SLOT_WORDS, sizeof(plan));    // written by the join's last workgroup out (system-scope stores)
         const uint64_t walk_units = slots[k * BATCH_SLOT_WORDS + sizeof(PlanSummary) / 8];
@@ -1474,10 +1523,18 @@ static int batch_chunk(rhj_join_desc *joins, const std::vector<BatchItem> &items
     return 0;
 }
 
-static int join_batch(rhj_join_desc *joins, uint64_t n)
+template <class D>
+static int join_batch(D *joins, uint64_t n)
 {
     if (n == 0) return 0;
     if (!joins) return -1;
+    bool invalid = false;                                 // the whole batch is validated before anything is launched
+    for (uint64_t i = 0; i < n; ++i) {
+        D &q = joins[i];
+        q.matches = 0; q.rc = 0; q.path = 0;
+        if (!batch_valid(q)) { q.rc = -3; invalid = true; }
+    }
+    if (invalid) return -3;
     if (ctx_init()) return -1;
     const bool timed = g.timing >= 1;
     if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
@@ -1485,8 +1542,7 @@ static int join_batch(rhj_join_desc *joins, uint64_t n)
     std::vector<uint64_t> alone;
     uint64_t sum_r = 0, sum_s = 0, sum_m = 0, units = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        rhj_join_desc &q = joins[i];
-        q.matches = 0; q.rc = 0; q.path = 0;
+        const D &q = joins[i];
         sum_r += q.nR; sum_s += q.nS;
         if (q.nR == 0 || q.nS == 0) continue;                         // rhjoin.c:15-16: nothing to launch
         const int bits = g.order_any ? auto_radix_bits(q.nR, q.nS) : g.bits;
@@ -1508,11 +1564,15 @@ static int join_batch(rhj_join_desc *joins, uint64_t n)
         if (batch_chunk(joins, items, lo, hi, alone, units)) return -1;
         lo = hi;
     }
-    // the joins that run alone, through the single-join code (which keeps its own stats: summed up below)
+    // the joins that run alone, through the single-join code (which keeps its own stats: summed up below); relations given by
+    // columns are materialised first
     for (const uint64_t i : alone) {
-        rhj_join_desc &q = joins[i];
+        D &q = joins[i];
         uint64_t m = 0;
-        const int rc = join_device({q.d_R, q.nR, q.d_S, q.nS, q.d_out, q.d_out ? q.out_capacity : 0, false, nullptr, &m, g.bits});
+        JoinReq req = {batch_in(q, 0), q.nR, batch_in(q, 1), q.nS, q.d_out, q.d_out ? q.out_capacity : 0, false, nullptr, &m, g.bits};
+        req.via_sel = batch_cols<D>; req.srcR = batch_src(q, 0); req.srcS = batch_src(q, 1);
+        if (materialise(req)) return -1;
+        const int rc = join_device(req);
         // (counting only, nothing was short: the tiled path says 1 whenever M passes the capacity, the small and fused paths
         // only when there is a buffer — a batch says the latter for every join)
         q.matches = m; q.rc = rc == 1 && !q.d_out ? 0 : rc; q.path = g.stats.reserved & 0xff;
@@ -2001,11 +2061,24 @@ int rhj_join_batch_device(rhj_join_desc *joins, uint64_t n)
 }
 int rhj_batch_takes(int bits, uint64_t nR, uint64_t nS) { return batch_takes(bits, nR, nS); }
 
+/* The same for joins whose relations are key columns read through optional row-id vectors (include/rhj.h): the batched
+ * launches read {col[sel ? sel[i] : i], i} themselves (k_batch_hist_cols, k_batch_scatter_cols), no relation is materialised */
+int rhj_join_cols_batch_device(rhj_join_cols_desc *joins, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return join_batch(joins, n);
+}
+
 /* The join of two relations given as KEY COLUMNS: tuple i of a relation is {keys[i], i} — what GetRelation makes of a base
  * relation (inter_res.c:199-204, :223-227: row_id = i) — without materialising the 16-byte tuples: on the two-pass partition
  * (9..15 radix bits) pass 1 reads the columns themselves, 8 bytes a tuple instead of 16 (the north_star's "coalesced uint64
  * column loads"); on every other path the tuples are built first (one streaming kernel) and the ordinary join runs.  Same
  * pairs, same order as rhj_join_device on the materialised relations. */
+static int keys_two_pass(const JoinReq &q)
+{
+    return !g.order_any && q.bits > PT_MAX_BITS && !split_bits(q) && !g.wide_row_ids && !g.no_fused && !g.force_hbm && q.nR && q.nS;
+}
+
 int rhj_join_keys_device(const uint64_t *d_keysR, uint64_t nR, const uint64_t *d_keysS, uint64_t nS, rhj_result_tuple *d_out,
                          uint64_t out_capacity, uint64_t *matches)
 {
@@ -2014,11 +2087,37 @@ int rhj_join_keys_device(const uint64_t *d_keysR, uint64_t nR, const uint64_t *d
     if (matches) *matches = 0;
     if (nR >= (1ull << 32) || nS >= (1ull << 32)) return -2;
     JoinReq q = {(const rhj_tuple *)d_keysR, nR, (const rhj_tuple *)d_keysS, nS, d_out, out_capacity, false, nullptr, &m, g.bits};
-    q.cols_input = !g.order_any && q.bits > PT_MAX_BITS && !split_bits(q) && !g.wide_row_ids && !g.no_fused && !g.force_hbm && nR && nS;
+    q.cols_input = keys_two_pass(q);
     if (!q.cols_input) {
         if (ctx_init() || ensure(g.inR, (nR ? nR : 1) * sizeof(rhj_tuple)) || ensure(g.inS, (nS ? nS : 1) * sizeof(rhj_tuple))) return -1;
         if (rhj_build_relation_device(d_keysR, nullptr, nR, (rhj_tuple *)g.inR.p) || rhj_build_relation_device(d_keysS, nullptr, nS, (rhj_tuple *)g.inS.p)) return -1;
         q.R = (const rhj_tuple *)g.inR.p; q.S = (const rhj_tuple *)g.inS.p;
+    }
+    const int rc = join_device(q);
+    if (matches) *matches = m;
+    return rc;
+}
+
+/* One join on columns read through optional row-id vectors (include/rhj.h): tuple i of a relation is {col[sel ? sel[i] : i], i}.
+ * Where the small path takes the join its partition launches read exactly that (k_small_hist_cols, k_small_scatter_cols);
+ * on every other route the relations are materialised first (join_device), except that two whole columns on the two-pass
+ * partition are read as rhj_join_keys_device reads them.  Same pairs, same order as rhj_join_device() on the relations
+ * rhj_build_relation_device() makes. */
+int rhj_join_cols_device(const uint64_t *d_colR, const uint64_t *d_selR, uint64_t nR, const uint64_t *d_colS, const uint64_t *d_selS,
+                         uint64_t nS, rhj_result_tuple *d_out, uint64_t out_capacity, uint64_t *matches)
+{
+    RhjApiLock api_lock;
+    uint64_t m = 0;
+    if (matches) *matches = 0;
+    if ((nR && !d_colR) || (nS && !d_colS)) return -3;
+    if (nR >= (1ull << 32) || nS >= (1ull << 32)) return -2;
+    JoinReq q = {nullptr, nR, nullptr, nS, d_out, out_capacity, false, nullptr, &m, g.bits};
+    if (!d_selR && !d_selS && keys_two_pass(q)) {
+        q.R = (const rhj_tuple *)d_colR; q.S = (const rhj_tuple *)d_colS;
+        q.cols_input = 1;
+    } else {
+        q.via_sel = true;
+        q.srcR = ColSrc{d_colR, d_selR}; q.srcS = ColSrc{d_colS, d_selS};
     }
     const int rc = join_device(q);
     if (matches) *matches = m;

@@ -14,6 +14,12 @@
 // joins of the contest's workload) skip k_small_hist: the scatter workgroups count the digits of all the relation's
 // tiles themselves (small_selfhist) and clear the join kernel's words.
 //
+// The relation is read at three places only — small_hist_body, small_selfhist and the tile load at the top of
+// small_scatter_body; behind the scatter everything is a partitioned 16-byte tuple array.  The bodies take a compile-time
+// switch COLS: false reads rhj_tuple[n], true reads tuple i as {col[sel ? sel[i] : i], i} from a key column through an
+// optional row-id vector (ColSrc; k_small_hist_cols, k_small_scatter_cols and the batched k_batch_*_cols), so the output
+// of a filter joins without a relation being materialised in between.
+//
 // (A single persistent kernel with grid-wide barriers between these phases was built first and measured slower,
 // 0.30 ms against 0.19 ms: on MI355X a grid barrier costs 6 us bare and 20-50 us with the agent-scope release /
 // acquire fences that make one phase's stores visible to the other XCDs — tools/micro/gridbar.hip, profiles/README.md.)
@@ -46,11 +52,38 @@ __host__ __device__ constexpr size_t small_lds_bytes(int bits)
     return (size_t)SM_TILE * 16 + ((size_t)SM_WAVES + 3) * ((size_t)1 << bits) * 4;
 }
 
+// Where a relation comes from when COLS is set (rhj_join_cols_device, rhj_join_cols_batch_device).  sel == nullptr (the whole
+// column) is a workgroup-uniform branch.  Only 8-byte loads: col and sel need no more than 8-byte alignment.
+struct ColSrc {
+    const uint64_t *col;
+    const uint64_t *sel;
+};
+
+// the values of a thread's SM_V tuples at i[k] (ok[k]: inside the relation): every sel load first, then every column load —
+// two dependent rounds of loads, not 2 x SM_V
+__device__ __forceinline__ void cols_values(const ColSrc &c, const uint64_t (&i)[SM_V], const bool (&ok)[SM_V], uint64_t (&v)[SM_V])
+{
+    uint64_t at[SM_V];
+#pragma unroll
+    for (int k = 0; k < SM_V; ++k) at[k] = i[k];
+    if (c.sel) {
+#pragma unroll
+        for (int k = 0; k < SM_V; ++k)
+            if (ok[k]) at[k] = c.sel[i[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < SM_V; ++k) {
+        v[k] = 0;
+        if (ok[k]) v[k] = c.col[at[k]];
+    }
+}
+
 // The kernels' bodies are device functions that take the workgroup's coordinates (bx, by) in a grid of (gx, gy) as arguments: the
 // single-join kernels below hand in those of their own launch, the batched ones (rhj_batch.hip.h) those of one join's plane
 // of a three-dimensional grid.
-__device__ __forceinline__ void small_hist_body(const RelArgs &r0, const RelArgs &r1, int bits, uint64_t *zero_words, uint64_t n_zero,
-                                                uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
+template <bool COLS>
+__device__ __forceinline__ void small_hist_body(const RelArgs &r0, const RelArgs &r1, const ColSrc &c0, const ColSrc &c1, int bits,
+                                                uint64_t *zero_words, uint64_t n_zero, uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
 {
     __shared__ uint32_t tile_h[1u << PT_MAX_BITS];
     const uint32_t tid = threadIdx.x;
@@ -67,10 +100,21 @@ __device__ __forceinline__ void small_hist_body(const RelArgs &r0, const RelArgs
     __syncthreads();
     const uint64_t beg = (uint64_t)t * SM_TILE;
     const uint64_t end = min(beg + (uint64_t)SM_TILE, r.n);
+    if constexpr (COLS) {
+        uint64_t i[SM_V], v[SM_V];
+        bool ok[SM_V];
 #pragma unroll
-    for (int k = 0; k < SM_V; ++k) {
-        const uint64_t i = beg + (uint32_t)k * SM_BLOCK + tid;
-        if (i < end) atomicAdd(&tile_h[(uint32_t)r.in[i].value & mask], 1u);
+        for (int k = 0; k < SM_V; ++k) { i[k] = beg + (uint32_t)k * SM_BLOCK + tid; ok[k] = i[k] < end; }
+        cols_values(by ? c1 : c0, i, ok, v);
+#pragma unroll
+        for (int k = 0; k < SM_V; ++k)
+            if (ok[k]) atomicAdd(&tile_h[(uint32_t)v[k] & mask], 1u);
+    } else {
+#pragma unroll
+        for (int k = 0; k < SM_V; ++k) {
+            const uint64_t i = beg + (uint32_t)k * SM_BLOCK + tid;
+            if (i < end) atomicAdd(&tile_h[(uint32_t)r.in[i].value & mask], 1u);
+        }
     }
     __syncthreads();
     if (tid < bins) r.cnt[(size_t)t * bins + tid] = tile_h[tid];
@@ -79,7 +123,13 @@ __device__ __forceinline__ void small_hist_body(const RelArgs &r0, const RelArgs
 
 __global__ __launch_bounds__(SM_BLOCK) void k_small_hist(RelArgs r0, RelArgs r1, int bits, uint64_t *zero_words, uint64_t n_zero)
 {
-    small_hist_body(r0, r1, bits, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+    small_hist_body<false>(r0, r1, ColSrc{}, ColSrc{}, bits, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_small_hist_cols(RelArgs r0, RelArgs r1, ColSrc c0, ColSrc c1, int bits, uint64_t *zero_words,
+                                                              uint64_t n_zero)
+{
+    small_hist_body<true>(r0, r1, c0, c1, bits, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // Sums of a relation's digit columns: for digit d (threads 0..bins-1 get the result) the tuples of digit d in the
@@ -146,7 +196,9 @@ __device__ __forceinline__ void small_colsum(const RelArgs &r, uint32_t t, int b
 // tiles itself (16 K tuples, L2-resident after the first workgroup) — `all` — and of the tiles before `t` — `before`.
 // h[] = 2 x bins words of LDS.  (The 88 joins of the contest's `small` workload are mostly this size: 57 us -> 48 us each.)
 constexpr uint32_t SM_SELF_TILES = 2;
-__device__ __forceinline__ void small_selfhist(const RelArgs &r, uint32_t t, int bits, uint32_t *h, uint32_t &before, uint32_t &all)
+template <bool COLS>
+__device__ __forceinline__ void small_selfhist(const RelArgs &r, const ColSrc &c, uint32_t t, int bits, uint32_t *h, uint32_t &before,
+                                               uint32_t &all)
 {
     const uint32_t tid = threadIdx.x;
     const uint32_t bins = 1u << bits, mask = bins - 1u;
@@ -155,13 +207,28 @@ __device__ __forceinline__ void small_selfhist(const RelArgs &r, uint32_t t, int
     for (uint32_t tt = 0; tt < r.tiles; ++tt) {
         const uint64_t beg = (uint64_t)tt * SM_TILE;
         const uint64_t end = min(beg + (uint64_t)SM_TILE, r.n);
+        if constexpr (COLS) {
+            uint64_t i[SM_V], v[SM_V];
+            bool ok[SM_V];
 #pragma unroll
-        for (int k = 0; k < SM_V; ++k) {
-            const uint64_t i = beg + (uint32_t)k * SM_BLOCK + tid;
-            if (i < end) {
-                const uint32_t d = (uint32_t)r.in[i].value & mask;
-                atomicAdd(&h[d], 1u);
-                if (tt < t) atomicAdd(&h[bins + d], 1u);
+            for (int k = 0; k < SM_V; ++k) { i[k] = beg + (uint32_t)k * SM_BLOCK + tid; ok[k] = i[k] < end; }
+            cols_values(c, i, ok, v);
+#pragma unroll
+            for (int k = 0; k < SM_V; ++k)
+                if (ok[k]) {
+                    const uint32_t d = (uint32_t)v[k] & mask;
+                    atomicAdd(&h[d], 1u);
+                    if (tt < t) atomicAdd(&h[bins + d], 1u);
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < SM_V; ++k) {
+                const uint64_t i = beg + (uint32_t)k * SM_BLOCK + tid;
+                if (i < end) {
+                    const uint32_t d = (uint32_t)r.in[i].value & mask;
+                    atomicAdd(&h[d], 1u);
+                    if (tt < t) atomicAdd(&h[bins + d], 1u);
+                }
             }
         }
     }
@@ -174,9 +241,10 @@ __device__ __forceinline__ void small_selfhist(const RelArgs &r, uint32_t t, int
 // grid (max tiles + 1, 2): workgroup (x, rel) scatters tile x of relation rel; workgroup (max tiles, 0) is the plan's.
 // self_hist: no k_small_hist launch went before (both relations have at most SM_SELF_TILES tiles): the digit counts are
 // taken from the tuples, and this launch clears the join kernel's words.
-__device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelArgs &r1, int bits, uint64_t *hist, uint64_t *psum,
-                                                   const PlanArgs &plan, int self_hist, uint64_t *zero_words, uint64_t n_zero,
-                                                   uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
+template <bool COLS>
+__device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelArgs &r1, const ColSrc &c0, const ColSrc &c1, int bits,
+                                                   uint64_t *hist, uint64_t *psum, const PlanArgs &plan, int self_hist, uint64_t *zero_words,
+                                                   uint64_t n_zero, uint32_t bx, uint32_t by, uint32_t gx, uint32_t gy)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint64_t sm[SM_BLOCK / 64 + 1];
@@ -206,7 +274,7 @@ __device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelA
             for (int rel = 0; rel < 2; ++rel) {
                 const RelArgs &r = rel ? r1 : r0;
                 uint32_t before, all;
-                small_selfhist(r, 0u, bits, part, before, all);
+                small_selfhist<COLS>(r, rel ? c1 : c0, 0u, bits, part, before, all);
                 const uint64_t ex = block_excl_scan<SM_BLOCK>(tid < bins ? (uint64_t)all : 0ull, nullptr, sm);
                 if (tid < bins) {
                     hist[(size_t)rel * bins + tid] = all;
@@ -299,21 +367,37 @@ __device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelA
     const uint64_t lt = lanemask_lt();
     const uint64_t beg = (uint64_t)t * SM_TILE;
     const uint32_t count = (uint32_t)min((uint64_t)SM_TILE, r.n - beg);
-    const uint4 *in = reinterpret_cast<const uint4 *>(r.in) + beg;
+    const ColSrc &c = by ? c1 : c0;
     SM_FINE(0);
     uint4 tp[SM_V];                                     // the tile's loads fly while the columns are summed
     bool ok[SM_V];
+    if constexpr (COLS) {
+        // consecutive lanes read consecutive sel[i]; a filter's output ascends, so the column gathers are near-coalesced
+        uint64_t pos[SM_V], v[SM_V];
 #pragma unroll
-    for (int k = 0; k < SM_V; ++k) {
-        const uint32_t i = w * (WAVE * SM_V) + (uint32_t)k * WAVE + lane;             // tile order (wave, round, lane)
-        ok[k] = i < count;
-        tp[k] = make_uint4(0, 0, 0, 0);
-        if (ok[k]) tp[k] = in[i];
+        for (int k = 0; k < SM_V; ++k) {
+            const uint32_t i = w * (WAVE * SM_V) + (uint32_t)k * WAVE + lane;         // tile order (wave, round, lane)
+            ok[k] = i < count;
+            pos[k] = beg + i;                           // the tuple's row id: its position in the relation, not sel[i]
+        }
+        cols_values(c, pos, ok, v);
+#pragma unroll
+        for (int k = 0; k < SM_V; ++k)
+            tp[k] = ok[k] ? make_uint4((uint32_t)v[k], (uint32_t)(v[k] >> 32), (uint32_t)pos[k], (uint32_t)(pos[k] >> 32)) : make_uint4(0, 0, 0, 0);
+    } else {
+        const uint4 *in = reinterpret_cast<const uint4 *>(r.in) + beg;
+#pragma unroll
+        for (int k = 0; k < SM_V; ++k) {
+            const uint32_t i = w * (WAVE * SM_V) + (uint32_t)k * WAVE + lane;         // tile order (wave, round, lane)
+            ok[k] = i < count;
+            tp[k] = make_uint4(0, 0, 0, 0);
+            if (ok[k]) tp[k] = in[i];
+        }
     }
     {
         // where this tile's tuples of digit d go: bucket start + the digit's tuples in earlier tiles
         uint32_t before, all;
-        if (self_hist) small_selfhist(r, t, bits, part, before, all);
+        if (self_hist) small_selfhist<COLS>(r, c, t, bits, part, before, all);
         else           small_colsum(r, t, bits, part, before, all);
         const uint64_t ex = block_excl_scan<SM_BLOCK>(tid < bins ? (uint64_t)all : 0ull, nullptr, sm);
         if (tid < bins) gstart[tid] = (uint32_t)ex + before;
@@ -382,7 +466,16 @@ __device__ __forceinline__ void small_scatter_body(const RelArgs &r0, const RelA
 __global__ __launch_bounds__(SM_BLOCK) void k_small_scatter(RelArgs r0, RelArgs r1, int bits, uint64_t *hist, uint64_t *psum, PlanArgs plan,
                                                             int self_hist, uint64_t *zero_words, uint64_t n_zero)
 {
-    small_scatter_body(r0, r1, bits, hist, psum, plan, self_hist, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+    small_scatter_body<false>(r0, r1, ColSrc{}, ColSrc{}, bits, hist, psum, plan, self_hist, zero_words, n_zero, blockIdx.x, blockIdx.y,
+                              gridDim.x, gridDim.y);
+}
+
+__global__ __launch_bounds__(SM_BLOCK) void k_small_scatter_cols(RelArgs r0, RelArgs r1, ColSrc c0, ColSrc c1, int bits, uint64_t *hist,
+                                                                 uint64_t *psum, PlanArgs plan, int self_hist, uint64_t *zero_words,
+                                                                 uint64_t n_zero)
+{
+    small_scatter_body<true>(r0, r1, c0, c1, bits, hist, psum, plan, self_hist, zero_words, n_zero, blockIdx.x, blockIdx.y, gridDim.x,
+                             gridDim.y);
 }
 
 }  // namespace rhj
