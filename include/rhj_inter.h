@@ -125,6 +125,48 @@ int rhj_filter_eq2_device(const uint64_t *d_colA, const uint64_t *d_selA, const 
  * there (it indexes a calloc of 0 entries, relation_map.c:64-74). */
 int rhj_column_stats_device(const uint64_t *d_col, uint64_t n, uint64_t *l, uint64_t *u, double *d);
 
+/* Many row-id rebuilds and view sums in one call: what consumes a pair list (the two gathers of InsertJoinToInterResults, the
+ * sums of CalculateQueryResults) for a whole batch of queries, one kernel launch and one stream synchronisation per chunk of
+ * up to 4096 items and 2^24 tiles of 2048 rows, in call order.  One item applies one index list to up to
+ * RHJ_APPLY_MAX_TERMS terms.  For row i < n and term t:
+ *     p = d_idx ? d_idx[i * idx_stride + side_t] : i
+ *     q = d_src_t ? d_src_t[p] : p
+ *     if d_dst_t:  d_dst_t[i] = q
+ *     if d_col_t:  sum_t += d_col_t[q]          (u64, wrap-around)
+ * so an item is the rebuild through one or both sides of a pair list (idx_stride 2, side 0 / 1, d_src the old vector or NULL
+ * for the fresh relation), the rebuild through a filter's hit list (idx_stride 1), the plain view sum (d_idx NULL, d_src the
+ * row-id vector) or the view sum through the last join's pairs with no table written (d_dst NULL).
+ *
+ * d_dst[0..n) of every writing term holds the gathered ids and nothing at or beyond d_dst[n] is written; every sum is exact
+ * modulo 2^64.  Inputs may be shared between items and between terms; outputs must not overlap each other or any input of the
+ * call.  Every pointer needs 8-byte alignment and no more (pairs + 1 with stride 2 is a legal d_idx).  The caller guarantees
+ * that every p indexes its d_src and every q its d_col.  An item with n == 0 has rc 0, sums 0 and path 0 and launches nothing;
+ * a batch of 0 items returns 0 without touching a device.
+ *
+ * The whole batch is validated before anything is launched: idx_stride outside {1, 2}, nterms outside
+ * 1..RHJ_APPLY_MAX_TERMS, a side outside 0..idx_stride - 1, side != 0 with d_idx == NULL, a term with neither d_dst nor d_col,
+ * or n above 2^35 give that item rc -3; then nothing runs and the call returns -3.  Otherwise 0, or a negative value on a HIP
+ * error.  rhj_last_stats() afterwards: n_r the rows summed over the items, units the items launched, ms_total the whole call
+ * (timing level >= 1), reserved 8. */
+#define RHJ_APPLY_MAX_TERMS 8
+typedef struct rhj_apply_term {
+    const uint64_t *d_src;   /* NULL: q = p */
+    uint64_t       *d_dst;   /* NULL: nothing written for this term */
+    const uint64_t *d_col;   /* NULL: no sum */
+    uint64_t        sum;     /* out; 0 without d_col */
+    int             side;    /* word of an index row, 0 .. idx_stride - 1 */
+} rhj_apply_term;
+typedef struct rhj_apply_desc {
+    const uint64_t *d_idx;   /* NULL: p = i */
+    uint64_t        n;
+    int             idx_stride;          /* 1 or 2 */
+    int             nterms;              /* 1 .. RHJ_APPLY_MAX_TERMS */
+    rhj_apply_term  terms[RHJ_APPLY_MAX_TERMS];
+    int             rc;      /* out */
+    int             path;    /* out: 8 (0 for an item that launched nothing) */
+} rhj_apply_desc;
+int rhj_apply_batch_device(rhj_apply_desc *items, uint64_t n);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

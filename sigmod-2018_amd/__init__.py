@@ -38,7 +38,7 @@ INTER_SYMBOLS = [
     "CalculateQueryResults", "PrintNullResults", "AreActiveInInter", "JoinInterNode", "CartesianInterResults",
     "InsertSingleRowIdsToInterResult", "rhj_gather_tables_device", "rhj_build_relation_device", "rhj_sum_gather_device", "rhj_sum_views_device",
     "rhj_filter_eq2_device", "rhj_resident_relation", "rhj_resident_result", "rhj_resident_inter",
-    "InitRelationMap", "FreeRelationMap", "PrintRelationMap", "rhj_column_stats_device",
+    "InitRelationMap", "FreeRelationMap", "PrintRelationMap", "rhj_column_stats_device", "rhj_apply_batch_device",
 ]
 
 
@@ -104,6 +104,20 @@ class FilterDesc(C.Structure):
                 ("d_out", C.c_void_p), ("hits", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
 
 
+APPLY_MAX_TERMS = 8                      # RHJ_APPLY_MAX_TERMS
+
+
+class ApplyTerm(C.Structure):
+    """rhj_apply_term (include/rhj_inter.h): one term of a batched apply item"""
+    _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("d_col", C.c_void_p), ("sum", C.c_uint64), ("side", C.c_int)]
+
+
+class ApplyDesc(C.Structure):
+    """rhj_apply_desc (include/rhj_inter.h): one item of rhj_apply_batch_device"""
+    _fields_ = [("d_idx", C.c_void_p), ("n", C.c_uint64), ("idx_stride", C.c_int), ("nterms", C.c_int),
+                ("terms", ApplyTerm * APPLY_MAX_TERMS), ("rc", C.c_int), ("path", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ms_hist", "ms_scan", "ms_scatter", "ms_plan", "ms_build", "ms_count",
                                          "ms_offsets", "ms_probe", "ms_total", "ms_h2d", "ms_d2h")] + \
@@ -113,7 +127,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -200,6 +214,8 @@ def load_library(path=None):
         L.rhj_filter_batch_device.argtypes = [C.POINTER(FilterDesc), C.c_uint64]
         L.rhj_filter_batch_takes.argtypes = [C.c_uint64]
         L.rhj_filter_batch_takes.restype = C.c_int
+    if hasattr(L, "rhj_apply_batch_device"):      # (A/B runs load earlier builds through this module too)
+        L.rhj_apply_batch_device.argtypes = [C.POINTER(ApplyDesc), C.c_uint64]
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -449,6 +465,52 @@ class RHJ:
         if rc < 0:
             raise RuntimeError("rhj_filter_batch_device failed (%d)" % rc)
         res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def apply_batch_device(self, items, with_info=False):
+        """Many row-id rebuilds and view sums in one call (rhj_apply_batch_device, include/rhj_inter.h): items =
+        [(idx or None, stride, n, terms), ...] with idx an int64 tensor that holds an index list ([n] with stride 1, a pair list
+        [n, 2] or a view of one with stride 2) and terms = [(side, src or None, want_rows, col or None), ...] (1..8 of them).
+        Row i of a term is q = src[p] (p itself without src), p = idx[i * stride + side] (i itself without idx).  Returns per
+        item a list of (rows tensor or None, sum or None): the n gathered ids where want_rows, the wrap-around sum of col[q]
+        as a Python int below 2^64 where col is given.  The row tensors are views of one allocation.  with_info: also the
+        list of the items' path ids (8: the batched launch, 0: an empty item)."""
+        torch = self.torch
+        n = len(items)
+        arr = (ApplyDesc * max(n, 1))()
+        places, lists, at = [], [], 0
+        for d, (idx, stride, rows, terms) in zip(arr, items):
+            if not 1 <= len(terms) <= APPLY_MAX_TERMS:
+                raise ValueError("an item has 1..%d terms, not %d" % (APPLY_MAX_TERMS, len(terms)))
+            d.d_idx = idx.data_ptr() if idx is not None else None
+            d.n, d.idx_stride, d.nterms = int(rows), int(stride), len(terms)
+            if idx is not None and idx.numel() == 0 and int(rows):
+                raise ValueError("an empty index list for %d rows" % int(rows))
+            lists.append(idx is not None)
+            mine = []
+            for t, (side, src, want_rows, col) in zip(d.terms, terms):
+                t.side = int(side)
+                t.d_src = src.data_ptr() if src is not None else None
+                t.d_col = col.data_ptr() if col is not None else None
+                mine.append(at if want_rows else None)
+                if want_rows:
+                    at += (int(rows) + 1) // 2 * 2               # 16-byte aligned pieces
+            places.append(mine)
+        out = torch.empty(max(at, 1), dtype=torch.int64, device=self.dev)
+        for d, mine, listed in zip(arr, places, lists):
+            for t, a in zip(d.terms, mine):
+                if a is not None:
+                    t.d_dst = out.data_ptr() + 8 * a
+            if listed and not d.d_idx:                           # an empty tensor has no address: the list of a join without a
+                d.d_idx = out.data_ptr()                         # match is still a list (side 1 is legal), and none of it is read
+        rc = self.lib.rhj_apply_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_apply_batch_device failed (%d)" % rc)
+        res = []
+        for i in range(n):
+            d = arr[i]
+            res.append([(out[a:a + d.n] if a is not None else None, d.terms[k].sum if d.terms[k].d_col else None)
+                        for k, a in enumerate(places[i])])
         return (res, [arr[i].path for i in range(n)]) if with_info else res
 
     def pairs_to_numpy(self, t):

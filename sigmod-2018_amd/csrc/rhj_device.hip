@@ -1399,7 +1399,7 @@ static int batch_arena(Buf &b, size_t bytes)
     return 0;
 }
 
-// the pinned host block of a chunk (both batched entry points; every chunk ends in a stream synchronisation before the next
+// the pinned host block of a chunk (every batched entry point; every chunk ends in a stream synchronisation before the next
 // one writes the block again)
 static int batch_pinned(size_t bytes)
 {
@@ -1834,6 +1834,135 @@ static int filter_batch(rhj_filter_desc *filters, uint64_t n)
     memset(&st, 0, sizeof(st));
     st.n_r = rows; st.matches = hits; st.units = items.size();
     st.reserved = 7;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
+        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
+    return 0;
+}
+
+// ---- batched rebuilds and view sums (rhj_apply_batch.hip.h) ----------------------------------------------------------------
+// rhj_apply_batch_device: every item of at least one row runs in the launch of its chunk (path 8); there is no run-alone class.
+// A chunk holds at most APPLY_MAX_ITEMS items and APPLY_MAX_TILES tiles (both conditions, not measurements: the first bounds
+// the uploaded block, the second keeps a chunk's tile starts far inside 32 bits), and a batch beyond either is cut in call
+// order.  A chunk is one upload, one launch and one stream synchronisation; it shares the pinned block and g.batch_desc with
+// the join and filter batches, and ends in that synchronisation before the block is written again.
+constexpr size_t APPLY_MAX_ITEMS = 4096;
+constexpr uint64_t APPLY_MAX_TILES = 1ull << 24;
+constexpr uint64_t APPLY_MAX_ROWS = APPLY_MAX_TILES * APPLY_TILE;       // 2^35
+
+static bool apply_valid(const rhj_apply_desc &q)
+{
+    if ((q.idx_stride != 1 && q.idx_stride != 2) || q.nterms < 1 || q.nterms > RHJ_APPLY_MAX_TERMS || q.n > APPLY_MAX_ROWS) return false;
+    for (int t = 0; t < q.nterms; ++t) {
+        const rhj_apply_term &a = q.terms[t];
+        if (a.side < 0 || a.side >= q.idx_stride || (a.side != 0 && !q.d_idx) || (!a.d_dst && !a.d_col)) return false;
+    }
+    return true;
+}
+
+static bool apply_sums(const rhj_apply_desc &q)
+{
+    for (int t = 0; t < q.nterms; ++t) if (q.terms[t].d_col) return true;
+    return false;
+}
+
+// One chunk: items[which[lo, hi)], every one valid and of at least one row.
+static int apply_chunk(rhj_apply_desc *items, const std::vector<uint64_t> &which, size_t lo, size_t hi)
+{
+    const size_t ni = hi - lo;
+    size_t nsum = 0;
+    for (size_t k = lo; k < hi; ++k) nsum += apply_sums(items[which[k]]);
+    // pinned block: [ni sum slots][ni descriptors][ni + 1 tile starts][accumulator and ticket words of the summing items, zero];
+    // all but the slots are uploaded in one copy
+    constexpr size_t WORDS = RHJ_APPLY_MAX_TERMS + 1;     // an item's accumulators and its ticket
+    const size_t slots_bytes = ni * APPLY_SLOT_WORDS * 8, desc_bytes = ni * sizeof(ApplyDesc), start_bytes = ((ni + 1) * 4 + 7) & ~(size_t)7;
+    const size_t words_bytes = nsum * WORDS * 8, up_bytes = desc_bytes + start_bytes + words_bytes;
+    if (batch_pinned(slots_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
+    uint64_t *slots = (uint64_t *)g.batch_pin;
+    ApplyDesc *hd = (ApplyDesc *)((char *)g.batch_pin + slots_bytes);
+    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes);
+    const ApplyDesc *dd = (const ApplyDesc *)g.batch_desc.p;
+    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes);
+    unsigned long long *d_words = (unsigned long long *)((char *)g.batch_desc.p + desc_bytes + start_bytes);
+    memset(slots, 0, slots_bytes);                        // (a summing item whose slot is not flagged done left no sums: an error)
+    memset((char *)hd + desc_bytes + start_bytes, 0, words_bytes);
+    uint32_t tiles = 0;
+    size_t s = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const rhj_apply_desc &q = items[which[lo + k]];
+        ApplyDesc d;
+        memset((void *)&d, 0, sizeof(d));
+        d.idx = q.d_idx; d.n = q.n; d.stride = q.idx_stride; d.nterms = q.nterms;
+        d.tiles = (uint32_t)((q.n + APPLY_TILE - 1) / APPLY_TILE);
+        for (int t = 0; t < q.nterms; ++t) {
+            d.t[t].src = q.terms[t].d_src; d.t[t].dst = q.terms[t].d_dst; d.t[t].col = q.terms[t].d_col; d.t[t].side = q.terms[t].side;
+            d.sides |= 1u << q.terms[t].side;
+        }
+        if (apply_sums(q)) {
+            d.acc = d_words + s * WORDS;
+            d.ticket = (uint32_t *)(d.acc + RHJ_APPLY_MAX_TERMS);
+            d.h_slot = (unsigned long long *)slots + k * APPLY_SLOT_WORDS;
+            ++s;
+        }
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        tile_start[k] = tiles;
+        tiles += d.tiles;
+    }
+    tile_start[ni] = tiles;
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    RHJ_LAUNCH(k_apply_batch, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)ni);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < ni; ++k) {
+        rhj_apply_desc &q = items[which[lo + k]];
+        q.path = 8;
+        if (!apply_sums(q)) continue;
+        const volatile uint64_t *h = (const volatile uint64_t *)slots + k * APPLY_SLOT_WORDS;     // written by the item's last workgroup out (system scope)
+        if (h[RHJ_APPLY_MAX_TERMS] != 1) { fprintf(stderr, "rhj: batched apply item %zu left no sums\n", (size_t)which[lo + k]); return -1; }
+        for (int t = 0; t < q.nterms; ++t) if (q.terms[t].d_col) q.terms[t].sum = h[t];
+    }
+    return 0;
+}
+
+static int apply_batch(rhj_apply_desc *items, uint64_t n)
+{
+    if (n == 0) return 0;
+    if (!items) return -1;
+    bool invalid = false;                                 // the whole batch is validated before anything is launched
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_apply_desc &q = items[i];
+        q.rc = 0; q.path = 0;
+        if (!apply_valid(q)) { q.rc = -3; invalid = true; continue; }
+        for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0;
+    }
+    if (invalid) return -3;
+    if (ctx_init()) return -1;
+    const bool timed = g.timing >= 1;
+    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    std::vector<uint64_t> which;
+    uint64_t rows = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rows += items[i].n;
+        if (items[i].n) which.push_back(i);               // an empty item: nothing to launch
+    }
+    for (size_t lo = 0; lo < which.size();) {
+        size_t hi = lo;
+        uint64_t tiles = 0;
+        while (hi < which.size() && hi - lo < APPLY_MAX_ITEMS) {
+            const uint64_t t = (items[which[hi]].n + APPLY_TILE - 1) / APPLY_TILE;
+            if (tiles + t > APPLY_MAX_TILES) break;       // (one item never has more: apply_valid)
+            tiles += t;
+            ++hi;
+        }
+        if (apply_chunk(items, which, lo, hi)) return -1;
+        lo = hi;
+    }
+    rhj_stats &st = g.stats;
+    memset(&st, 0, sizeof(st));
+    st.n_r = rows; st.units = which.size();
+    st.reserved = 8;
     if (timed) {
         HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
         HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
@@ -2352,6 +2481,13 @@ int rhj_filter_batch_device(rhj_filter_desc *filters, uint64_t n)
     return filter_batch(filters, n);
 }
 int rhj_filter_batch_takes(uint64_t rows) { return filter_batch_takes(rows); }
+
+/* Many row-id rebuilds and view sums in one call (include/rhj_inter.h; apply_batch above) */
+int rhj_apply_batch_device(rhj_apply_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return apply_batch(items, n);
+}
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */
 
