@@ -167,6 +167,85 @@ typedef struct rhj_apply_desc {
 } rhj_apply_desc;
 int rhj_apply_batch_device(rhj_apply_desc *items, uint64_t n);
 
+/* Many two-column equalities in one call (csrc/rhj_eq2_batch.hip.h): what SelfJoin and the same-node branch of JoinInterNode
+ * (inter_res.c:234-263, :363-389) need for a whole batch of queries.  d_out[0..hits) gets the ascending i in [0, n) with
+ * colA[selA ? selA[i] : i] == colB[selB ? selB[i] : i]; nothing at or beyond d_out[hits] is written; hits is exact, also with
+ * d_out == NULL (count only).  A one-item batch returns bit for bit what rhj_filter_eq2_device returns.  Inputs may be shared
+ * between items and between the two sides of one item (the same vector on both sides is the SelfJoin form); outputs must not
+ * overlap; every pointer needs only 8-byte alignment (a side takes the 16-byte loads only when the vector it scans - its sel,
+ * or its column without one - starts on a 16-byte boundary).  The items rhj_filter_batch_takes(n) names (1..4 194 304 rows) run
+ * together in two launches (masks, index lists) and one stream synchronisation per chunk of at most 4096 items and 1 GiB of
+ * masks, in call order, whatever their number (path 9); a larger item is run alone inside the same call by the single call's
+ * kernels (path 0).  n == 0: rc 0, hits 0, path 0, nothing launched; a batch of 0 items returns 0 without touching a device.
+ * The whole batch is validated before anything is launched: a NULL column with n > 0 gives that item rc -3, nothing runs and
+ * the call returns -3.  Otherwise 0, <0 on a HIP error.  rhj_last_stats() afterwards: n_r the rows and matches the hits summed
+ * over the items, units the items that went through the batched launches, ms_total the whole call (timing level >= 1),
+ * reserved 9. */
+typedef struct rhj_eq2_desc {
+    const uint64_t *d_colA, *d_selA;   /* sel NULL: the column's rows 0..n) */
+    const uint64_t *d_colB, *d_selB;
+    uint64_t        n;
+    uint64_t       *d_out;             /* capacity n; NULL: count only */
+    uint64_t        hits;              /* out */
+    int             rc;                /* out */
+    int             path;              /* out: 9 the batched launches, 0 run alone or nothing launched */
+} rhj_eq2_desc;
+int rhj_filter_eq2_batch_device(rhj_eq2_desc *items, uint64_t n);
+
+/* A batch of queries run level by level through the four batches above: one rhj_filter_batch_device call, then per join level
+ * at most one rhj_filter_eq2_batch_device call, at most two rhj_join_cols_batch_device calls and one rhj_apply_batch_device
+ * call, with no single call in between.  The relations are device-resident column stores; nothing but the descriptors and the
+ * answers crosses the bus.
+ *
+ * Per query (the reference's executor, query.c:334-465, without its optimiser): the filters restrict their bindings; the join
+ * predicates are applied left to right, in the order given; the views are summed over the final rows modulo 2^64.  A predicate
+ * whose two bindings already sit in one intermediate node, or are the same binding, is a two-column equality over that node's
+ * rows (SelfJoin / JoinInterNode's same-node branch); every other predicate is a join of the two nodes on the two columns read
+ * through the bindings' row-id vectors, after which the two nodes are one.  rows is the number of rows of the final result;
+ * rows == 0 is the case the reference prints NULL for every view in (sums are 0 then).  Sums do not depend on the order of the
+ * rows, so the answers are the same at every radix width and order mode.
+ *
+ * All filters of one binding are ONE conjunctive rhj_filter_desc (at most RHJ_FILTER_MAX_TERMS of them); a query without a
+ * join predicate sums its views through its one binding's vector in the first apply call.  A query whose intermediate result
+ * becomes empty is finished there and adds no further item.  Joins get room for max(nR, nS) pairs; those that need more run
+ * once more, in one second call per level, with room for their counts.
+ *
+ * The whole batch is validated before a device is touched: nrels outside 1..RHJ_QUERY_MAX_RELS, nviews outside
+ * 1..RHJ_QUERY_MAX_VIEWS, a negative count, a binding, relation or column index out of range, a used column that is NULL in a
+ * relation with rows, an operator outside '<', '>', '=', more than RHJ_FILTER_MAX_TERMS filters on one binding, or bindings
+ * that are not all in one node after the last predicate (a cross product, CartesianInterResults: not executed here) give that
+ * query rc -3; then nothing runs, no sums or rows are written and the call returns -3.  n == 0 returns 0.  Otherwise 0, or a
+ * negative value on a HIP error.  The call holds the library lock throughout and keeps its intermediate vectors in workspace
+ * buffers that grow and stay (rhj_release() frees them).  rhj_last_stats() afterwards: n_r the queries, matches the final rows
+ * summed over them, ms_total the whole call (timing level >= 1), reserved 10. */
+typedef struct rhj_device_relation {          /* a device-resident column store */
+    uint64_t num_tuples, num_columns;
+    const uint64_t *const *d_columns;         /* host array of num_columns device pointers */
+} rhj_device_relation;
+typedef struct rhj_query_filter { int rel, col; char op; uint64_t value; } rhj_query_filter;  /* rel = binding; value already converted, as rhj_filter_device */
+typedef struct rhj_query_join   { int relA, colA, relB, colB; } rhj_query_join;               /* rel = binding */
+typedef struct rhj_query_view   { int rel, col; } rhj_query_view;                             /* rel = binding */
+#define RHJ_QUERY_MAX_RELS  8
+#define RHJ_QUERY_MAX_VIEWS 8
+typedef struct rhj_query_desc {
+    int nrels;    const int *rels;                   /* binding -> index into the relation array; a relation may be bound twice */
+    int nfilters; const rhj_query_filter *filters;
+    int njoins;   const rhj_query_join *joins;       /* executed left to right, in this order: the caller's optimiser chose it */
+    int nviews;   const rhj_query_view *views;
+    uint64_t sums[RHJ_QUERY_MAX_VIEWS];              /* out: wrap-around u64 sums */
+    uint64_t rows;                                   /* out: rows of the final result; 0: the reference prints NULL for every view */
+    int rc;                                          /* out */
+} rhj_query_desc;
+int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n);
+/* The validation of one query, a pure function that needs no device: njoins, or -3.  kinds, when given, receives per step
+ * 0 for a join and 1 for a two-column equality (njoins entries; what was written before a -3 is not meaningful).  rels may
+ * be NULL: then relation and column indices are only checked against nrel and for sign. */
+int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds);
+/* What the last rhj_query_batch_device call of this process issued: the join levels (the largest njoins) and the calls of
+ * each inner batch (join_calls the first calls of the levels, join_reruns the second ones). */
+typedef struct rhj_query_batch_info { uint32_t levels, filter_calls, eq2_calls, join_calls, join_reruns, apply_calls; } rhj_query_batch_info;
+const rhj_query_batch_info *rhj_query_batch_last_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

@@ -39,6 +39,7 @@ INTER_SYMBOLS = [
     "InsertSingleRowIdsToInterResult", "rhj_gather_tables_device", "rhj_build_relation_device", "rhj_sum_gather_device", "rhj_sum_views_device",
     "rhj_filter_eq2_device", "rhj_resident_relation", "rhj_resident_result", "rhj_resident_inter",
     "InitRelationMap", "FreeRelationMap", "PrintRelationMap", "rhj_column_stats_device", "rhj_apply_batch_device",
+    "rhj_filter_eq2_batch_device", "rhj_query_batch_device", "rhj_query_levels", "rhj_query_batch_last_info",
 ]
 
 
@@ -118,6 +119,64 @@ class ApplyDesc(C.Structure):
                 ("terms", ApplyTerm * APPLY_MAX_TERMS), ("rc", C.c_int), ("path", C.c_int)]
 
 
+class Eq2Desc(C.Structure):
+    """rhj_eq2_desc (include/rhj_inter.h): one item of rhj_filter_eq2_batch_device"""
+    _fields_ = [("d_colA", C.c_void_p), ("d_selA", C.c_void_p), ("d_colB", C.c_void_p), ("d_selB", C.c_void_p), ("n", C.c_uint64),
+                ("d_out", C.c_void_p), ("hits", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
+
+
+QUERY_MAX_RELS = 8                       # RHJ_QUERY_MAX_RELS
+QUERY_MAX_VIEWS = 8                      # RHJ_QUERY_MAX_VIEWS
+
+
+class DeviceRelation(C.Structure):
+    """rhj_device_relation (include/rhj_inter.h): a device-resident column store"""
+    _fields_ = [("num_tuples", C.c_uint64), ("num_columns", C.c_uint64), ("d_columns", C.POINTER(C.c_void_p))]
+
+
+class QueryFilter(C.Structure):
+    _fields_ = [("rel", C.c_int), ("col", C.c_int), ("op", C.c_char), ("value", C.c_uint64)]
+
+
+class QueryJoin(C.Structure):
+    _fields_ = [("relA", C.c_int), ("colA", C.c_int), ("relB", C.c_int), ("colB", C.c_int)]
+
+
+class QueryView(C.Structure):
+    _fields_ = [("rel", C.c_int), ("col", C.c_int)]
+
+
+class QueryDesc(C.Structure):
+    """rhj_query_desc (include/rhj_inter.h): one query of rhj_query_batch_device"""
+    _fields_ = [("nrels", C.c_int), ("rels", C.POINTER(C.c_int)), ("nfilters", C.c_int), ("filters", C.POINTER(QueryFilter)),
+                ("njoins", C.c_int), ("joins", C.POINTER(QueryJoin)), ("nviews", C.c_int), ("views", C.POINTER(QueryView)),
+                ("sums", C.c_uint64 * QUERY_MAX_VIEWS), ("rows", C.c_uint64), ("rc", C.c_int)]
+
+
+class QueryBatchInfo(C.Structure):
+    """rhj_query_batch_info (include/rhj_inter.h): the calls the last rhj_query_batch_device issued"""
+    _fields_ = [(n, C.c_uint32) for n in ("levels", "filter_calls", "eq2_calls", "join_calls", "join_reruns", "apply_calls")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def query_descs(queries):
+    """(QueryDesc array, what keeps its pointers alive) of queries = [(relations, joins, filters, views), ...]: relations the
+    relation index of every binding, joins [(a, ca, b, cb)], filters [(a, ca, op, value)], views [(a, c)], a and b bindings."""
+    arr = (QueryDesc * max(len(queries), 1))()
+    keep = []
+    for d, (rels, joins, filters, views) in zip(arr, queries):
+        r = (C.c_int * max(len(rels), 1))(*rels)
+        f = (QueryFilter * max(len(filters), 1))(*[QueryFilter(a, c, op.encode(), int(v) & ((1 << 64) - 1)) for a, c, op, v in filters])
+        j = (QueryJoin * max(len(joins), 1))(*[QueryJoin(*p) for p in joins])
+        v = (QueryView * max(len(views), 1))(*[QueryView(*p) for p in views])
+        keep.append((r, f, j, v))
+        d.nrels, d.rels, d.nfilters, d.filters = len(rels), r, len(filters), f
+        d.njoins, d.joins, d.nviews, d.views = len(joins), j, len(views), v
+    return arr, keep
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ms_hist", "ms_scan", "ms_scatter", "ms_plan", "ms_build", "ms_count",
                                          "ms_offsets", "ms_probe", "ms_total", "ms_h2d", "ms_d2h")] + \
@@ -127,7 +186,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -216,6 +275,11 @@ def load_library(path=None):
         L.rhj_filter_batch_takes.restype = C.c_int
     if hasattr(L, "rhj_apply_batch_device"):      # (A/B runs load earlier builds through this module too)
         L.rhj_apply_batch_device.argtypes = [C.POINTER(ApplyDesc), C.c_uint64]
+    if hasattr(L, "rhj_query_batch_device"):      # (A/B runs load earlier builds through this module too)
+        L.rhj_filter_eq2_batch_device.argtypes = [C.POINTER(Eq2Desc), C.c_uint64]
+        L.rhj_query_batch_device.argtypes = [C.POINTER(DeviceRelation), C.c_int, C.POINTER(QueryDesc), C.c_uint64]
+        L.rhj_query_levels.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(C.c_int)]
+        L.rhj_query_batch_last_info.restype = C.POINTER(QueryBatchInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -512,6 +576,56 @@ class RHJ:
             res.append([(out[a:a + d.n] if a is not None else None, d.terms[k].sum if d.terms[k].d_col else None)
                         for k, a in enumerate(places[i])])
         return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def filter_eq2_batch_device(self, items, count_only=False, with_info=False):
+        """Many two-column equalities in one call (rhj_filter_eq2_batch_device, include/rhj_inter.h): items =
+        [(colA, selA, colB, selB, n), ...], int64 tensors, a vector may be None (the column's rows 0..n).  Returns
+        [(indices tensor, hits), ...]: the ascending i with colA[selA[i]] == colB[selB[i]], or (None, hits) with count_only;
+        the index lists are views of one allocation.  with_info: also the list of the items' path ids (9: batched)."""
+        torch = self.torch
+        n = len(items)
+        arr = (Eq2Desc * max(n, 1))()
+        for d, (colA, selA, colB, selB, rows) in zip(arr, items):
+            d.d_colA, d.d_selA = colA.data_ptr(), (selA.data_ptr() if selA is not None else None)
+            d.d_colB, d.d_selB = colB.data_ptr(), (selB.data_ptr() if selB is not None else None)
+            d.n = int(rows)
+        out = None
+        if not count_only:
+            starts = np.concatenate([[0], np.cumsum([(int(it[4]) + 1) // 2 * 2 for it in items])]).astype(np.int64)      # 16-byte aligned pieces
+            out = torch.empty(max(int(starts[-1]), 1), dtype=torch.int64, device=self.dev)
+            for i in range(n):
+                arr[i].d_out = out.data_ptr() + 8 * int(starts[i])
+        rc = self.lib.rhj_filter_eq2_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_filter_eq2_batch_device failed (%d)" % rc)
+        res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def device_relations(self, cols):
+        """(DeviceRelation array, what keeps its pointers alive) of cols[r][c]: int64 tensors, the columns of relation r"""
+        arr = (DeviceRelation * max(len(cols), 1))()
+        keep = []
+        for d, rel in zip(arr, cols):
+            p = (C.c_void_p * max(len(rel), 1))(*[c.data_ptr() if c.numel() else None for c in rel])
+            keep.append(p)
+            d.num_tuples, d.num_columns, d.d_columns = (rel[0].shape[0] if len(rel) else 0), len(rel), p
+        return arr, keep
+
+    def query_batch_device(self, cols, queries, with_info=False):
+        """A batch of queries run level by level (rhj_query_batch_device, include/rhj_inter.h): cols[r][c] the int64 column
+        tensors of relation r, queries = [(relations, joins, filters, views), ...] as query_descs() takes them.  Returns per
+        query (sums, rows): the views' wrap-around sums as Python ints below 2^64 and the rows of the final result (0: the
+        reference prints NULL for every view).  with_info: also rhj_query_batch_last_info() as a dict."""
+        rels, keep_rels = self.device_relations(cols)
+        arr, keep = query_descs(queries)
+        rc = self.lib.rhj_query_batch_device(rels, len(cols), arr, len(queries))
+        if rc == -3:
+            raise ValueError("rhj_query_batch_device refused queries %s" % [i for i in range(len(queries)) if arr[i].rc == -3])
+        if rc < 0:
+            raise RuntimeError("rhj_query_batch_device failed (%d)" % rc)
+        del keep_rels, keep
+        res = [(list(arr[i].sums[:arr[i].nviews]), arr[i].rows) for i in range(len(queries))]
+        return (res, self.lib.rhj_query_batch_last_info().contents.as_dict()) if with_info else res
 
     def pairs_to_numpy(self, t):
         a = t.cpu().numpy()

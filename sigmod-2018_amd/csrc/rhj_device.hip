@@ -1842,6 +1842,143 @@ static int filter_batch(rhj_filter_desc *filters, uint64_t n)
     return 0;
 }
 
+// ---- batched two-column equalities (rhj_eq2_batch.hip.h) ---------------------------------------------------------------------
+// rhj_filter_eq2_batch_device: rhj_filter_batch_device's scheme over rhj_eq2_desc — the same row limit, chunking rules, arena,
+// pinned block and descriptor buffer.  An item beyond FBATCH_MAX_ROWS runs alone by the single call's kernels.
+static void eq2batch_desc(const rhj_eq2_desc &q, uint64_t *masks, uint64_t *counts, uint64_t *h_total, Eq2BatchDesc &d)
+{
+    memset((void *)&d, 0, sizeof(d));
+    d.colA = q.d_colA; d.selA = q.d_selA; d.colB = q.d_colB; d.selB = q.d_selB;
+    d.n = q.n; d.out = q.d_out; d.masks = masks; d.tile_count = counts; d.h_total = (unsigned long long *)h_total;
+    d.vecA = ((uintptr_t)(q.d_selA ? q.d_selA : q.d_colA) & 15u) == 0;      // the 16-byte loads need the scanned vector's base aligned
+    d.vecB = ((uintptr_t)(q.d_selB ? q.d_selB : q.d_colB) & 15u) == 0;
+}
+
+// One chunk: items[lo, hi), every one with 1..FBATCH_MAX_ROWS rows.
+static int eq2batch_chunk(rhj_eq2_desc *eqs, const std::vector<FBatchItem> &items, size_t lo, size_t hi)
+{
+    const size_t nf = hi - lo;
+    if (batch_arena(g.fbatch_arena, items[hi - 1].end)) return -1;
+    // pinned block: [nf hit totals][nf descriptors][nf + 1 tile starts][nf + 1 task starts]; all but the totals are uploaded in one copy
+    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(Eq2BatchDesc), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
+    if (batch_pinned(totals_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
+    uint64_t *totals = (uint64_t *)g.batch_pin;
+    Eq2BatchDesc *hd = (Eq2BatchDesc *)((char *)g.batch_pin + totals_bytes);
+    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes), *task_start = tile_start + nf + 1;
+    const Eq2BatchDesc *dd = (const Eq2BatchDesc *)g.batch_desc.p;
+    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes), *d_task_start = d_tile_start + nf + 1;
+    memset(totals, 0xff, totals_bytes);                   // (a slot nobody wrote reads as "no total": an error, not an answer)
+    char *A = (char *)g.fbatch_arena.p;
+    uint32_t tiles = 0, tasks = 0;
+    for (size_t k = 0; k < nf; ++k) {
+        const FBatchItem &it = items[lo + k];
+        const rhj_eq2_desc &q = eqs[it.idx];
+        Eq2BatchDesc d;
+        eq2batch_desc(q, (uint64_t *)(A + it.masks), (uint64_t *)(A + it.counts), totals + k, d);
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        const uint32_t t = (uint32_t)((q.n + FILTER_TILE - 1) / FILTER_TILE);
+        tile_start[k] = tiles; task_start[k] = tasks;
+        tiles += t;
+        tasks += q.d_out ? (t + 1) / 2 : 1;               // count only: one wave sums the tile counts, nothing else to do
+    }
+    tile_start[nf] = tiles; task_start[nf] = tasks;
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    RHJ_LAUNCH(k_eq2batch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)nf);
+    const uint32_t want = (tasks + 256 / WAVE - 1) / (256 / WAVE), cap = (uint32_t)g.cus * 32;      // grid-stride, as filter_write_grid
+    RHJ_LAUNCH(k_eq2batch_write, dim3(want < cap ? want : cap), dim3(256), 0, g.stream, dd, d_task_start, (uint32_t)nf);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < nf; ++k) {
+        rhj_eq2_desc &q = eqs[items[lo + k].idx];
+        const uint64_t h = ((volatile uint64_t *)totals)[k];            // written by the wave of the item's last task (system-scope store)
+        if (h > q.n) { fprintf(stderr, "rhj: batched equality %zu left no hit total\n", (size_t)items[lo + k].idx); return -1; }
+        q.hits = h; q.path = 9;
+    }
+    return 0;
+}
+
+// an item beyond FBATCH_MAX_ROWS, alone: the single call as it is, or, counting only, its mask launch and the scan's total
+static int eq2batch_alone(rhj_eq2_desc &q)
+{
+    uint64_t h = 0;
+    if (q.d_out) {
+        const int rc = filter_eq2_device(q.d_colA, q.d_selA, q.d_colB, q.d_selB, q.n, q.d_out, &h);
+        if (rc) return rc;
+    } else {
+        const uint64_t n = q.n, tiles = (n + FILTER_TILE - 1) / FILTER_TILE;
+        if (tiles >= (1ull << 32)) return -2;
+        if (ensure(g.fmask, ((n + 63) / 64 + FILTER_ROUNDS * 8 + 8) * 8) || ensure(g.ftile, tiles * 8) || ensure(g.fbase, tiles * 8) ||
+            ensure(g.summary, sizeof(PlanSummary)))
+            return -1;
+        uint64_t *total = &((PlanSummary *)g.summary.p)->matches;
+        RHJ_LAUNCH(k_filter_mask_eq2, dim3((unsigned)tiles), dim3(256), 0, g.stream, q.d_colA, q.d_selA, q.d_colB, q.d_selB, n,
+                   (uint64_t *)g.fmask.p, (uint64_t *)g.ftile.p);
+        if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
+        HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        h = *(volatile uint64_t *)&g.pin->hits;
+    }
+    q.hits = h; q.path = 0;
+    return 0;
+}
+
+static int eq2_batch(rhj_eq2_desc *eqs, uint64_t n)
+{
+    if (n == 0) return 0;
+    if (!eqs) return -1;
+    bool invalid = false;                                 // the whole batch is validated before anything is launched
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_eq2_desc &q = eqs[i];
+        q.hits = 0; q.rc = 0; q.path = 0;
+        if (q.n && (!q.d_colA || !q.d_colB)) { q.rc = -3; invalid = true; }
+    }
+    if (invalid) return -3;
+    if (ctx_init()) return -1;
+    const bool timed = g.timing >= 1;
+    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    std::vector<FBatchItem> items;
+    std::vector<uint64_t> alone;
+    uint64_t rows = 0, hits = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rows += eqs[i].n;
+        if (eqs[i].n == 0) continue;                      // nothing to launch
+        if (!filter_batch_takes(eqs[i].n)) { alone.push_back(i); continue; }
+        FBatchItem it;
+        it.idx = i; it.masks = it.counts = it.end = 0;
+        items.push_back(it);
+    }
+    for (size_t lo = 0; lo < items.size();) {
+        size_t hi = lo, at = 0;
+        while (hi < items.size() && hi - lo < FBATCH_MAX_FILTERS) {
+            const uint64_t rows_hi = eqs[items[hi].idx].n;
+            const size_t masks = at, counts = masks + ((fbatch_mask_bytes(rows_hi) + 255) & ~(size_t)255);
+            const size_t end = counts + (((size_t)((rows_hi + FILTER_TILE - 1) / FILTER_TILE) * 8 + 255) & ~(size_t)255);
+            if (hi > lo && end > BATCH_ARENA_BUDGET) break;
+            items[hi].masks = masks; items[hi].counts = counts; items[hi].end = end;
+            at = end;
+            ++hi;
+        }
+        if (eq2batch_chunk(eqs, items, lo, hi)) return -1;
+        lo = hi;
+    }
+    for (const uint64_t i : alone) {
+        const int rc = eq2batch_alone(eqs[i]);
+        if (rc < 0) { eqs[i].rc = rc; return rc; }
+    }
+    for (uint64_t i = 0; i < n; ++i) hits += eqs[i].hits;
+    rhj_stats &st = g.stats;
+    memset(&st, 0, sizeof(st));
+    st.n_r = rows; st.matches = hits; st.units = items.size();
+    st.reserved = 9;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
+        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
+    return 0;
+}
+
 // ---- batched rebuilds and view sums (rhj_apply_batch.hip.h) ----------------------------------------------------------------
 // rhj_apply_batch_device: every item of at least one row runs in the launch of its chunk (path 8); there is no run-alone class.
 // A chunk holds at most APPLY_MAX_ITEMS items and APPLY_MAX_TILES tiles (both conditions, not measurements: the first bounds
@@ -1967,6 +2104,307 @@ static int apply_batch(rhj_apply_desc *items, uint64_t n)
         HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
         HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
         st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
+    return 0;
+}
+
+// ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
+// rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
+// equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
+// apply batch.  Host code only.  What a level reads and what it writes never share a buffer:
+//   g_qb.filt       the filters' hit lists: a binding's vector until a join rebuilds it, possibly levels later
+//   g_qb.idx        the level's index lists (equalities' hits, joins' pairs); dead once the level's apply batch has run
+//   g_qb.idx2       the pairs of the joins run a second time (the first call's lists of the others are still needed)
+//   g_qb.level[l]   the vectors level l rebuilds: read by any later level, so every level has its own
+// They belong to the library's own context (the entry point runs on no other), grow and stay, and go with rhj_release().
+struct QueryWorkspace {
+    Buf              filt, idx, idx2;
+    std::vector<Buf> level;
+    hipEvent_t       ev[2] = {};     // the whole call (its inner batches run untimed); created by the first timed call
+} g_qb;
+
+static void query_release()
+{
+    for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
+    for (Buf &b : g_qb.level) if (b.p) (void)hipFree(b.p);
+    g_qb.level.clear();
+}
+
+static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds)
+{
+    if (!q || q->nrels < 1 || q->nrels > RHJ_QUERY_MAX_RELS || !q->rels || q->nviews < 1 || q->nviews > RHJ_QUERY_MAX_VIEWS || !q->views) return -3;
+    if (q->nfilters < 0 || q->njoins < 0 || (q->nfilters && !q->filters) || (q->njoins && !q->joins)) return -3;
+    for (int b = 0; b < q->nrels; ++b) {
+        const int r = q->rels[b];
+        if (r < 0 || r >= nrel || (rels && rels[r].num_tuples && rels[r].num_columns && !rels[r].d_columns)) return -3;
+    }
+    const auto col_ok = [&](int b, int c) {
+        if (b < 0 || b >= q->nrels || c < 0) return false;
+        if (!rels) return true;
+        const rhj_device_relation &R = rels[q->rels[b]];
+        return (uint64_t)c < R.num_columns && (R.num_tuples == 0 || R.d_columns[c] != nullptr);
+    };
+    int per_binding[RHJ_QUERY_MAX_RELS] = {};
+    for (int f = 0; f < q->nfilters; ++f) {
+        const rhj_query_filter &p = q->filters[f];
+        if (!col_ok(p.rel, p.col) || op_code(p.op) < 0 || ++per_binding[p.rel] > RHJ_FILTER_MAX_TERMS) return -3;
+    }
+    int node[RHJ_QUERY_MAX_RELS];
+    for (int b = 0; b < q->nrels; ++b) node[b] = b;
+    for (int l = 0; l < q->njoins; ++l) {
+        const rhj_query_join &p = q->joins[l];
+        if (!col_ok(p.relA, p.colA) || !col_ok(p.relB, p.colB)) return -3;
+        const int na = node[p.relA], nb = node[p.relB];
+        if (kinds) kinds[l] = na == nb;
+        for (int x = 0; x < q->nrels; ++x) if (node[x] == nb) node[x] = na;      // the two nodes merge into A's
+    }
+    for (int v = 0; v < q->nviews; ++v) if (!col_ok(q->views[v].rel, q->views[v].col)) return -3;
+    for (int b = 1; b < q->nrels; ++b) if (node[b] != node[0]) return -3;          // a cross product is not executed here
+    return q->njoins;
+}
+
+struct QueryState {
+    const uint64_t *vec[RHJ_QUERY_MAX_RELS];              // binding -> its row-id vector; nullptr: the whole relation
+    int             node[RHJ_QUERY_MAX_RELS];             // binding -> its node (two merged nodes are the A side's)
+    uint64_t        rows[RHJ_QUERY_MAX_RELS];             // node -> its rows
+    bool            alive;                                // neither finished nor empty
+};
+
+struct QueryBump {                                        // byte offsets of 16-byte aligned pieces of one buffer
+    size_t at = 0;
+    size_t take(uint64_t words) { const size_t o = at; at += (size_t)((words + 1) / 2 * 2) * 8; return o; }
+};
+
+struct QueryTimingOff {                                   // the inner batches record and wait for no events of their own
+    int was;
+    QueryTimingOff() : was(g.timing) { g.timing = 0; }
+    ~QueryTimingOff() { g.timing = was; }
+};
+
+rhj_query_batch_info g_query_info = {};
+
+static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
+{
+    if (n == 0) return 0;
+    if (!queries || (nrel > 0 && !rels)) return -1;
+    memset(&g_query_info, 0, sizeof(g_query_info));
+    bool invalid = false;                                 // the whole batch is validated before a device is touched
+    int maxl = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int lv = query_levels(&queries[i], nrel, rels, nullptr);
+        queries[i].rc = lv < 0 ? -3 : 0;
+        invalid |= lv < 0;
+        if (lv > maxl) maxl = lv;
+    }
+    if (invalid) return -3;
+    for (uint64_t i = 0; i < n; ++i) { memset(queries[i].sums, 0, sizeof(queries[i].sums)); queries[i].rows = 0; }
+    if (ctx_init()) return -1;
+    const bool timed = g.timing >= 1;
+    if (timed && !g_qb.ev[1]) for (auto &ev : g_qb.ev) HIP_TRY(hipEventCreate(&ev));
+    if (timed) HIP_TRY(hipEventRecord(g_qb.ev[0], g.stream));
+    rhj_query_batch_info &info = g_query_info;
+    info.levels = (uint32_t)maxl;
+    const auto column = [&](const rhj_query_desc &q, int b, int c) { return rels[q.rels[b]].d_columns[c]; };
+    {
+        QueryTimingOff inner_untimed;
+        std::vector<QueryState> st(n);
+
+        // the filters: all of one binding are one conjunction, all of them over all queries one call
+        std::vector<rhj_filter_desc> fd;
+        std::vector<std::pair<uint64_t, int>> fwho;       // (query, binding) of a descriptor
+        std::vector<size_t> foff;
+        QueryBump fb;
+        for (uint64_t i = 0; i < n; ++i) {
+            const rhj_query_desc &q = queries[i];
+            QueryState &s = st[i];
+            s.alive = true;
+            for (int b = 0; b < q.nrels; ++b) {
+                s.vec[b] = nullptr; s.node[b] = b; s.rows[b] = rels[q.rels[b]].num_tuples;
+                if (s.rows[b] == 0) s.alive = false;      // an empty relation: every result it takes part in is empty
+            }
+            if (!s.alive) continue;
+            for (int b = 0; b < q.nrels; ++b) {
+                rhj_filter_desc d;
+                memset(&d, 0, sizeof(d));
+                for (int f = 0; f < q.nfilters; ++f) {
+                    const rhj_query_filter &p = q.filters[f];
+                    if (p.rel != b) continue;
+                    rhj_filter_term &t = d.terms[d.nterms++];
+                    t.d_col = column(q, b, p.col); t.value = p.value; t.op = p.op;
+                }
+                if (d.nterms == 0) continue;              // no filter: the binding stays its whole relation
+                d.n = s.rows[b];
+                fd.push_back(d); fwho.emplace_back(i, b); foff.push_back(fb.take(d.n));
+            }
+        }
+        if (!fd.empty()) {
+            if (ensure(g_qb.filt, fb.at)) return -1;
+            for (size_t k = 0; k < fd.size(); ++k) fd[k].d_out = (uint64_t *)((char *)g_qb.filt.p + foff[k]);
+            ++info.filter_calls;
+            const int rc = filter_batch(fd.data(), fd.size());
+            if (rc < 0) return rc;
+            for (size_t k = 0; k < fd.size(); ++k) {
+                QueryState &s = st[fwho[k].first];
+                const int b = fwho[k].second;
+                s.vec[b] = fd[k].d_out; s.rows[b] = fd[k].hits;
+                if (fd[k].hits == 0) s.alive = false;     // a filter without a hit: rows = 0
+            }
+        }
+
+        // the levels.  (Level 0 also runs when no query has a join: the queries without one sum their views in its apply call.)
+        if (g_qb.level.size() < (size_t)(maxl > 1 ? maxl : 1)) g_qb.level.resize((size_t)(maxl > 1 ? maxl : 1));
+        std::vector<rhj_eq2_desc> ed;
+        std::vector<rhj_join_cols_desc> jd, jd2;
+        std::vector<rhj_apply_desc> ad;
+        std::vector<uint64_t> active, awho, short_k;
+        std::vector<size_t> eoff, joff, where, voff;
+        std::vector<int> kind;
+        for (int l = 0; l < maxl || l == 0; ++l) {
+            ed.clear(); jd.clear(); jd2.clear(); ad.clear(); active.clear(); awho.clear(); short_k.clear();
+            eoff.clear(); joff.clear(); where.clear(); voff.clear(); kind.clear();
+            QueryBump ib;
+            for (uint64_t i = 0; i < n; ++i) {
+                const rhj_query_desc &q = queries[i];
+                const QueryState &s = st[i];
+                if (!s.alive || q.njoins <= l) continue;
+                const rhj_query_join &p = q.joins[l];
+                const int na = s.node[p.relA], nb = s.node[p.relB];
+                active.push_back(i);
+                kind.push_back(na == nb);
+                if (na == nb) {                           // both bindings in one node: the two-column equality over its rows
+                    rhj_eq2_desc d;
+                    memset(&d, 0, sizeof(d));
+                    d.d_colA = column(q, p.relA, p.colA); d.d_selA = s.vec[p.relA];
+                    d.d_colB = column(q, p.relB, p.colB); d.d_selB = s.vec[p.relB];
+                    d.n = s.rows[na];
+                    where.push_back(ed.size());
+                    ed.push_back(d); eoff.push_back(ib.take(d.n));
+                } else {
+                    rhj_join_cols_desc d;
+                    memset(&d, 0, sizeof(d));
+                    d.d_colR = column(q, p.relA, p.colA); d.d_selR = s.vec[p.relA]; d.nR = s.rows[na];
+                    d.d_colS = column(q, p.relB, p.colB); d.d_selS = s.vec[p.relB]; d.nS = s.rows[nb];
+                    d.out_capacity = d.nR > d.nS ? d.nR : d.nS;
+                    where.push_back(jd.size());
+                    jd.push_back(d); joff.push_back(ib.take(2 * d.out_capacity));
+                }
+            }
+            if (ensure(g_qb.idx, ib.at)) return -1;
+            for (size_t k = 0; k < ed.size(); ++k) ed[k].d_out = (uint64_t *)((char *)g_qb.idx.p + eoff[k]);
+            for (size_t k = 0; k < jd.size(); ++k) jd[k].d_out = (rhj_result_tuple *)((char *)g_qb.idx.p + joff[k]);
+            if (!ed.empty()) {
+                ++info.eq2_calls;
+                const int rc = eq2_batch(ed.data(), ed.size());
+                if (rc < 0) return rc;
+            }
+            if (!jd.empty()) {
+                ++info.join_calls;
+                const int rc = join_batch(jd.data(), jd.size());
+                if (rc < 0) return rc;
+                if (rc == 1) {                            // fan-out above the guess: the counts are known now
+                    QueryBump rb;
+                    joff.clear();
+                    for (size_t k = 0; k < jd.size(); ++k) {
+                        if (jd[k].rc != 1) continue;
+                        rhj_join_cols_desc d = jd[k];
+                        d.out_capacity = d.matches;
+                        short_k.push_back(k); jd2.push_back(d); joff.push_back(rb.take(2 * d.out_capacity));
+                    }
+                    if (ensure(g_qb.idx2, rb.at)) return -1;
+                    for (size_t k = 0; k < jd2.size(); ++k) jd2[k].d_out = (rhj_result_tuple *)((char *)g_qb.idx2.p + joff[k]);
+                    ++info.join_reruns;
+                    const int rc2 = join_batch(jd2.data(), jd2.size());
+                    if (rc2 < 0) return rc2;
+                    if (rc2 != 0) { fprintf(stderr, "rhj: a join run again with room for its count was short once more\n"); return -1; }
+                    for (size_t k = 0; k < jd2.size(); ++k) jd[short_k[k]] = jd2[k];
+                }
+            }
+
+            // one apply batch: the queries that go on rebuild the vectors of the two nodes, those that finish sum their views
+            QueryBump vb;
+            for (size_t a = 0; a < active.size(); ++a) {
+                const uint64_t i = active[a];
+                const rhj_query_desc &q = queries[i];
+                QueryState &s = st[i];
+                const rhj_query_join &p = q.joins[l];
+                const int na = s.node[p.relA], nb = s.node[p.relB];
+                rhj_apply_desc d;
+                memset(&d, 0, sizeof(d));
+                if (kind[a]) { d.d_idx = ed[where[a]].d_out; d.n = ed[where[a]].hits; d.idx_stride = 1; }
+                else         { d.d_idx = (const uint64_t *)jd[where[a]].d_out; d.n = jd[where[a]].matches; d.idx_stride = 2; }
+                if (d.n == 0) { s.alive = false; continue; }              // an empty list: rows = 0, no item
+                if (l == q.njoins - 1) {
+                    for (int v = 0; v < q.nviews; ++v) {
+                        const int x = q.views[v].rel;
+                        rhj_apply_term &t = d.terms[d.nterms++];
+                        t.side = s.node[x] == nb && na != nb; t.d_src = s.vec[x]; t.d_col = column(q, x, q.views[v].col);
+                    }
+                } else {
+                    for (int x = 0; x < q.nrels; ++x) {
+                        if (s.node[x] != na && s.node[x] != nb) continue;
+                        rhj_apply_term &t = d.terms[d.nterms++];
+                        t.side = s.node[x] == nb && na != nb; t.d_src = s.vec[x];
+                        voff.push_back(vb.take(d.n));
+                    }
+                }
+                ad.push_back(d); awho.push_back(i);
+            }
+            if (l == 0) {
+                for (uint64_t i = 0; i < n; ++i) {        // no join predicate: the views through the one binding's vector
+                    const rhj_query_desc &q = queries[i];
+                    if (!st[i].alive || q.njoins != 0) continue;
+                    rhj_apply_desc d;
+                    memset(&d, 0, sizeof(d));
+                    d.n = st[i].rows[0]; d.idx_stride = 1;
+                    for (int v = 0; v < q.nviews; ++v) {
+                        rhj_apply_term &t = d.terms[d.nterms++];
+                        t.d_src = st[i].vec[0]; t.d_col = column(q, 0, q.views[v].col);
+                    }
+                    ad.push_back(d); awho.push_back(i);
+                }
+            }
+            if (active.empty() && ad.empty()) continue;   // nobody alive at this level
+            if (ensure(g_qb.level[l], vb.at)) return -1;
+            size_t vk = 0;
+            for (size_t a = 0; a < ad.size(); ++a) {
+                const rhj_query_desc &q = queries[awho[a]];
+                if (q.njoins == 0 || l == q.njoins - 1) continue;
+                for (int t = 0; t < ad[a].nterms; ++t) ad[a].terms[t].d_dst = (uint64_t *)((char *)g_qb.level[l].p + voff[vk++]);
+            }
+            ++info.apply_calls;
+            const int rc = apply_batch(ad.data(), ad.size());
+            if (rc < 0) return rc;
+            for (size_t a = 0; a < ad.size(); ++a) {
+                rhj_query_desc &q = queries[awho[a]];
+                QueryState &s = st[awho[a]];
+                const rhj_apply_desc &d = ad[a];
+                if (q.njoins == 0 || l == q.njoins - 1) {
+                    for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.terms[v].sum;
+                    q.rows = d.n;
+                    s.alive = false;                      // finished
+                    continue;
+                }
+                const rhj_query_join &p = q.joins[l];
+                const int na = s.node[p.relA], nb = s.node[p.relB];
+                int t = 0;
+                for (int x = 0; x < q.nrels; ++x) {
+                    if (s.node[x] != na && s.node[x] != nb) continue;
+                    s.vec[x] = d.terms[t++].d_dst; s.node[x] = na;
+                }
+                s.rows[na] = d.n;
+            }
+        }
+    }
+    uint64_t rows = 0;
+    for (uint64_t i = 0; i < n; ++i) rows += queries[i].rows;
+    rhj_stats &stt = g.stats;
+    memset(&stt, 0, sizeof(stt));
+    stt.n_r = n; stt.matches = rows;
+    stt.reserved = 10;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g_qb.ev[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g_qb.ev[1]));
+        stt.ms_total = ev_ms(g_qb.ev[0], g_qb.ev[1]);
     }
     return 0;
 }
@@ -2489,6 +2927,22 @@ int rhj_apply_batch_device(rhj_apply_desc *items, uint64_t n)
     return apply_batch(items, n);
 }
 
+/* Many two-column equalities in one call (include/rhj_inter.h; eq2_batch above) */
+int rhj_filter_eq2_batch_device(rhj_eq2_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return eq2_batch(items, n);
+}
+
+/* A batch of queries run level by level through the batched entry points (include/rhj_inter.h; query_batch above) */
+int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return query_batch(rels, nrel, queries, n);
+}
+int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds) { return query_levels(q, nrel, rels, kinds); }
+const rhj_query_batch_info *rhj_query_batch_last_info(void) { return &g_query_info; }
+
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */
 
 int rhj_bucket_histogram_device(const rhj_tuple *d_in, uint64_t n, uint64_t *d_hist)
@@ -2538,6 +2992,8 @@ void rhj_release(void)
     RhjApiLock api_lock;
     rhj_host_pool_release();
     Ctx *keep = g_cur;
+    g_cur = &g_all[0];
+    if (g.ready) { (void)hipSetDevice(g.device); (void)hipStreamSynchronize(g.stream); query_release(); }
     for (int d = MAX_DEVICES - 1; d >= 0; --d) { g_cur = &g_all[d]; release_current(); }   // (the library's own device last: it stays current)
     g_cur = keep;
 }

@@ -40,6 +40,7 @@
 //   rhj_filter.hip.h       predicate -> ballot masks -> ascending index list.
 //   rhj_filter_batch.hip.h many conjunctive filters in the two launches of one: the same masks and write body, every
 //                          workgroup finding its filter in the chunk's array of tile starts.
+//   rhj_eq2_batch.hip.h    many two-column equalities (colA[selA[i]] == colB[selB[i]]) in the same two launches.
 //   rhj_apply_batch.hip.h  many row-id rebuilds and view sums in one launch: an index list applied to up to 8 terms per item.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
@@ -58,5 +59,6 @@
 #include "rhj_batch.hip.h"
 #include "rhj_filter.hip.h"
 #include "rhj_filter_batch.hip.h"
+#include "rhj_eq2_batch.hip.h"
 #include "rhj_apply_batch.hip.h"
 #include "rhj_diag.hip.h"
