@@ -501,15 +501,28 @@ class RHJ:
             raise RuntimeError("rhj_filter_device failed (%d)" % rc)
         return out[:hits.value]
 
+    def _mask_batch(self, entry, arr, n, count_only, with_info):
+        """The second half of filter_batch_device and filter_eq2_batch_device: arr[0..n) has every field but d_out.  Places the
+        items' outputs in one allocation, calls the entry point and returns the result list (and the path ids)."""
+        out = None
+        if not count_only:
+            starts = np.concatenate([[0], np.cumsum([(arr[i].n + 1) // 2 * 2 for i in range(n)])]).astype(np.int64)      # 16-byte aligned pieces
+            out = self.torch.empty(max(int(starts[-1]), 1), dtype=self.torch.int64, device=self.dev)
+            for i in range(n):
+                arr[i].d_out = out.data_ptr() + 8 * int(starts[i])
+        rc = getattr(self.lib, entry)(arr, n)
+        if rc < 0:
+            raise RuntimeError("%s failed (%d)" % (entry, rc))
+        res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
     def filter_batch_device(self, filters, count_only=False, with_info=False):
         """Many independent conjunctive filters in one call (rhj_filter_batch_device): filters = [(terms, d_sel), ...] with
         terms = [(d_col, op, value), ...] (1..4 of them, columns of one relation; int64 tensors as for filter_device) and
         d_sel a row-id vector or None.  Returns [(indices tensor, hits), ...], or (None, hits) with count_only; the index lists
         are views of one allocation.  with_info: also the list of the filters' path ids (7: batched)."""
-        torch = self.torch
         n = len(filters)
         arr = (FilterDesc * max(n, 1))()
-        rows = []
         for d, (terms, d_sel) in zip(arr, filters):
             if not 1 <= len(terms) <= FILTER_MAX_TERMS:
                 raise ValueError("a filter has 1..%d terms, not %d" % (FILTER_MAX_TERMS, len(terms)))
@@ -518,18 +531,7 @@ class RHJ:
             d.nterms = len(terms)
             for t, (d_col, op, value) in zip(d.terms, terms):
                 t.d_col, t.op, t.value = d_col.data_ptr(), op.encode(), int(value) & ((1 << 64) - 1)
-            rows.append(d.n)
-        out = None
-        if not count_only:
-            starts = np.concatenate([[0], np.cumsum([(r + 1) // 2 * 2 for r in rows])]).astype(np.int64)      # 16-byte aligned pieces
-            out = torch.empty(max(int(starts[-1]), 1), dtype=torch.int64, device=self.dev)
-            for i in range(n):
-                arr[i].d_out = out.data_ptr() + 8 * int(starts[i])
-        rc = self.lib.rhj_filter_batch_device(arr, n)
-        if rc < 0:
-            raise RuntimeError("rhj_filter_batch_device failed (%d)" % rc)
-        res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
-        return (res, [arr[i].path for i in range(n)]) if with_info else res
+        return self._mask_batch("rhj_filter_batch_device", arr, n, count_only, with_info)
 
     def apply_batch_device(self, items, with_info=False):
         """Many row-id rebuilds and view sums in one call (rhj_apply_batch_device, include/rhj_inter.h): items =
@@ -582,24 +584,13 @@ class RHJ:
         [(colA, selA, colB, selB, n), ...], int64 tensors, a vector may be None (the column's rows 0..n).  Returns
         [(indices tensor, hits), ...]: the ascending i with colA[selA[i]] == colB[selB[i]], or (None, hits) with count_only;
         the index lists are views of one allocation.  with_info: also the list of the items' path ids (9: batched)."""
-        torch = self.torch
         n = len(items)
         arr = (Eq2Desc * max(n, 1))()
         for d, (colA, selA, colB, selB, rows) in zip(arr, items):
             d.d_colA, d.d_selA = colA.data_ptr(), (selA.data_ptr() if selA is not None else None)
             d.d_colB, d.d_selB = colB.data_ptr(), (selB.data_ptr() if selB is not None else None)
             d.n = int(rows)
-        out = None
-        if not count_only:
-            starts = np.concatenate([[0], np.cumsum([(int(it[4]) + 1) // 2 * 2 for it in items])]).astype(np.int64)      # 16-byte aligned pieces
-            out = torch.empty(max(int(starts[-1]), 1), dtype=torch.int64, device=self.dev)
-            for i in range(n):
-                arr[i].d_out = out.data_ptr() + 8 * int(starts[i])
-        rc = self.lib.rhj_filter_eq2_batch_device(arr, n)
-        if rc < 0:
-            raise RuntimeError("rhj_filter_eq2_batch_device failed (%d)" % rc)
-        res = [(None, arr[i].hits) if count_only else (out[int(starts[i]):int(starts[i]) + arr[i].hits], arr[i].hits) for i in range(n)]
-        return (res, [arr[i].path for i in range(n)]) if with_info else res
+        return self._mask_batch("rhj_filter_eq2_batch_device", arr, n, count_only, with_info)
 
     def device_relations(self, cols):
         """(DeviceRelation array, what keeps its pointers alive) of cols[r][c]: int64 tensors, the columns of relation r"""

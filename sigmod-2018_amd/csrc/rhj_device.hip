@@ -1411,6 +1411,35 @@ static int batch_pinned(size_t bytes)
     return 0;
 }
 
+// The frame of every batched entry point.  batch_open: reset(q) clears item q's results and says whether q is valid; the whole
+// batch is validated before anything is launched, an invalid item gets rc -3 and the call returns -3.  Then the context, and
+// with timing on the event the call starts at.  batch_close: st becomes the call's rhj_last_stats(), with the time between the
+// two events (what a batch runs alone records the stage events).
+template <class D, class Reset>
+static int batch_open(D *items, uint64_t n, Reset reset, bool &timed)
+{
+    if (!items) return -1;
+    bool invalid = false;
+    for (uint64_t i = 0; i < n; ++i)
+        if (!reset(items[i])) { items[i].rc = -3; invalid = true; }
+    if (invalid) return -3;
+    if (ctx_init()) return -1;
+    timed = g.timing >= 1;
+    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    return 0;
+}
+
+static int batch_close(bool timed, const rhj_stats &st)
+{
+    g.stats = st;
+    if (timed) {
+        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
+        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
+        g.stats.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
+    }
+    return 0;
+}
+
 struct BatchItem {
     uint64_t   idx;                                       // the join's place in the caller's array
     int        bits;
@@ -1527,17 +1556,8 @@ template <class D>
 static int join_batch(D *joins, uint64_t n)
 {
     if (n == 0) return 0;
-    if (!joins) return -1;
-    bool invalid = false;                                 // the whole batch is validated before anything is launched
-    for (uint64_t i = 0; i < n; ++i) {
-        D &q = joins[i];
-        q.matches = 0; q.rc = 0; q.path = 0;
-        if (!batch_valid(q)) { q.rc = -3; invalid = true; }
-    }
-    if (invalid) return -3;
-    if (ctx_init()) return -1;
-    const bool timed = g.timing >= 1;
-    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    bool timed = false;
+    if (const int rc = batch_open(joins, n, [](D &q) { q.matches = 0; q.rc = 0; q.path = 0; return batch_valid(q); }, timed)) return rc;
     std::vector<BatchItem> items;
     std::vector<uint64_t> alone;
     uint64_t sum_r = 0, sum_s = 0, sum_m = 0, units = 0;
@@ -1581,15 +1601,10 @@ static int join_batch(D *joins, uint64_t n)
     }
     int any_short = 0;
     for (uint64_t i = 0; i < n; ++i) { sum_m += joins[i].matches; any_short |= joins[i].rc == 1; }
-    rhj_stats &st = g.stats;
-    memset(&st, 0, sizeof(st));
+    rhj_stats st = {};
     st.n_r = sum_r; st.n_s = sum_s; st.matches = sum_m; st.units = units; st.radix_bits = g.bits;
     st.reserved = 6;
-    if (timed) {
-        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
-        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
-        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
-    }
+    if (batch_close(timed, st)) return -1;
     return any_short;
 }
 
@@ -1623,6 +1638,26 @@ int filter_write_out(uint64_t n, uint64_t tiles, uint64_t *total, uint64_t *d_ou
     HIP_TRY(hipStreamSynchronize(g.stream));
     *hits = *(volatile uint64_t *)&g.pin->hits;
     return 0;
+}
+
+// tile counts -> the hit total alone (a count-only item that runs outside its batch): the scan, and its total copied back
+int filter_count_out(uint64_t tiles, uint64_t *total, uint64_t *hits)
+{
+    if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
+    HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    *hits = *(volatile uint64_t *)&g.pin->hits;
+    return 0;
+}
+
+// What an item that runs alone inside a batch works in, the single calls' buffers: mask words, tile counts, their scan and the
+// total.  The mask bytes are what k_filter_mask and k_filter_mask_eq2 need, n / 8 + 576 or more; k_fbatch_mask's
+// fbatch_mask_bytes(n) is at most n / 8 + 16, so this covers it for every n.
+int filter_workspace(uint64_t n, uint64_t tiles)
+{
+    return ensure(g.fmask, ((n + 63) / 64 + FILTER_ROUNDS * 8 + 8) * 8) || ensure(g.ftile, tiles * 8) || ensure(g.fbase, tiles * 8) ||
+           ensure(g.summary, sizeof(PlanSummary)) ? -1 : 0;
 }
 
 int filter_device(const uint64_t *d_col, const uint64_t *d_sel, uint64_t n, char op, uint64_t value, uint64_t *d_out,
@@ -1676,13 +1711,14 @@ int filter_eq2_device(const uint64_t *colA, const uint64_t *selA, const uint64_t
     return 0;
 }
 
-// ---- batched filters (rhj_filter_batch.hip.h) -----------------------------------------------------------------------------
-// rhj_filter_batch_device: the filters filter_batch_takes() names run as chunks of two launches and one stream synchronisation
-// each; a larger one is run alone, by the same mask kernel and the scan + write launches of a large single filter.
+// ---- batched filters and two-column equalities (rhj_filter_batch.hip.h, rhj_eq2_batch.hip.h) --------------------------------
+// rhj_filter_batch_device and rhj_filter_eq2_batch_device are ONE scheme over two descriptors (templates over rhj_filter_desc /
+// rhj_eq2_desc, as join_batch is over its two): the items filter_batch_takes() names run as chunks of two launches and one stream
+// synchronisation each; a larger one is run alone (fbatch_alone).
 //
-// A chunk's filters live side by side in ONE arena (every filter its mask words, 16 bytes per 128 rows, and its tile counts),
-// which never exceeds BATCH_ARENA_BUDGET, and a chunk never holds more than FBATCH_MAX_FILTERS filters: a batch beyond either is
-// cut into chunks, in call order.  The arena is the batch's own: g.fmask / g.ftile / g.fbase stay what the single calls made them.
+// A chunk's items live side by side in ONE arena (every item its mask words, 16 bytes per 128 rows, and its tile counts), which
+// never exceeds BATCH_ARENA_BUDGET, and a chunk never holds more than FBATCH_MAX_FILTERS items: a batch beyond either is cut into
+// chunks, in call order.  The arena is the batches' own: g.fmask / g.ftile / g.fbase stay what the single calls made them.
 constexpr uint64_t FBATCH_MAX_ROWS = FILTER_SELF_TILES * FILTER_TILE;
 constexpr size_t FBATCH_MAX_FILTERS = 4096;
 
@@ -1691,9 +1727,13 @@ static int filter_batch_takes(uint64_t rows) { return rows >= 1 && rows <= FBATC
 static size_t fbatch_mask_bytes(uint64_t n) { return (size_t)((n + 2 * WAVE - 1) / (2 * WAVE)) * 16; }
 
 struct FBatchItem {
-    uint64_t idx;                                         // the filter's place in the caller's array
+    uint64_t idx;                                         // the item's place in the caller's array
     size_t   masks, counts, end;                          // byte offsets in the arena
 };
+
+// What differs between the two: the device descriptor and how it is filled, the validity rule, the two kernels, the path id,
+// the noun of the error text, and how an item beyond FBATCH_MAX_ROWS runs alone.
+template <class D> using fbatch_dev = std::conditional_t<std::is_same<D, rhj_filter_desc>::value, FBatchDesc, Eq2BatchDesc>;
 
 static void fbatch_desc(const rhj_filter_desc &q, uint64_t *masks, uint64_t *counts, uint64_t *h_total, FBatchDesc &d)
 {
@@ -1708,26 +1748,61 @@ static void fbatch_desc(const rhj_filter_desc &q, uint64_t *masks, uint64_t *cou
     d.vec = (scanned & 15u) == 0;
 }
 
-// One chunk: items[lo, hi), every one with 1..FBATCH_MAX_ROWS rows.
-static int fbatch_chunk(rhj_filter_desc *filters, const std::vector<FBatchItem> &items, size_t lo, size_t hi)
+static void fbatch_desc(const rhj_eq2_desc &q, uint64_t *masks, uint64_t *counts, uint64_t *h_total, Eq2BatchDesc &d)
 {
+    memset((void *)&d, 0, sizeof(d));
+    d.colA = q.d_colA; d.selA = q.d_selA; d.colB = q.d_colB; d.selB = q.d_selB;
+    d.n = q.n; d.out = q.d_out; d.masks = masks; d.tile_count = counts; d.h_total = (unsigned long long *)h_total;
+    d.vecA = ((uintptr_t)(q.d_selA ? q.d_selA : q.d_colA) & 15u) == 0;      // the 16-byte loads need the scanned vector's base aligned
+    d.vecB = ((uintptr_t)(q.d_selB ? q.d_selB : q.d_colB) & 15u) == 0;
+}
+
+static bool fbatch_valid(const rhj_filter_desc &q)
+{
+    bool ok = q.nterms >= 1 && q.nterms <= RHJ_FILTER_MAX_TERMS;
+    for (int t = 0; ok && t < q.nterms; ++t) ok = op_code(q.terms[t].op) >= 0 && (q.n == 0 || q.terms[t].d_col != nullptr);
+    return ok;
+}
+static bool fbatch_valid(const rhj_eq2_desc &q) { return q.n == 0 || (q.d_colA && q.d_colB); }
+
+static inline int fbatch_path(const rhj_filter_desc &) { return 7; }
+static inline int fbatch_path(const rhj_eq2_desc &) { return 9; }
+static inline const char *fbatch_noun(const rhj_filter_desc &) { return "filter"; }
+static inline const char *fbatch_noun(const rhj_eq2_desc &) { return "equality"; }
+
+static void fbatch_launch(const FBatchDesc *dd, uint32_t nf, const uint32_t *tile_start, uint32_t tiles, const uint32_t *task_start, uint32_t write_grid)
+{
+    RHJ_LAUNCH(k_fbatch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, tile_start, nf);
+    RHJ_LAUNCH(k_fbatch_write, dim3(write_grid), dim3(256), 0, g.stream, dd, task_start, nf);
+}
+static void fbatch_launch(const Eq2BatchDesc *dd, uint32_t nf, const uint32_t *tile_start, uint32_t tiles, const uint32_t *task_start, uint32_t write_grid)
+{
+    RHJ_LAUNCH(k_eq2batch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, tile_start, nf);
+    RHJ_LAUNCH(k_eq2batch_write, dim3(write_grid), dim3(256), 0, g.stream, dd, task_start, nf);
+}
+
+// One chunk: items[lo, hi), every one with 1..FBATCH_MAX_ROWS rows.
+template <class D>
+static int fbatch_chunk(D *qs, const std::vector<FBatchItem> &items, size_t lo, size_t hi)
+{
+    using Dev = fbatch_dev<D>;
     const size_t nf = hi - lo;
     if (batch_arena(g.fbatch_arena, items[hi - 1].end)) return -1;
     // pinned block: [nf hit totals][nf descriptors][nf + 1 tile starts][nf + 1 task starts]; all but the totals are uploaded in one copy
-    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(FBatchDesc), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
+    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(Dev), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
     if (batch_pinned(totals_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
     uint64_t *totals = (uint64_t *)g.batch_pin;
-    FBatchDesc *hd = (FBatchDesc *)((char *)g.batch_pin + totals_bytes);
+    Dev *hd = (Dev *)((char *)g.batch_pin + totals_bytes);
     uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes), *task_start = tile_start + nf + 1;
-    const FBatchDesc *dd = (const FBatchDesc *)g.batch_desc.p;
+    const Dev *dd = (const Dev *)g.batch_desc.p;
     const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes), *d_task_start = d_tile_start + nf + 1;
     memset(totals, 0xff, totals_bytes);                   // (a slot nobody wrote reads as "no total": an error, not an answer)
     char *A = (char *)g.fbatch_arena.p;
     uint32_t tiles = 0, tasks = 0;
     for (size_t k = 0; k < nf; ++k) {
         const FBatchItem &it = items[lo + k];
-        const rhj_filter_desc &q = filters[it.idx];
-        FBatchDesc d;
+        const D &q = qs[it.idx];
+        Dev d;
         fbatch_desc(q, (uint64_t *)(A + it.masks), (uint64_t *)(A + it.counts), totals + k, d);
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
         const uint32_t t = (uint32_t)((q.n + FILTER_TILE - 1) / FILTER_TILE);
@@ -1737,16 +1812,15 @@ static int fbatch_chunk(rhj_filter_desc *filters, const std::vector<FBatchItem> 
     }
     tile_start[nf] = tiles; task_start[nf] = tasks;
     HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
-    RHJ_LAUNCH(k_fbatch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)nf);
     const uint32_t want = (tasks + 256 / WAVE - 1) / (256 / WAVE), cap = (uint32_t)g.cus * 32;      // grid-stride, as filter_write_grid
-    RHJ_LAUNCH(k_fbatch_write, dim3(want < cap ? want : cap), dim3(256), 0, g.stream, dd, d_task_start, (uint32_t)nf);
+    fbatch_launch(dd, (uint32_t)nf, d_tile_start, tiles, d_task_start, want < cap ? want : cap);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
     for (size_t k = 0; k < nf; ++k) {
-        rhj_filter_desc &q = filters[items[lo + k].idx];
-        const uint64_t h = ((volatile uint64_t *)totals)[k];            // written by the wave of the filter's last task (system-scope store)
-        if (h > q.n) { fprintf(stderr, "rhj: batched filter %zu left no hit total\n", (size_t)items[lo + k].idx); return -1; }
-        q.hits = h; q.path = 7;
+        D &q = qs[items[lo + k].idx];
+        const uint64_t h = ((volatile uint64_t *)totals)[k];            // written by the wave of the item's last task (system-scope store)
+        if (h > q.n) { fprintf(stderr, "rhj: batched %s %zu left no hit total\n", fbatch_noun(q), (size_t)items[lo + k].idx); return -1; }
+        q.hits = h; q.path = fbatch_path(q);
     }
     return 0;
 }
@@ -1757,9 +1831,7 @@ static int fbatch_alone(rhj_filter_desc &q)
     const uint64_t n = q.n, tiles = (n + FILTER_TILE - 1) / FILTER_TILE;
     if (tiles >= (1ull << 32)) return -2;
     const size_t up_bytes = sizeof(FBatchDesc) + 2 * 4;
-    if (ensure(g.fmask, fbatch_mask_bytes(n)) || ensure(g.ftile, tiles * 8) || ensure(g.fbase, tiles * 8) ||
-        ensure(g.summary, sizeof(PlanSummary)) || batch_pinned(up_bytes) || ensure(g.batch_desc, up_bytes))
-        return -1;
+    if (filter_workspace(n, tiles) || batch_pinned(up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
     FBatchDesc *hd = (FBatchDesc *)g.batch_pin;
     uint32_t *tile_start = (uint32_t *)(hd + 1);
     FBatchDesc d;
@@ -1771,134 +1843,13 @@ static int fbatch_alone(rhj_filter_desc &q)
     RHJ_LAUNCH(k_fbatch_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, (const FBatchDesc *)g.batch_desc.p,
                (const uint32_t *)((const char *)g.batch_desc.p + sizeof(FBatchDesc)), 1u);
     uint64_t h = 0;
-    if (q.d_out) {
-        if (filter_write_out(n, tiles, total, q.d_out, &h)) return -1;
-    } else {                                              // count only: the scan's total is all there is to fetch
-        if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
-        HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        h = *(volatile uint64_t *)&g.pin->hits;
-    }
+    if (q.d_out ? filter_write_out(n, tiles, total, q.d_out, &h) : filter_count_out(tiles, total, &h)) return -1;
     q.hits = h; q.path = 0;
     return 0;
 }
 
-static int filter_batch(rhj_filter_desc *filters, uint64_t n)
-{
-    if (n == 0) return 0;
-    if (!filters) return -1;
-    bool invalid = false;                                 // the whole batch is validated before anything is launched
-    for (uint64_t i = 0; i < n; ++i) {
-        rhj_filter_desc &q = filters[i];
-        q.hits = 0; q.rc = 0; q.path = 0;
-        bool ok = q.nterms >= 1 && q.nterms <= RHJ_FILTER_MAX_TERMS;
-        for (int t = 0; ok && t < q.nterms; ++t) ok = op_code(q.terms[t].op) >= 0 && (q.n == 0 || q.terms[t].d_col != nullptr);
-        if (!ok) { q.rc = -3; invalid = true; }
-    }
-    if (invalid) return -3;
-    if (ctx_init()) return -1;
-    const bool timed = g.timing >= 1;
-    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
-    std::vector<FBatchItem> items;
-    std::vector<uint64_t> alone;
-    uint64_t rows = 0, hits = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        rows += filters[i].n;
-        if (filters[i].n == 0) continue;                  // nothing to launch
-        if (!filter_batch_takes(filters[i].n)) { alone.push_back(i); continue; }
-        FBatchItem it;
-        it.idx = i; it.masks = it.counts = it.end = 0;
-        items.push_back(it);
-    }
-    for (size_t lo = 0; lo < items.size();) {
-        size_t hi = lo, at = 0;
-        while (hi < items.size() && hi - lo < FBATCH_MAX_FILTERS) {
-            const uint64_t rows_hi = filters[items[hi].idx].n;
-            const size_t masks = at, counts = masks + ((fbatch_mask_bytes(rows_hi) + 255) & ~(size_t)255);
-            const size_t end = counts + (((size_t)((rows_hi + FILTER_TILE - 1) / FILTER_TILE) * 8 + 255) & ~(size_t)255);
-            if (hi > lo && end > BATCH_ARENA_BUDGET) break;
-            items[hi].masks = masks; items[hi].counts = counts; items[hi].end = end;
-            at = end;
-            ++hi;
-        }
-        if (fbatch_chunk(filters, items, lo, hi)) return -1;
-        lo = hi;
-    }
-    for (const uint64_t i : alone) {
-        const int rc = fbatch_alone(filters[i]);
-        if (rc < 0) { filters[i].rc = rc; return rc; }
-    }
-    for (uint64_t i = 0; i < n; ++i) hits += filters[i].hits;
-    rhj_stats &st = g.stats;
-    memset(&st, 0, sizeof(st));
-    st.n_r = rows; st.matches = hits; st.units = items.size();
-    st.reserved = 7;
-    if (timed) {
-        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
-        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
-        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
-    }
-    return 0;
-}
-
-// ---- batched two-column equalities (rhj_eq2_batch.hip.h) ---------------------------------------------------------------------
-// rhj_filter_eq2_batch_device: rhj_filter_batch_device's scheme over rhj_eq2_desc — the same row limit, chunking rules, arena,
-// pinned block and descriptor buffer.  An item beyond FBATCH_MAX_ROWS runs alone by the single call's kernels.
-static void eq2batch_desc(const rhj_eq2_desc &q, uint64_t *masks, uint64_t *counts, uint64_t *h_total, Eq2BatchDesc &d)
-{
-    memset((void *)&d, 0, sizeof(d));
-    d.colA = q.d_colA; d.selA = q.d_selA; d.colB = q.d_colB; d.selB = q.d_selB;
-    d.n = q.n; d.out = q.d_out; d.masks = masks; d.tile_count = counts; d.h_total = (unsigned long long *)h_total;
-    d.vecA = ((uintptr_t)(q.d_selA ? q.d_selA : q.d_colA) & 15u) == 0;      // the 16-byte loads need the scanned vector's base aligned
-    d.vecB = ((uintptr_t)(q.d_selB ? q.d_selB : q.d_colB) & 15u) == 0;
-}
-
-// One chunk: items[lo, hi), every one with 1..FBATCH_MAX_ROWS rows.
-static int eq2batch_chunk(rhj_eq2_desc *eqs, const std::vector<FBatchItem> &items, size_t lo, size_t hi)
-{
-    const size_t nf = hi - lo;
-    if (batch_arena(g.fbatch_arena, items[hi - 1].end)) return -1;
-    // pinned block: [nf hit totals][nf descriptors][nf + 1 tile starts][nf + 1 task starts]; all but the totals are uploaded in one copy
-    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(Eq2BatchDesc), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
-    if (batch_pinned(totals_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    uint64_t *totals = (uint64_t *)g.batch_pin;
-    Eq2BatchDesc *hd = (Eq2BatchDesc *)((char *)g.batch_pin + totals_bytes);
-    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes), *task_start = tile_start + nf + 1;
-    const Eq2BatchDesc *dd = (const Eq2BatchDesc *)g.batch_desc.p;
-    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes), *d_task_start = d_tile_start + nf + 1;
-    memset(totals, 0xff, totals_bytes);                   // (a slot nobody wrote reads as "no total": an error, not an answer)
-    char *A = (char *)g.fbatch_arena.p;
-    uint32_t tiles = 0, tasks = 0;
-    for (size_t k = 0; k < nf; ++k) {
-        const FBatchItem &it = items[lo + k];
-        const rhj_eq2_desc &q = eqs[it.idx];
-        Eq2BatchDesc d;
-        eq2batch_desc(q, (uint64_t *)(A + it.masks), (uint64_t *)(A + it.counts), totals + k, d);
-        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
-        const uint32_t t = (uint32_t)((q.n + FILTER_TILE - 1) / FILTER_TILE);
-        tile_start[k] = tiles; task_start[k] = tasks;
-        tiles += t;
-        tasks += q.d_out ? (t + 1) / 2 : 1;               // count only: one wave sums the tile counts, nothing else to do
-    }
-    tile_start[nf] = tiles; task_start[nf] = tasks;
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
-    RHJ_LAUNCH(k_eq2batch_mask, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)nf);
-    const uint32_t want = (tasks + 256 / WAVE - 1) / (256 / WAVE), cap = (uint32_t)g.cus * 32;      // grid-stride, as filter_write_grid
-    RHJ_LAUNCH(k_eq2batch_write, dim3(want < cap ? want : cap), dim3(256), 0, g.stream, dd, d_task_start, (uint32_t)nf);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    for (size_t k = 0; k < nf; ++k) {
-        rhj_eq2_desc &q = eqs[items[lo + k].idx];
-        const uint64_t h = ((volatile uint64_t *)totals)[k];            // written by the wave of the item's last task (system-scope store)
-        if (h > q.n) { fprintf(stderr, "rhj: batched equality %zu left no hit total\n", (size_t)items[lo + k].idx); return -1; }
-        q.hits = h; q.path = 9;
-    }
-    return 0;
-}
-
-// an item beyond FBATCH_MAX_ROWS, alone: the single call as it is, or, counting only, its mask launch and the scan's total
-static int eq2batch_alone(rhj_eq2_desc &q)
+// an equality beyond FBATCH_MAX_ROWS, alone: the single call as it is, or, counting only, its mask launch and the scan's total
+static int fbatch_alone(rhj_eq2_desc &q)
 {
     uint64_t h = 0;
     if (q.d_out) {
@@ -1907,43 +1858,29 @@ static int eq2batch_alone(rhj_eq2_desc &q)
     } else {
         const uint64_t n = q.n, tiles = (n + FILTER_TILE - 1) / FILTER_TILE;
         if (tiles >= (1ull << 32)) return -2;
-        if (ensure(g.fmask, ((n + 63) / 64 + FILTER_ROUNDS * 8 + 8) * 8) || ensure(g.ftile, tiles * 8) || ensure(g.fbase, tiles * 8) ||
-            ensure(g.summary, sizeof(PlanSummary)))
-            return -1;
+        if (filter_workspace(n, tiles)) return -1;
         uint64_t *total = &((PlanSummary *)g.summary.p)->matches;
         RHJ_LAUNCH(k_filter_mask_eq2, dim3((unsigned)tiles), dim3(256), 0, g.stream, q.d_colA, q.d_selA, q.d_colB, q.d_selB, n,
                    (uint64_t *)g.fmask.p, (uint64_t *)g.ftile.p);
-        if (launch_offsets((const uint64_t *)g.ftile.p, (uint64_t *)g.fbase.p, nullptr, tiles, tiles, total)) return -1;
-        HIP_TRY(hipMemcpyAsync(&g.pin->hits, total, 8, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        h = *(volatile uint64_t *)&g.pin->hits;
+        if (filter_count_out(tiles, total, &h)) return -1;
     }
     q.hits = h; q.path = 0;
     return 0;
 }
 
-static int eq2_batch(rhj_eq2_desc *eqs, uint64_t n)
+template <class D>
+static int filter_batch(D *qs, uint64_t n)
 {
     if (n == 0) return 0;
-    if (!eqs) return -1;
-    bool invalid = false;                                 // the whole batch is validated before anything is launched
-    for (uint64_t i = 0; i < n; ++i) {
-        rhj_eq2_desc &q = eqs[i];
-        q.hits = 0; q.rc = 0; q.path = 0;
-        if (q.n && (!q.d_colA || !q.d_colB)) { q.rc = -3; invalid = true; }
-    }
-    if (invalid) return -3;
-    if (ctx_init()) return -1;
-    const bool timed = g.timing >= 1;
-    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+    bool timed = false;
+    if (const int rc = batch_open(qs, n, [](D &q) { q.hits = 0; q.rc = 0; q.path = 0; return fbatch_valid(q); }, timed)) return rc;
     std::vector<FBatchItem> items;
     std::vector<uint64_t> alone;
     uint64_t rows = 0, hits = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        rows += eqs[i].n;
-        if (eqs[i].n == 0) continue;                      // nothing to launch
-        if (!filter_batch_takes(eqs[i].n)) { alone.push_back(i); continue; }
+        rows += qs[i].n;
+        if (qs[i].n == 0) continue;                       // nothing to launch
+        if (!filter_batch_takes(qs[i].n)) { alone.push_back(i); continue; }
         FBatchItem it;
         it.idx = i; it.masks = it.counts = it.end = 0;
         items.push_back(it);
@@ -1951,7 +1888,7 @@ static int eq2_batch(rhj_eq2_desc *eqs, uint64_t n)
     for (size_t lo = 0; lo < items.size();) {
         size_t hi = lo, at = 0;
         while (hi < items.size() && hi - lo < FBATCH_MAX_FILTERS) {
-            const uint64_t rows_hi = eqs[items[hi].idx].n;
+            const uint64_t rows_hi = qs[items[hi].idx].n;
             const size_t masks = at, counts = masks + ((fbatch_mask_bytes(rows_hi) + 255) & ~(size_t)255);
             const size_t end = counts + (((size_t)((rows_hi + FILTER_TILE - 1) / FILTER_TILE) * 8 + 255) & ~(size_t)255);
             if (hi > lo && end > BATCH_ARENA_BUDGET) break;
@@ -1959,24 +1896,18 @@ static int eq2_batch(rhj_eq2_desc *eqs, uint64_t n)
             at = end;
             ++hi;
         }
-        if (eq2batch_chunk(eqs, items, lo, hi)) return -1;
+        if (fbatch_chunk(qs, items, lo, hi)) return -1;
         lo = hi;
     }
     for (const uint64_t i : alone) {
-        const int rc = eq2batch_alone(eqs[i]);
-        if (rc < 0) { eqs[i].rc = rc; return rc; }
+        const int rc = fbatch_alone(qs[i]);
+        if (rc < 0) { qs[i].rc = rc; return rc; }
     }
-    for (uint64_t i = 0; i < n; ++i) hits += eqs[i].hits;
-    rhj_stats &st = g.stats;
-    memset(&st, 0, sizeof(st));
+    for (uint64_t i = 0; i < n; ++i) hits += qs[i].hits;
+    rhj_stats st = {};
     st.n_r = rows; st.matches = hits; st.units = items.size();
-    st.reserved = 9;
-    if (timed) {
-        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
-        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
-        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
-    }
-    return 0;
+    st.reserved = fbatch_path(qs[0]);
+    return batch_close(timed, st);
 }
 
 // ---- batched rebuilds and view sums (rhj_apply_batch.hip.h) ----------------------------------------------------------------
@@ -2066,18 +1997,14 @@ static int apply_chunk(rhj_apply_desc *items, const std::vector<uint64_t> &which
 static int apply_batch(rhj_apply_desc *items, uint64_t n)
 {
     if (n == 0) return 0;
-    if (!items) return -1;
-    bool invalid = false;                                 // the whole batch is validated before anything is launched
-    for (uint64_t i = 0; i < n; ++i) {
-        rhj_apply_desc &q = items[i];
+    bool timed = false;
+    const auto reset = [](rhj_apply_desc &q) {
         q.rc = 0; q.path = 0;
-        if (!apply_valid(q)) { q.rc = -3; invalid = true; continue; }
+        if (!apply_valid(q)) return false;
         for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0;
-    }
-    if (invalid) return -3;
-    if (ctx_init()) return -1;
-    const bool timed = g.timing >= 1;
-    if (timed) HIP_TRY(hipEventRecord(g.ev_batch[0], g.stream));
+        return true;
+    };
+    if (const int rc = batch_open(items, n, reset, timed)) return rc;
     std::vector<uint64_t> which;
     uint64_t rows = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -2096,16 +2023,10 @@ static int apply_batch(rhj_apply_desc *items, uint64_t n)
         if (apply_chunk(items, which, lo, hi)) return -1;
         lo = hi;
     }
-    rhj_stats &st = g.stats;
-    memset(&st, 0, sizeof(st));
+    rhj_stats st = {};
     st.n_r = rows; st.units = which.size();
     st.reserved = 8;
-    if (timed) {
-        HIP_TRY(hipEventRecord(g.ev_batch[1], g.stream));
-        HIP_TRY(hipEventSynchronize(g.ev_batch[1]));
-        st.ms_total = ev_ms(g.ev_batch[0], g.ev_batch[1]);
-    }
-    return 0;
+    return batch_close(timed, st);
 }
 
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
@@ -2294,7 +2215,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
             for (size_t k = 0; k < jd.size(); ++k) jd[k].d_out = (rhj_result_tuple *)((char *)g_qb.idx.p + joff[k]);
             if (!ed.empty()) {
                 ++info.eq2_calls;
-                const int rc = eq2_batch(ed.data(), ed.size());
+                const int rc = filter_batch(ed.data(), ed.size());
                 if (rc < 0) return rc;
             }
             if (!jd.empty()) {
@@ -2927,11 +2848,11 @@ int rhj_apply_batch_device(rhj_apply_desc *items, uint64_t n)
     return apply_batch(items, n);
 }
 
-/* Many two-column equalities in one call (include/rhj_inter.h; eq2_batch above) */
+/* Many two-column equalities in one call (include/rhj_inter.h; filter_batch above) */
 int rhj_filter_eq2_batch_device(rhj_eq2_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    return eq2_batch(items, n);
+    return filter_batch(items, n);
 }
 
 /* A batch of queries run level by level through the batched entry points (include/rhj_inter.h; query_batch above) */

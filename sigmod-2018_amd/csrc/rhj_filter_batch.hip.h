@@ -13,6 +13,12 @@
 // A filter is a conjunction of up to RHJ_FILTER_MAX_TERMS predicates over columns of one relation.  The mask kernel keeps a
 // round's two ballot words in SGPRs and ANDs every term's ballots into them, so only one term's 16 values a lane are live at a
 // time; the mask layout is k_filter_mask's, and the write pass is k_filter_write<true>'s own body (filter_write_task).
+//
+// The batch of two-column equalities (rhj_eq2_batch.hip.h) is the same scheme over another descriptor, and what the two have
+// in common is written once, here: fbatch_find, the bounds ballots (fbatch_bounds), the loads of one column through its optional
+// row-id vector (fbatch_side), the mask store and tile count (fbatch_mask_round, fbatch_mask_count), and the whole write pass (fbatch_write_tasks, a
+// template over the descriptor type; k_fbatch_write and k_eq2batch_write are its two instances).  A mask kernel keeps what is
+// its own: the term loop with its early-out and three comparisons here, the two sides and one equality there.
 #pragma once
 #include "rhj.h"
 #include "rhj_filter.hip.h"
@@ -56,9 +62,76 @@ __device__ __forceinline__ uint32_t fbatch_find(const uint32_t *__restrict__ sta
     return lo;
 }
 
-__global__ __launch_bounds__(256) void k_fbatch_mask(const FBatchDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t nf)
+// The bounds ballots every mask kernel starts from: me[k] / mo[k] the even / odd rows of round k that lie inside [0, n).
+__device__ __forceinline__ void fbatch_bounds(uint64_t n, uint64_t lbase, uint64_t (&me)[FILTER_ROUNDS], uint64_t (&mo)[FILTER_ROUNDS])
+{
+#pragma unroll
+    for (int k = 0; k < FILTER_ROUNDS; ++k) {
+        const uint64_t i = lbase + (uint64_t)k * 2 * WAVE;
+        me[k] = __ballot(i < n);
+        mo[k] = __ballot(i + 1 < n);
+    }
+}
+
+// One column's values of a wave's eight rounds, read directly or through a row-id vector: v0[k] / v1[k] the even / odd row of
+// lane's pair in round k.  fast: 16-byte loads of the scanned vector, the wave's 1024 rows in bounds; otherwise a row whose bit
+// in me / mo is clear (out of bounds, or dropped by an earlier term) reads row 0 in its place (n >= 1), and the caller keeps
+// its comparison out of the masks.  Every branch is wave-uniform and outside the rounds, so that the eight (sixteen) loads are
+// in flight together.
+__device__ __forceinline__ void fbatch_side(fb_gcu64 col, fb_gcu64 sel, bool fast, uint64_t lbase, uint32_t lane, const uint64_t (&me)[FILTER_ROUNDS],
+                                            const uint64_t (&mo)[FILTER_ROUNDS], uint64_t (&v0)[FILTER_ROUNDS], uint64_t (&v1)[FILTER_ROUNDS])
+{
+    if (fast) {
+        if (sel) {
+            fb_u64x2 x[FILTER_ROUNDS];
+#pragma unroll
+            for (int k = 0; k < FILTER_ROUNDS; ++k) x[k] = *(fb_gcu64x2)(sel + lbase + (uint64_t)k * 2 * WAVE);
+#pragma unroll
+            for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = col[x[k].x]; v1[k] = col[x[k].y]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < FILTER_ROUNDS; ++k) {
+                const fb_u64x2 x = *(fb_gcu64x2)(col + lbase + (uint64_t)k * 2 * WAVE);
+                v0[k] = x.x; v1[k] = x.y;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < FILTER_ROUNDS; ++k) {
+            const uint64_t i = lbase + (uint64_t)k * 2 * WAVE;
+            v0[k] = (me[k] >> lane) & 1 ? i : 0;
+            v1[k] = (mo[k] >> lane) & 1 ? i + 1 : 0;
+        }
+        if (sel) {
+#pragma unroll
+            for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = sel[v0[k]]; v1[k] = sel[v1[k]]; }
+        }
+#pragma unroll
+        for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = col[v0[k]]; v1[k] = col[v1[k]]; }
+    }
+}
+
+// The end of every mask kernel, in k_filter_mask's layout: fbatch_mask_round stores the two mask words of round k and returns
+// their hits, fbatch_mask_count sums the four waves' hits into the tile's count.
+__device__ __forceinline__ uint32_t fbatch_mask_round(uint64_t n, uint64_t wbase, uint32_t lane, int k, uint64_t me, uint64_t mo, fb_gu64 masks)
+{
+    if (lane == 0 && wbase + (uint64_t)k * 2 * WAVE < n) {
+        masks[(wbase >> 6) + 2 * k] = me;
+        masks[(wbase >> 6) + 2 * k + 1] = mo;
+    }
+    return (uint32_t)__popcll(me) + (uint32_t)__popcll(mo);
+}
+
+__device__ __forceinline__ void fbatch_mask_count(uint32_t cnt, uint32_t lane, uint32_t w, uint32_t tile, fb_gu64 tile_count)
 {
     __shared__ uint32_t wsum[4];
+    if (lane == 0) wsum[w] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_count[tile] = (uint64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(256) void k_fbatch_mask(const FBatchDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t nf)
+{
     const uint32_t j = fbatch_find(tile_start, nf, blockIdx.x);
     const FBatchDesc &d = descs[j];
     const uint32_t tile = blockIdx.x - tile_start[j];
@@ -71,12 +144,7 @@ __global__ __launch_bounds__(256) void k_fbatch_mask(const FBatchDesc *__restric
     const uint64_t lbase = wbase + 2 * lane;                     // this lane's first element of round 0
     const bool fast = d.vec && wbase + FILTER_WAVE_ELEMS <= n;   // 16-byte loads, whole wave range in bounds
     uint64_t me[FILTER_ROUNDS], mo[FILTER_ROUNDS];               // wave-uniform: the rows in bounds, then those every term so far holds on
-#pragma unroll
-    for (int k = 0; k < FILTER_ROUNDS; ++k) {
-        const uint64_t i = lbase + (uint64_t)k * 2 * WAVE;
-        me[k] = __ballot(i < n);
-        mo[k] = __ballot(i + 1 < n);
-    }
+    fbatch_bounds(n, lbase, me, mo);
     for (int t = 0; t < nterms; ++t) {
         uint64_t live = 0;
 #pragma unroll
@@ -85,37 +153,8 @@ __global__ __launch_bounds__(256) void k_fbatch_mask(const FBatchDesc *__restric
         const fb_gcu64 col = (fb_gcu64)d.t[t].col;
         const uint64_t value = d.t[t].value;
         const int op = d.t[t].op;
-        // every branch below is wave-uniform and outside the rounds, so that a term's eight (sixteen) loads are in flight together
         uint64_t v0[FILTER_ROUNDS], v1[FILTER_ROUNDS];
-        if (fast) {
-            if (sel) {
-                fb_u64x2 x[FILTER_ROUNDS];
-#pragma unroll
-                for (int k = 0; k < FILTER_ROUNDS; ++k) x[k] = *(fb_gcu64x2)(sel + lbase + (uint64_t)k * 2 * WAVE);
-#pragma unroll
-                for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = col[x[k].x]; v1[k] = col[x[k].y]; }
-            } else {
-#pragma unroll
-                for (int k = 0; k < FILTER_ROUNDS; ++k) {
-                    const fb_u64x2 x = *(fb_gcu64x2)(col + lbase + (uint64_t)k * 2 * WAVE);
-                    v0[k] = x.x; v1[k] = x.y;
-                }
-            }
-        } else {
-            // a row out of bounds, or one an earlier term dropped, reads row 0 in its place (n >= 1; its mask bit is 0 already)
-#pragma unroll
-            for (int k = 0; k < FILTER_ROUNDS; ++k) {
-                const uint64_t i = lbase + (uint64_t)k * 2 * WAVE;
-                v0[k] = (me[k] >> lane) & 1 ? i : 0;
-                v1[k] = (mo[k] >> lane) & 1 ? i + 1 : 0;
-            }
-            if (sel) {
-#pragma unroll
-                for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = sel[v0[k]]; v1[k] = sel[v1[k]]; }
-            }
-#pragma unroll
-            for (int k = 0; k < FILTER_ROUNDS; ++k) { v0[k] = col[v0[k]]; v1[k] = col[v1[k]]; }
-        }
+        fbatch_side(col, sel, fast, lbase, lane, me, mo, v0, v1);
         if (op == 0) {
 #pragma unroll
             for (int k = 0; k < FILTER_ROUNDS; ++k) { me[k] &= __ballot(v0[k] < value); mo[k] &= __ballot(v1[k] < value); }
@@ -129,21 +168,15 @@ __global__ __launch_bounds__(256) void k_fbatch_mask(const FBatchDesc *__restric
     }
     uint32_t cnt = 0;
 #pragma unroll
-    for (int k = 0; k < FILTER_ROUNDS; ++k) {
-        if (lane == 0 && wbase + (uint64_t)k * 2 * WAVE < n) {
-            masks[(wbase >> 6) + 2 * k] = me[k];
-            masks[(wbase >> 6) + 2 * k + 1] = mo[k];
-        }
-        cnt += (uint32_t)__popcll(me[k]) + (uint32_t)__popcll(mo[k]);
-    }
-    if (lane == 0) wsum[w] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[tile] = (uint64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    for (int k = 0; k < FILTER_ROUNDS; ++k) cnt += fbatch_mask_round(n, wbase, lane, k, me[k], mo[k], masks);
+    fbatch_mask_count(cnt, lane, w, tile, tile_count);
 }
 
-// A filter with an output has one task per pair of tiles, as in k_filter_write; a count-only filter has ONE task, whose wave
-// sums the filter's tile counts and writes nothing but the total.
-__global__ __launch_bounds__(256) void k_fbatch_write(const FBatchDesc *__restrict__ descs, const uint32_t *__restrict__ task_start, uint32_t nf)
+// The write pass of a batch, over either descriptor type (it reads n, out, masks, tile_count and h_total).  An item with an
+// output has one task per pair of tiles, as in k_filter_write; a count-only item has ONE task, whose wave sums the item's tile
+// counts and writes nothing but the total.
+template <class D>
+__device__ __forceinline__ void fbatch_write_tasks(const D *descs, const uint32_t *task_start, uint32_t nf)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t ntasks_all = task_start[nf];
@@ -151,7 +184,7 @@ __global__ __launch_bounds__(256) void k_fbatch_write(const FBatchDesc *__restri
     const uint64_t lt = lanemask_lt();
     for (uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (256 / WAVE) + (threadIdx.x >> 6))); x < ntasks_all; x += stride) {
         const uint32_t j = fbatch_find(task_start, nf, x);
-        const FBatchDesc &d = descs[j];
+        const D &d = descs[j];
         const uint64_t n = d.n;
         const uint64_t ntiles = (n + FILTER_TILE - 1) / FILTER_TILE;
         if (d.out == nullptr) {
@@ -164,6 +197,11 @@ __global__ __launch_bounds__(256) void k_fbatch_write(const FBatchDesc *__restri
         }
         filter_write_task<true>(n, ntiles, (ntiles + 1) / 2, x - task_start[j], d.masks, d.tile_count, d.out, d.h_total, lane, lt);
     }
+}
+
+__global__ __launch_bounds__(256) void k_fbatch_write(const FBatchDesc *__restrict__ descs, const uint32_t *__restrict__ task_start, uint32_t nf)
+{
+    fbatch_write_tasks(descs, task_start, nf);
 }
 
 }  // namespace rhj
