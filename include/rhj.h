@@ -184,6 +184,16 @@ int  rhj_last_spec(void);
  * rhj_last_exact(): the last join — 0 not launched, 1 it did the join, 2 it handed over. */
 void rhj_set_exact(int on);
 int  rhj_last_exact(void);
+/* rhj_last_walk_units(): how many units of the last join the fused kernel left to k_join_walk (csrc/rhj_join_fused.hip.h: a tuple
+ * with more than 16 matches, a full overflow buffer or patch list, ...) — for tests that must know which kernel wrote a unit's
+ * pairs.  The small path and the batched joins (the sum over the batch's joins) have the number on the host anyway; the
+ * two-pass fused path has it when the speculation was tried, and always after rhj_set_walk_count(1) (default 0), which makes
+ * that join's 32-byte read-back of its ticket words unconditional and changes nothing else.  -1: the last join did not fetch
+ * the number (another path, a count-only call, the knob off, a batch that failed).  With several devices (rhj_set_devices) the
+ * knob goes to every device's context like the other switches; the getter speaks of the library's own device, and
+ * rhj_join_devices' other devices' numbers are not added to it. */
+void    rhj_set_walk_count(int on);
+int64_t rhj_last_walk_units(void);
 
 /* ---- several GPUs of one node behind this interface (SURVEY.md 8b "RHJ_DEVICES", 8e; rhjoin.c:42-57: bucket b of R only meets
  * bucket b of S, so contiguous bucket ranges are independent joins and their pair lists, concatenated in range order, ARE the

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "RadixHashJoin", "Filter", "InsertResult", "InsertRowIdResult", "GetResultNum", "FindResultRowId",
     "FindResultTuples", "FreeResult", "PrintResult", "FreeRelation", "SchedulerInit", "SchedulerDestroy",
     "rhj_set_radix_bits", "rhj_get_radix_bits", "rhj_set_empty_mode", "rhj_set_node_pairs", "rhj_set_device", "rhj_get_device",
-    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_cols_batch_device", "rhj_join_cols_device", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device", "rhj_filter_batch_device", "rhj_filter_batch_takes",
+    "rhj_set_stream", "rhj_set_force_hbm_table", "rhj_set_fused", "rhj_set_resident", "rhj_set_small", "rhj_set_lowradix", "rhj_set_count_in_pass1", "rhj_set_spec", "rhj_last_spec", "rhj_set_exact", "rhj_last_exact", "rhj_set_walk_count", "rhj_last_walk_units", "rhj_set_devices", "rhj_get_devices", "rhj_device_range", "rhj_set_devices_balance", "rhj_plan_device_ranges", "rhj_plan_device_slices", "rhj_cut_to_slice", "rhj_join_devices", "rhj_gather_pairs_devices", "rhj_set_order", "rhj_get_order", "rhj_auto_radix_bits", "rhj_sub_bits", "rhj_set_timing", "rhj_join_device", "rhj_join_batch_device", "rhj_batch_takes", "rhj_join_cols_batch_device", "rhj_join_cols_device", "rhj_join_keys_device", "rhj_partition_device", "rhj_filter_device", "rhj_filter_batch_device", "rhj_filter_batch_takes",
     "rhj_register_relation_map", "rhj_unregister_relation_map", "rhj_registered_columns", "rhj_pinned_ranges",
     "rhj_bucket_histogram_device", "rhj_select_bucket_range_device", "rhj_join_device_range", "rhj_join_device_slice", "rhj_pin_refusals",
     "rhj_release", "rhj_last_stats", "rhj_version",
@@ -234,6 +234,8 @@ def load_library(path=None):
     L.rhj_set_count_in_pass1.argtypes = [C.c_int]
     L.rhj_set_spec.argtypes = [C.c_int]
     L.rhj_last_spec.restype = C.c_int
+    L.rhj_set_walk_count.argtypes = [C.c_int]
+    L.rhj_last_walk_units.restype = C.c_int64
     if hasattr(L, "rhj_last_exact"):              # (A/B runs load earlier builds through this module too)
         L.rhj_last_exact.restype = C.c_int
     if hasattr(L, "rhj_set_devices"):

@@ -118,6 +118,8 @@ struct Ctx {
     int         exact_score = 2;     // > 0: launch it where it applies (a join it did adds 1, up to 4; one it handed back for its input takes 2 off)
     int         exact_skipped = 0;   // eligible joins not given to it since the score went to zero: every 16th tries again
     int         last_exact = 0;      // the last join: 0 not launched, 1 k_join_exact did the join, 2 it handed over (rhj_last_exact)
+    int         walk_count = 0;      // 1: the two-pass fused path reads the ticket words back after every join (rhj_set_walk_count; tests)
+    int64_t     last_walk_units = -1;    // the last join or batch: units k_join_walk took, -1 where the number was not fetched (rhj_last_walk_units)
     int         msd = 0;             // RHJ_MSD=1: pass 1 of the two-pass partition takes the HIGH bits of the radix, pass 2 the low ones (A/B)
     int         lo_override = 0;     // RHJ_LO_BITS: pass-1 digit bits of the two-pass partition (experiments; default bits / 2)
     int         seen_wide = 0;       // a join of this process needed 16-byte intermediates: launch those kernels from now on
@@ -553,6 +555,7 @@ static int begin_join(const JoinReq &q)
     st.ms_h2d = keep_h2d;
     st.n_r = q.nR; st.n_s = q.nS; st.radix_bits = q.bits;
     g.last_spec = g.last_exact = 0;                    // (only the fused path tries them: a join on another path says "not tried")
+    g.last_walk_units = -1;                            // (the small and fused paths, and a batch, leave the number)
     *q.matches = 0;
     if (q.ctx_out) *q.ctx_out = nullptr;
     return 0;
@@ -816,6 +819,7 @@ static int join_small(const JoinReq &q, JoinSetup &s)
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
         plan = g.pin->summary;                         // written by the join kernel's last workgroup (system-scope stores)
+        g.last_walk_units = plan.fused_ok && out ? (int64_t)g.pin->walk_units : -1;   // (what the launch below is decided by)
         if (plan.fused_ok && out && g.pin->walk_units != 0) {
             // some unit's pairs need the index walked again (a probe tuple with more than 16 matches, ...): the host is
             // waiting on this stream anyway, so the second kernel is launched only now — a launch that returns at once
@@ -927,10 +931,12 @@ static int join_fused(const JoinReq &q, JoinSetup &s)
         RHJ_LAUNCH(k_join_walk, dim3(fgrid), dim3(FJ_BLOCK), FUSED_LDS, g.stream, fa, FUSED_LDS);   // returns at once when no unit needs it
         RHJ_STAGE(ST_END);
         HIP_TRY(hipMemcpyAsync(&g.pin->summary, g.summary.p, sizeof(PlanSummary), hipMemcpyDeviceToHost, g.stream));
-        if (try_spec) HIP_TRY(hipMemcpyAsync(g.pin->ticket, g.status.p, sizeof(g.pin->ticket), hipMemcpyDeviceToHost, g.stream));
+        const bool fetch_ticket = try_spec || g.walk_count;   // (rhj_set_walk_count(1): word 2, the walk list's length, for the tests)
+        if (fetch_ticket) HIP_TRY(hipMemcpyAsync(g.pin->ticket, g.status.p, sizeof(g.pin->ticket), hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g.stream));
         plan = g.pin->summary;
+        g.last_walk_units = fetch_ticket && plan.fused_ok && out ? (int64_t)g.pin->ticket[2] : -1;
         g.last_spec = 0;
         g.last_exact = 0;
         if (try_spec) {
@@ -1458,7 +1464,8 @@ template <class D> constexpr bool batch_cols = std::is_same<D, rhj_join_cols_des
 
 // One chunk: items[lo, hi).  Joins whose plan refused the fused path are appended to `alone`.
 template <class D>
-static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo, size_t hi, std::vector<uint64_t> &alone, uint64_t &units)
+static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo, size_t hi, std::vector<uint64_t> &alone, uint64_t &units,
+                       int64_t &walked_units)
 {
     const size_t n = hi - lo;
     if (batch_arena(g.batch_arena, items[hi - 1].L.end)) return -1;
@@ -1533,6 +1540,7 @@ static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo,
         PlanSummary plan;
         memcpy(&plan, slots + k * BATCH_SLOT_WORDS, sizeof(plan));    // written by the join's last workgroup out (system-scope stores)
         const uint64_t walk_units = slots[k * BATCH_SLOT_WORDS + sizeof(PlanSummary) / 8];
+        if (plan.fused_ok && q.d_out) walked_units += (int64_t)walk_units;
         if (!plan.fused_ok) { alone.push_back(items[lo + k].idx); continue; }   // a bucket's build side beyond the LDS index
         if (plan.matches == FJ_NO_TOTAL) { fprintf(stderr, "rhj: batched join %zu left no match total (chained scan incomplete)\n", (size_t)items[lo + k].idx); return -1; }
         if (q.d_out && walk_units != 0) {
@@ -1555,12 +1563,15 @@ static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo,
 template <class D>
 static int join_batch(D *joins, uint64_t n)
 {
+    g.last_walk_units = -1;                                            // (a batch that fails leaves no earlier join's number behind)
     if (n == 0) return 0;
     bool timed = false;
     if (const int rc = batch_open(joins, n, [](D &q) { q.matches = 0; q.rc = 0; q.path = 0; return batch_valid(q); }, timed)) return rc;
     std::vector<BatchItem> items;
     std::vector<uint64_t> alone;
     uint64_t sum_r = 0, sum_s = 0, sum_m = 0, units = 0;
+    int64_t walked_units = 0;                                          // rhj_last_walk_units: the sum over the batch's joins
+    bool walked_known = true;
     for (uint64_t i = 0; i < n; ++i) {
         const D &q = joins[i];
         sum_r += q.nR; sum_s += q.nS;
@@ -1581,7 +1592,7 @@ static int join_batch(D *joins, uint64_t n)
             at = L.end;
             ++hi;
         }
-        if (batch_chunk(joins, items, lo, hi, alone, units)) return -1;
+        if (batch_chunk(joins, items, lo, hi, alone, units, walked_units)) return -1;
         lo = hi;
     }
     // the joins that run alone, through the single-join code (which keeps its own stats: summed up below); relations given by
@@ -1598,7 +1609,9 @@ static int join_batch(D *joins, uint64_t n)
         q.matches = m; q.rc = rc == 1 && !q.d_out ? 0 : rc; q.path = g.stats.reserved & 0xff;
         if (rc < 0) return rc;
         units += g.stats.units;
+        if (g.last_walk_units < 0) walked_known = false; else walked_units += g.last_walk_units;
     }
+    g.last_walk_units = walked_known ? walked_units : -1;
     int any_short = 0;
     for (uint64_t i = 0; i < n; ++i) { sum_m += joins[i].matches; any_short |= joins[i].rc == 1; }
     rhj_stats st = {};
@@ -2382,6 +2395,7 @@ static void adopt_knobs(Ctx &d, const Ctx &s)
     d.bits = s.bits; d.null_on_empty = s.null_on_empty; d.force_hbm = s.force_hbm; d.order_any = s.order_any;
     d.no_fused = s.no_fused; d.force_fused = s.force_fused; d.no_resident = s.no_resident; d.wide_row_ids = s.wide_row_ids;
     d.timing = s.timing; d.no_count_in_pass1 = s.no_count_in_pass1; d.no_spec = s.no_spec; d.no_exact = s.no_exact;
+    d.walk_count = s.walk_count;
     d.lo_override = s.lo_override; d.msd = s.msd; d.no_lowradix = s.no_lowradix; d.no_small = s.no_small; d.small_tiles = s.small_tiles;
     d.node_pairs = s.node_pairs;
 }
@@ -2462,6 +2476,8 @@ void rhj_set_spec(int on) { g.no_spec = !on; g.spec_score = 2; g.spec_skipped = 
 int rhj_last_spec(void) { return g.last_spec; }
 void rhj_set_exact(int on) { g.no_exact = !on; g.exact_score = 2; g.exact_skipped = 0; }
 int rhj_last_exact(void) { return g.last_exact; }
+void rhj_set_walk_count(int on) { g.walk_count = on != 0; }
+int64_t rhj_last_walk_units(void) { return g.last_walk_units; }
 void rhj_set_count_in_pass1(int on) { g.no_count_in_pass1 = !on; }
 void rhj_set_order(int any) { g.order_any = any != 0; }
 int rhj_auto_radix_bits(uint64_t nR, uint64_t nS) { return auto_radix_bits(nR, nS); }

@@ -976,7 +976,9 @@ __device__ __forceinline__ void fj_emit_res(const FusedArgs &f, const IX &X, con
 // group's total goes into the chained scan of the unit's groups (fj_group_lookback), the first matches leave from the
 // registers and the records are read back 64 at a time, each pair to its tuple's offset + ordinal.  Returns the lane's matches.
 // The candidate walk of one group: c = matches per tuple, first = the first match's build row id, the records of the others in
-// rec[0 .. returned count) (at most FJ_REC_CAP are stored; `cannot`: more than that, or an ordinal beyond eight bits).
+// rec[0 .. returned count) (at most FJ_REC_CAP are stored; `cannot`: more than that, or an ordinal beyond sixteen bits — the
+// record's second word is tuple | ordinal << 8: the tuple's place in the group takes the low eight bits, fj_emit_records reads
+// the ordinal at r.z >> 8, and a tuple's 65 536th match, cc >= 65535, gives up).
 template <bool N32, class IX>
 __device__ __forceinline__ uint32_t fj_walk_group(const IX &X, const FjGather<N32> &G, const uint4 (&q)[FJ_V], const bool (&okk)[FJ_V],
                                                   uint4 *rec, uint32_t (&c)[FJ_V], uint32_t (&first)[FJ_V], bool &cannot)

@@ -16,6 +16,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from source_constants import c_int as _c_int, one as _one
+
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sigmod-2018_amd", "csrc")
 SOURCES = ("rhj_join_fused.hip.h", "rhj_join_tiled.hip.h", "rhj_device.hip")      # in include order
 
@@ -23,21 +25,6 @@ SOURCES = ("rhj_join_fused.hip.h", "rhj_join_tiled.hip.h", "rhj_device.hip")    
 def _read(name):
     with open(os.path.join(CSRC, name)) as f:
         return f.read()
-
-
-def _c_int(expr, names):
-    """A C constant expression of unsigned integers (+ - * / parentheses, names defined before) as Python computes it."""
-    e = re.sub(r"\b(\d+)[uU]?[lL]{0,2}\b", r"\1", expr.strip())
-    if not re.fullmatch(r"[\w\s+\-*/()]+", e):
-        raise ValueError("not an integer constant expression: %r" % expr)
-    return int(eval(e.replace("/", "//"), {"__builtins__": {}}, dict(names)))
-
-
-def _one(pattern, text, what):
-    m = re.search(pattern, text)
-    if not m:
-        raise AssertionError("tests/tiled_model.py no longer finds %s in the sources" % what)
-    return m
 
 
 Constants = namedtuple("Constants", "LDS_BUDGET FJ_LDS_EXTRA FUSED_LDS LDS_MAX_SLOTS FUSED_LDS_CAP BUILD_CHUNK PR_UNIT T32_PAD "
