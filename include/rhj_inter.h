@@ -246,6 +246,35 @@ int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relatio
 typedef struct rhj_query_batch_info { uint32_t levels, filter_calls, eq2_calls, join_calls, join_reruns, apply_calls; } rhj_query_batch_info;
 const rhj_query_batch_info *rhj_query_batch_last_info(void);
 
+/* The statistics of many columns in one call (csrc/rhj_stats_batch.hip.h): what InitRelationMap needs for every column of every
+ * relation, and what a caller of rhj_query_batch_device needs for its own optimiser.  Every column gets, bit for bit, what
+ * rhj_column_stats_device returns (relation_map.c:53-84): l the minimum and u the maximum, compared unsigned; d the number of
+ * distinct v - l when u - l + 1 < 50 000 000, else the number of distinct (v - l) % 5 000 000 (the wrapped full range too).
+ * Every column of at least one row goes through the batched launches (path 11), three launches and two stream
+ * synchronisations per chunk of at most 4096 columns, 2^24 tiles of 2048 rows and 256 MiB of flag bitmaps (one bit a flag;
+ * the widest column needs 6.25 MB), in call order; columns whose bitmaps did not fit their chunk's arena keep their extremes
+ * and are marked and counted in a following chunk of two launches and one synchronisation.  Columns may be shared between
+ * items and the same column may appear twice; a column needs 8-byte alignment and no more.  n == 0: l = u = 0, d = 0, rc 0,
+ * path 0, nothing launched; a batch of 0 columns returns 0 without touching a device.
+ *
+ * The whole batch is validated before anything is launched: a NULL column with n > 0, or n above 2^35, gives that item rc -3;
+ * then nothing runs, no l, u or d is written and the call returns -3.  Otherwise 0, or a negative value on a HIP error.
+ * rhj_last_stats() afterwards: n_r the rows summed over the columns, units the columns launched, ms_total the whole call
+ * (timing level >= 1), reserved 11. */
+typedef struct rhj_colstats_desc {
+    const uint64_t *d_col; uint64_t n;   /* a device column, 8-byte aligned and no more (col + 1 is legal) */
+    uint64_t l, u;                       /* out: min, max */
+    double   d;                          /* out: the reference's distinct-value estimate */
+    int      rc;                         /* out */
+    int      path;                       /* out: 11 the batched launches, 0 nothing launched */
+} rhj_colstats_desc;
+int rhj_column_stats_batch_device(rhj_colstats_desc *cols, uint64_t n);
+/* flags the estimate of a column with these extremes counts over: u - l + 1 when that is below 50 000 000, else 5 000 000
+ * (also for l = 0, u = 2^64 - 1, whose u - l + 1 wraps to 0); 0 for l > u.  Pure function, needs no device. */
+uint64_t rhj_column_stats_flags(uint64_t l, uint64_t u);
+typedef struct rhj_colstats_batch_info { uint32_t chunks, columns; } rhj_colstats_batch_info;   /* of the last call: chunks run, columns that went through them */
+const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

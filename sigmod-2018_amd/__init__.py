@@ -40,6 +40,7 @@ INTER_SYMBOLS = [
     "rhj_filter_eq2_device", "rhj_resident_relation", "rhj_resident_result", "rhj_resident_inter",
     "InitRelationMap", "FreeRelationMap", "PrintRelationMap", "rhj_column_stats_device", "rhj_apply_batch_device",
     "rhj_filter_eq2_batch_device", "rhj_query_batch_device", "rhj_query_levels", "rhj_query_batch_last_info",
+    "rhj_column_stats_batch_device", "rhj_column_stats_flags", "rhj_column_stats_batch_last_info",
 ]
 
 
@@ -161,6 +162,20 @@ class QueryBatchInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ColStatsDesc(C.Structure):
+    """rhj_colstats_desc (include/rhj_inter.h): one column of rhj_column_stats_batch_device"""
+    _fields_ = [("d_col", C.c_void_p), ("n", C.c_uint64), ("l", C.c_uint64), ("u", C.c_uint64), ("d", C.c_double),
+                ("rc", C.c_int), ("path", C.c_int)]
+
+
+class ColStatsBatchInfo(C.Structure):
+    """rhj_colstats_batch_info (include/rhj_inter.h): what the last rhj_column_stats_batch_device ran"""
+    _fields_ = [("chunks", C.c_uint32), ("columns", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def query_descs(queries):
     """(QueryDesc array, what keeps its pointers alive) of queries = [(relations, joins, filters, views), ...]: relations the
     relation index of every binding, joins [(a, ca, b, cb)], filters [(a, ca, op, value)], views [(a, c)], a and b bindings."""
@@ -186,7 +201,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -282,6 +297,11 @@ def load_library(path=None):
         L.rhj_query_batch_device.argtypes = [C.POINTER(DeviceRelation), C.c_int, C.POINTER(QueryDesc), C.c_uint64]
         L.rhj_query_levels.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(C.c_int)]
         L.rhj_query_batch_last_info.restype = C.POINTER(QueryBatchInfo)
+    if hasattr(L, "rhj_column_stats_batch_device"):   # (A/B runs load earlier builds through this module too)
+        L.rhj_column_stats_batch_device.argtypes = [C.POINTER(ColStatsDesc), C.c_uint64]
+        L.rhj_column_stats_flags.argtypes = [C.c_uint64, C.c_uint64]
+        L.rhj_column_stats_flags.restype = C.c_uint64
+        L.rhj_column_stats_batch_last_info.restype = C.POINTER(ColStatsBatchInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -619,6 +639,25 @@ class RHJ:
         del keep_rels, keep
         res = [(list(arr[i].sums[:arr[i].nviews]), arr[i].rows) for i in range(len(queries))]
         return (res, self.lib.rhj_query_batch_last_info().contents.as_dict()) if with_info else res
+
+    def column_stats_batch_device(self, cols, with_info=False):
+        """The optimiser's statistics of many columns in one call (rhj_column_stats_batch_device, include/rhj_inter.h): cols
+        int64 tensors [n] (views such as col[1:] are fine; a column may be listed twice).  Returns [(l, u, d), ...]: minimum
+        and maximum as Python ints below 2^64 and the reference's distinct-value estimate as a float; (0, 0, 0.0) for an
+        empty column.  with_info: also the list of the columns' path ids (11: the batched launches, 0: an empty column) and
+        rhj_column_stats_batch_last_info() as a dict."""
+        n = len(cols)
+        arr = (ColStatsDesc * max(n, 1))()
+        for d, col in zip(arr, cols):
+            d.n = col.shape[0]
+            d.d_col = col.data_ptr() if d.n else None
+        rc = self.lib.rhj_column_stats_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_column_stats_batch_device failed (%d)" % rc)
+        res = [(arr[i].l, arr[i].u, arr[i].d) for i in range(n)]
+        if with_info:
+            return res, [arr[i].path for i in range(n)], self.lib.rhj_column_stats_batch_last_info().contents.as_dict()
+        return res
 
     def pairs_to_numpy(self, t):
         a = t.cpu().numpy()

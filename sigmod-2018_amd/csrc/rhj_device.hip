@@ -78,7 +78,7 @@ enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSE
     X(partR) X(partS) X(tmpR) X(tmpS) X(cntR) X(cntS) X(chunk) X(histpsum) X(passhp) X(units) X(bunits) X(ldsb) X(meta)   \
     X(summary) X(ucount) X(ubase) X(uflag) X(tab32) X(tab64) X(stash_cnt) X(stash_row) X(status) X(dbg) X(bsum) X(digR)  \
     X(digS) X(ovf) X(ovf_base) X(runR) X(runS) X(walk) X(xrows) X(lr_tmp) X(lr_words) X(lr_status) X(stripR) X(stripS)   \
-    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc) X(fbatch_arena)                      \
+    X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc) X(fbatch_arena) X(stats_arena)      \
     X(inR) X(inS) X(out) X(fcol_sel) X(fmask) X(ftile) X(fbase) X(fout)                                                    \
     X(fcol)                                                      /* staging of an unregistered column (host Filter()) */
 
@@ -2042,6 +2042,188 @@ static int apply_batch(rhj_apply_desc *items, uint64_t n)
     return batch_close(timed, st);
 }
 
+// ---- batched column statistics (rhj_stats_batch.hip.h) ---------------------------------------------------------------------
+// rhj_column_stats_batch_device: every column of at least one row runs in the launches of its chunk (path 11); there is no
+// run-alone class.  A chunk holds at most STATS_MAX_COLUMNS columns and STATS_MAX_TILES tiles (conditions, as the apply
+// batch's) and STATS_ARENA_BYTES of bitmaps (the widest column's is 6.25 MB), and a batch beyond any of them is cut in call
+// order.  How many bitmap bytes a column needs is known only after pass 1, so stats_pass1 runs k_statsbatch_minmax over the
+// columns the first two limits admit, and stats_chunk then marks and counts them in runs that fit the arena: the first run
+// is the chunk that pass 1 belongs to (three launches, two stream waits), and the columns that did not fit keep their
+// extremes and make up the following chunks (two launches, one wait each).  The uploaded block is
+//   [3 words a column: ~0, 0, 0][descriptors][columns + 1 row-tile starts][columns + 1 word-tile starts]
+// in g.batch_desc; the descriptors and both arrays of tile starts are uploaded once more with the placement of every run.
+constexpr size_t STATS_MAX_COLUMNS = 4096;
+constexpr uint64_t STATS_MAX_TILES = 1ull << 24;
+constexpr uint64_t STATS_MAX_ROWS = STATS_MAX_TILES * STATS_TILE;       // 2^35
+constexpr size_t STATS_ARENA_BYTES = 256ull * 1024 * 1024;
+
+rhj_colstats_batch_info g_stats_info = {};
+
+static uint64_t stats_flags(uint64_t l, uint64_t u)
+{
+    if (l > u) return 0;
+    const uint64_t size = u - l + 1;                      // 0: the full range, wrapped
+    return size == 0 || size >= STATS_CAP ? STATS_FOLD : size;
+}
+
+static inline size_t stats_bitmap_bytes(uint64_t flags) { return (size_t)((flags + 31) / 32) * 4; }
+
+// the arena grows to what a chunk needs, at least doubling, and never beyond STATS_ARENA_BYTES
+static int stats_arena(size_t bytes)
+{
+    Buf &b = g.stats_arena;
+    if (bytes <= b.cap) return 0;
+    size_t want = 2 * b.cap > bytes ? 2 * b.cap : bytes;
+    if (want > STATS_ARENA_BYTES) want = STATS_ARENA_BYTES;
+    if (b.p) HIP_TRY(hipFree(b.p));
+    b.p = nullptr; b.cap = 0;
+    HIP_TRY(hipMalloc(&b.p, want));
+    b.cap = want;
+    return 0;
+}
+
+struct StatsBlock {                                       // where the parts of a pass-1 group's block lie, host and device side
+    size_t              nc, words_bytes, desc_bytes, start_bytes;
+    unsigned long long *back;                             // pinned: what is read back (3 words a column)
+    char               *up;                               // pinned: what is uploaded
+    StatsDesc *hd() const { return (StatsDesc *)(up + words_bytes); }
+    uint32_t *tile_start() const { return (uint32_t *)(up + words_bytes + desc_bytes); }
+    uint32_t *wtile_start() const { return (uint32_t *)(up + words_bytes + desc_bytes + start_bytes); }
+    unsigned long long *d_words() const { return (unsigned long long *)g.batch_desc.p; }
+    const StatsDesc *dd() const { return (const StatsDesc *)((const char *)g.batch_desc.p + words_bytes); }
+    const uint32_t *d_tile_start() const { return (const uint32_t *)((const char *)g.batch_desc.p + words_bytes + desc_bytes); }
+    const uint32_t *d_wtile_start() const { return (const uint32_t *)((const char *)g.batch_desc.p + words_bytes + desc_bytes + start_bytes); }
+};
+
+// Pass 1 of cols[which[lo, hi)], every one valid and of at least one row: the extremes into the descriptors of the caller.
+static int stats_pass1(rhj_colstats_desc *cols, const std::vector<uint64_t> &which, size_t lo, size_t hi, StatsBlock &B)
+{
+    B.nc = hi - lo;
+    B.words_bytes = B.nc * 24; B.desc_bytes = B.nc * sizeof(StatsDesc); B.start_bytes = ((B.nc + 1) * 4 + 7) & ~(size_t)7;
+    const size_t up_bytes = B.words_bytes + B.desc_bytes + 2 * B.start_bytes;
+    if (batch_pinned(B.words_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
+    B.back = (unsigned long long *)g.batch_pin;
+    B.up = (char *)g.batch_pin + B.words_bytes;
+    unsigned long long *words = (unsigned long long *)B.up;
+    StatsDesc *hd = B.hd();
+    uint32_t *tile_start = B.tile_start();
+    uint32_t tiles = 0;
+    for (size_t k = 0; k < B.nc; ++k) {
+        const rhj_colstats_desc &q = cols[which[lo + k]];
+        words[3 * k] = ~0ull; words[3 * k + 1] = 0; words[3 * k + 2] = 0;
+        StatsDesc d;
+        memset((void *)&d, 0, sizeof(d));
+        d.col = q.d_col; d.n = q.n; d.words = B.d_words() + 3 * k;
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        tile_start[k] = tiles;
+        tiles += (uint32_t)((q.n + STATS_TILE - 1) / STATS_TILE);
+    }
+    tile_start[B.nc] = tiles;
+    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, B.up, B.words_bytes + B.desc_bytes + B.start_bytes, hipMemcpyHostToDevice, g.stream));
+    RHJ_LAUNCH(k_statsbatch_minmax, dim3(tiles), dim3(256), 0, g.stream, B.dd(), B.d_tile_start(), (uint32_t)B.nc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(B.back, B.d_words(), B.words_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < B.nc; ++k) {
+        rhj_colstats_desc &q = cols[which[lo + k]];
+        q.l = B.back[3 * k]; q.u = B.back[3 * k + 1];
+        if (q.l > q.u) { fprintf(stderr, "rhj: batched statistics column %zu left no extremes\n", (size_t)which[lo + k]); return -1; }
+    }
+    return 0;
+}
+
+// Passes 2 and 3 of columns [a, b) of the group pass 1 ran (their extremes are in the caller's descriptors, their bitmaps
+// fit the arena together): one chunk.
+static int stats_chunk(rhj_colstats_desc *cols, const std::vector<uint64_t> &which, size_t lo, const StatsBlock &B, size_t a, size_t b)
+{
+    StatsDesc *hd = B.hd();
+    uint32_t *tile_start = B.tile_start(), *wtile_start = B.wtile_start();      // of this run: both begin at 0
+    size_t at = 0;
+    for (size_t k = a; k < b; ++k) at += stats_bitmap_bytes(stats_flags(cols[which[lo + k]].l, cols[which[lo + k]].u));
+    if (stats_arena(at)) return -1;
+    at = 0;
+    uint32_t tiles = 0, wtiles = 0;
+    for (size_t k = a; k < b; ++k) {
+        const rhj_colstats_desc &q = cols[which[lo + k]];
+        const uint64_t flags = stats_flags(q.l, q.u);
+        StatsDesc d;
+        memcpy((void *)&d, (const void *)&hd[k], sizeof(d));
+        d.bits = (uint32_t *)((char *)g.stats_arena.p + at);
+        d.lo = q.l;
+        d.fold = q.u - q.l + 1 == flags ? 0 : (uint32_t)STATS_FOLD;
+        d.nwords = (uint32_t)((flags + 31) / 32);
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        at += stats_bitmap_bytes(flags);
+        tile_start[k - a] = tiles;
+        tiles += (uint32_t)((q.n + STATS_TILE - 1) / STATS_TILE);
+        wtile_start[k - a] = wtiles;
+        wtiles += (d.nwords + STATS_WORD_TILE - 1) / STATS_WORD_TILE;
+    }
+    tile_start[b - a] = tiles;
+    wtile_start[b - a] = wtiles;
+    const uint32_t nc = (uint32_t)(b - a);
+    // the placement: the descriptors, both arrays of tile starts (the columns' words stay as the device has them)
+    HIP_TRY(hipMemcpyAsync((char *)g.batch_desc.p + B.words_bytes, B.up + B.words_bytes, B.desc_bytes + 2 * B.start_bytes, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemsetAsync(g.stats_arena.p, 0, at, g.stream));
+    RHJ_LAUNCH(k_statsbatch_mark, dim3(tiles), dim3(256), 0, g.stream, B.dd() + a, B.d_tile_start(), nc);
+    RHJ_LAUNCH(k_statsbatch_count, dim3(wtiles), dim3(256), 0, g.stream, B.dd() + a, B.d_wtile_start(), nc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(B.back, B.d_words(), B.words_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = a; k < b; ++k) {
+        rhj_colstats_desc &q = cols[which[lo + k]];
+        q.d = (double)B.back[3 * k + 2];
+        q.path = 11;
+    }
+    ++g_stats_info.chunks;
+    g_stats_info.columns += nc;
+    return 0;
+}
+
+static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
+{
+    memset(&g_stats_info, 0, sizeof(g_stats_info));
+    if (n == 0) return 0;
+    bool timed = false;
+    const auto reset = [](rhj_colstats_desc &q) { q.rc = 0; q.path = 0; return q.n <= STATS_MAX_ROWS && (q.n == 0 || q.d_col); };
+    if (const int rc = batch_open(cols, n, reset, timed)) return rc;
+    std::vector<uint64_t> which;
+    uint64_t rows = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rows += cols[i].n;
+        if (cols[i].n) which.push_back(i);
+        else { cols[i].l = cols[i].u = 0; cols[i].d = 0; }   // an empty column: nothing to launch
+    }
+    for (size_t lo = 0; lo < which.size();) {
+        size_t hi = lo;
+        uint64_t tiles = 0;
+        while (hi < which.size() && hi - lo < STATS_MAX_COLUMNS) {
+            const uint64_t t = (cols[which[hi]].n + STATS_TILE - 1) / STATS_TILE;
+            if (tiles + t > STATS_MAX_TILES) break;       // (one column never has more: the validation)
+            tiles += t;
+            ++hi;
+        }
+        StatsBlock B;
+        if (stats_pass1(cols, which, lo, hi, B)) return -1;
+        for (size_t a = 0; a < B.nc;) {
+            size_t b = a, bytes = 0;
+            while (b < B.nc) {
+                const size_t mine = stats_bitmap_bytes(stats_flags(cols[which[lo + b]].l, cols[which[lo + b]].u));
+                if (bytes + mine > STATS_ARENA_BYTES) break;  // (one column alone always fits)
+                bytes += mine;
+                ++b;
+            }
+            if (stats_chunk(cols, which, lo, B, a, b)) return -1;
+            a = b;
+        }
+        lo = hi;
+    }
+    rhj_stats st = {};
+    st.n_r = rows; st.units = which.size();
+    st.reserved = 11;
+    return batch_close(timed, st);
+}
+
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
 // rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
 // equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
@@ -2870,6 +3052,15 @@ int rhj_filter_eq2_batch_device(rhj_eq2_desc *items, uint64_t n)
     RhjApiLock api_lock;
     return filter_batch(items, n);
 }
+
+/* The statistics of many columns in one call (include/rhj_inter.h; stats_batch above) */
+int rhj_column_stats_batch_device(rhj_colstats_desc *cols, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return stats_batch(cols, n);
+}
+uint64_t rhj_column_stats_flags(uint64_t l, uint64_t u) { return stats_flags(l, u); }
+const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void) { return &g_stats_info; }
 
 /* A batch of queries run level by level through the batched entry points (include/rhj_inter.h; query_batch above) */
 int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)

@@ -929,13 +929,28 @@ int InitRelationMap(rhj_relation_listnode *head, rhj_relation_map *rel_map)     
             // block of the file mapping, pinned for the copy), and the optimiser's statistics computed on it
             if (rhj_dev_register_column(rm.columns[c], rm.num_tuples, c == 0 ? (const void *)first : nullptr, rm.num_columns * rm.num_tuples * 8))
                 die("InitRelationMap");
-            rhj_column_stats *st = &rm.col_stats[c];
-            st->f = (double)rm.num_tuples;
-            if (rhj_column_stats_device(DevColumn(&rm, (int)c), rm.num_tuples, &st->l, &st->u, &st->d)) die("InitRelationMap");
+            rm.col_stats[c].f = (double)rm.num_tuples;
         }
         if (rm.num_tuples > most_rows) most_rows = rm.num_tuples;
         TRACE("InitRelationMap: relation %d loaded", loaded);
     }
+    // the optimiser's statistics of every column of every relation, computed on the device copies in ONE batched call
+    std::vector<rhj_colstats_desc> cols;
+    for (int r = 0; r < loaded; ++r)
+        for (uint64_t c = 0; c < rel_map[r].num_columns; ++c) {
+            rhj_colstats_desc q = {};
+            q.n = rel_map[r].num_tuples;
+            void *temp = nullptr;                        // (registered a moment ago: the device copy, never an upload)
+            if (q.n && ((q.d_col = rhj_dev_column(rel_map[r].columns[c], q.n, &temp)) == nullptr || temp)) die("InitRelationMap");
+            cols.push_back(q);
+        }
+    if (rhj_column_stats_batch_device(cols.data(), cols.size())) die("InitRelationMap");
+    size_t k = 0;
+    for (int r = 0; r < loaded; ++r)
+        for (uint64_t c = 0; c < rel_map[r].num_columns; ++c, ++k) {
+            rhj_column_stats *st = &rel_map[r].col_stats[c];
+            st->l = cols[k].l; st->u = cols[k].u; st->d = cols[k].d;
+        }
     if (most_rows) (void)rhj_dev_reserve(most_rows);    // the joins' workspace for inputs of the base relations' size
     return 0;
 }

@@ -42,6 +42,7 @@
 //                          workgroup finding its filter in the chunk's array of tile starts.
 //   rhj_eq2_batch.hip.h    many two-column equalities (colA[selA[i]] == colB[selB[i]]) in the same two launches.
 //   rhj_apply_batch.hip.h  many row-id rebuilds and view sums in one launch: an index list applied to up to 8 terms per item.
+//   rhj_stats_batch.hip.h  the statistics of many columns in three launches: min / max, one bit per flag, popcounts.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -61,4 +62,5 @@
 #include "rhj_filter_batch.hip.h"
 #include "rhj_eq2_batch.hip.h"
 #include "rhj_apply_batch.hip.h"
+#include "rhj_stats_batch.hip.h"
 #include "rhj_diag.hip.h"
