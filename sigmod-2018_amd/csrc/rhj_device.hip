@@ -7,6 +7,7 @@
 #include "rhj_kernels.hip.h"
 #include "rhj_shard_kernels.hip.h"
 #include "rhj_internal.h"
+#include "rhj_block.h"
 #include <mutex>
 #include <thread>
 #include <atomic>
@@ -130,8 +131,8 @@ struct Ctx {
     uint64_t    node_pairs = 65535;
     hipEvent_t  ev[ST_N + 1] = {};
     hipEvent_t  ev_x[4] = {};
-    hipEvent_t  ev_batch[2] = {};    // rhj_join_batch_device, rhj_filter_batch_device: the whole call (what they run alone records the stage events)
-    void       *batch_pin = nullptr; // the same two: pinned host block of a chunk's answers (summaries / hit totals) and of what is uploaded for it
+    hipEvent_t  ev_batch[2] = {};    // every batched entry point but the query batch: the whole call (what they run alone records the stage events)
+    void       *batch_pin = nullptr; // every batched entry point: pinned host block of a chunk's answers and of what is uploaded for it (rhj_block.h)
     size_t      batch_pin_cap = 0;
 #define RHJ_BUF(name) Buf name;
     RHJ_WORKSPACE(RHJ_BUF)
@@ -1353,6 +1354,9 @@ constexpr uint64_t BATCH_MAX_JOINS = 65535;               // grid y / z of one c
 constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join's slot in the pinned block: PlanSummary, walk count
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
+// what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11 };
+
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
     if (bits < 1 || bits > PT_MAX_BITS || nR == 0 || nS == 0) return 0;
@@ -1367,7 +1371,7 @@ struct BatchPlace {                                       // byte offsets of one
     uint32_t span;
 };
 
-static void batch_place(int bits, uint64_t nR, uint64_t nS, size_t at, BatchPlace &L)
+static size_t batch_place(int bits, uint64_t nR, uint64_t nS, size_t at, BatchPlace &L)
 {
     const uint32_t bins = 1u << bits;
     auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
@@ -1388,16 +1392,16 @@ static void batch_place(int bits, uint64_t nR, uint64_t nS, size_t at, BatchPlac
     L.ovf = take(fj_ovf_bytes(BJ_WGS));
     L.ovf_base = take((size_t)BJ_WGS * 2 * FJ_GROUPS * 16 * 4);
     L.walk = take((L.unit_bound + 1) * sizeof(FjWalkItem));
-    L.end = at;
+    return L.end = at;
 }
 
-// the arena grows to what a chunk needs, at least doubling, and never beyond the budget (ensure() adds slack of its own)
-static int batch_arena(Buf &b, size_t bytes)
+// an arena grows to what a chunk needs, at least doubling, and never beyond its budget (ensure() adds slack of its own)
+static int batch_arena(Buf &b, size_t bytes, size_t budget)
 {
     if (bytes <= b.cap) return 0;
     size_t want = 2 * b.cap > bytes ? 2 * b.cap : bytes;
-    if (want > BATCH_ARENA_BUDGET) want = BATCH_ARENA_BUDGET;
-    if (want < bytes) want = bytes;                       // (one join alone never needs more than a few MB)
+    if (want > budget) want = budget;
+    if (want < bytes) want = bytes;                       // (one item alone never needs more than a few MB)
     if (b.p) HIP_TRY(hipFree(b.p));
     b.p = nullptr; b.cap = 0;
     HIP_TRY(hipMalloc(&b.p, want));
@@ -1414,6 +1418,43 @@ static int batch_pinned(size_t bytes)
     g.batch_pin = nullptr; g.batch_pin_cap = 0;
     HIP_TRY(hipHostMalloc(&g.batch_pin, 2 * bytes, hipHostMallocDefault));
     g.batch_pin_cap = 2 * bytes;
+    return 0;
+}
+
+// a chunk's block (rhj_block.h): pieces(b) declares it, once for the sizes, then over the pinned side and g.batch_desc
+template <class Pieces>
+static int batch_block(Block &blk, Pieces pieces)
+{
+    Block sizes;
+    pieces(sizes);
+    if (batch_pinned(sizes.bytes()) || ensure(g.batch_desc, sizes.up_bytes())) return -1;
+    blk = Block(g.batch_pin, g.batch_desc.p);
+    pieces(blk);
+    return 0;
+}
+
+// one copy: the uploaded pieces whose host side is [first, end)
+static int batch_upload(const Block &blk, const void *first, const void *end)
+{
+    HIP_TRY(hipMemcpyAsync(blk.mirror(first), first, (size_t)((const char *)end - (const char *)first), hipMemcpyHostToDevice, g.stream));
+    return 0;
+}
+
+// Cuts items [0, n) into chunks [lo, hi) in call order and runs them.  use(i, used) is what a chunk that uses `used` so far uses
+// once item i has joined it (0: an empty chunk); a chunk takes its first item whatever that uses, then at most max_count - 1
+// more, each only if the chunk stays within `limit` with it.  run(lo, hi, used) runs a chunk.
+template <class Use, class Run>
+static int batch_cut(size_t n, size_t max_count, uint64_t limit, Use use, Run run)
+{
+    for (size_t lo = 0, hi; lo < n; lo = hi) {
+        uint64_t used = use(lo, 0);
+        for (hi = lo + 1; hi < n && hi - lo < max_count; ++hi) {
+            const uint64_t next = use(hi, used);
+            if (next > limit) break;
+            used = next;
+        }
+        if (run(lo, hi, used)) return -1;
+    }
     return 0;
 }
 
@@ -1468,16 +1509,12 @@ static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo,
                        int64_t &walked_units)
 {
     const size_t n = hi - lo;
-    if (batch_arena(g.batch_arena, items[hi - 1].L.end)) return -1;
-    // pinned block: [n summary slots][n descriptors][3 lists of n join numbers]; descriptors and lists are uploaded in one copy
-    const size_t slots_bytes = n * BATCH_SLOT_WORDS * 8, desc_bytes = n * sizeof(BatchJoin), up_bytes = desc_bytes + 3 * n * 4;
-    if (batch_pinned(slots_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    uint64_t *slots = (uint64_t *)g.batch_pin;
-    BatchJoin *hd = (BatchJoin *)((char *)g.batch_pin + slots_bytes);
-    uint32_t *hl = (uint32_t *)((char *)hd + desc_bytes);             // [0, n) histogram, [n, 2n) resident, [2n, 3n) gathering
-    const BatchJoin *dd = (const BatchJoin *)g.batch_desc.p;
-    const uint32_t *dl = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes);
-    memset(slots, 0xff, slots_bytes);                                 // (a slot nobody wrote reads as "no match total": an error, not an answer)
+    if (batch_arena(g.batch_arena, items[hi - 1].L.end, BATCH_ARENA_BUDGET)) return -1;
+    // the block: [n summary slots] read back; [n descriptors][3 lists of n join numbers] uploaded in one copy
+    Block blk;
+    uint64_t *slots; BatchJoin *hd, *dd; uint32_t *hl, *dl;           // hl: [0, n) histogram, [n, 2n) resident, [2n, 3n) gathering
+    if (batch_block(blk, [&](Block &b) { b.back(slots, n * BATCH_SLOT_WORDS); b.up(hd, dd, n); b.up(hl, dl, 3 * n); })) return -1;
+    memset(slots, 0xff, n * BATCH_SLOT_WORDS * 8);                    // (a slot nobody wrote reads as "no match total": an error, not an answer)
     char *A = (char *)g.batch_arena.p;
     uint32_t n_hist = 0, n_res = 0, n_gat = 0;
     int max_bits = 1;
@@ -1522,7 +1559,7 @@ static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo,
         if (it.bits > max_bits) max_bits = it.bits;
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
     }
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
     if constexpr (batch_cols<D>) {
         if (n_hist) RHJ_LAUNCH(k_batch_hist_cols, dim3(BJ_MAX_TILES, 2, n_hist), dim3(SM_BLOCK), 0, g.stream, dd, dl);
         RHJ_LAUNCH(k_batch_scatter_cols, dim3(BJ_MAX_TILES + 1, 2, (unsigned)n), dim3(SM_BLOCK), small_lds_bytes(max_bits), g.stream, dd);
@@ -1550,7 +1587,7 @@ static int batch_chunk(D *joins, const std::vector<BatchItem> &items, size_t lo,
         }
         q.matches = plan.matches;
         q.rc = q.d_out && plan.matches > q.out_capacity ? 1 : 0;
-        q.path = 6;
+        q.path = PATH_BATCH_JOIN;
         units += plan.units;
     }
     if (walked) {
@@ -1582,19 +1619,10 @@ static int join_batch(D *joins, uint64_t n)
         it.idx = i; it.bits = bits;
         items.push_back(it);
     }
-    for (size_t lo = 0; lo < items.size();) {
-        size_t hi = lo, at = 0;
-        while (hi < items.size() && hi - lo < BATCH_MAX_JOINS) {
-            BatchPlace L;
-            batch_place(items[hi].bits, joins[items[hi].idx].nR, joins[items[hi].idx].nS, at, L);
-            if (hi > lo && L.end > BATCH_ARENA_BUDGET) break;
-            items[hi].L = L;
-            at = L.end;
-            ++hi;
-        }
-        if (batch_chunk(joins, items, lo, hi, alone, units, walked_units)) return -1;
-        lo = hi;
-    }
+    // (a join that does not fit is placed again, first in the next chunk)
+    const auto place = [&](size_t k, uint64_t at) { return batch_place(items[k].bits, joins[items[k].idx].nR, joins[items[k].idx].nS, (size_t)at, items[k].L); };
+    if (batch_cut(items.size(), BATCH_MAX_JOINS, BATCH_ARENA_BUDGET, place,
+                  [&](size_t lo, size_t hi, uint64_t) { return batch_chunk(joins, items, lo, hi, alone, units, walked_units); })) return -1;
     // the joins that run alone, through the single-join code (which keeps its own stats: summed up below); relations given by
     // columns are materialised first
     for (const uint64_t i : alone) {
@@ -1616,7 +1644,7 @@ static int join_batch(D *joins, uint64_t n)
     for (uint64_t i = 0; i < n; ++i) { sum_m += joins[i].matches; any_short |= joins[i].rc == 1; }
     rhj_stats st = {};
     st.n_r = sum_r; st.n_s = sum_s; st.matches = sum_m; st.units = units; st.radix_bits = g.bits;
-    st.reserved = 6;
+    st.reserved = PATH_BATCH_JOIN;
     if (batch_close(timed, st)) return -1;
     return any_short;
 }
@@ -1744,6 +1772,14 @@ struct FBatchItem {
     size_t   masks, counts, end;                          // byte offsets in the arena
 };
 
+static size_t fbatch_place(uint64_t rows, size_t at, FBatchItem &it)
+{
+    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    it.masks = take(fbatch_mask_bytes(rows));
+    it.counts = take((size_t)((rows + FILTER_TILE - 1) / FILTER_TILE) * 8);
+    return it.end = at;
+}
+
 // What differs between the two: the device descriptor and how it is filled, the validity rule, the two kernels, the path id,
 // the noun of the error text, and how an item beyond FBATCH_MAX_ROWS runs alone.
 template <class D> using fbatch_dev = std::conditional_t<std::is_same<D, rhj_filter_desc>::value, FBatchDesc, Eq2BatchDesc>;
@@ -1778,8 +1814,8 @@ static bool fbatch_valid(const rhj_filter_desc &q)
 }
 static bool fbatch_valid(const rhj_eq2_desc &q) { return q.n == 0 || (q.d_colA && q.d_colB); }
 
-static inline int fbatch_path(const rhj_filter_desc &) { return 7; }
-static inline int fbatch_path(const rhj_eq2_desc &) { return 9; }
+static inline int fbatch_path(const rhj_filter_desc &) { return PATH_BATCH_FILTER; }
+static inline int fbatch_path(const rhj_eq2_desc &) { return PATH_BATCH_EQ2; }
 static inline const char *fbatch_noun(const rhj_filter_desc &) { return "filter"; }
 static inline const char *fbatch_noun(const rhj_eq2_desc &) { return "equality"; }
 
@@ -1800,16 +1836,12 @@ static int fbatch_chunk(D *qs, const std::vector<FBatchItem> &items, size_t lo, 
 {
     using Dev = fbatch_dev<D>;
     const size_t nf = hi - lo;
-    if (batch_arena(g.fbatch_arena, items[hi - 1].end)) return -1;
-    // pinned block: [nf hit totals][nf descriptors][nf + 1 tile starts][nf + 1 task starts]; all but the totals are uploaded in one copy
-    const size_t totals_bytes = nf * 8, desc_bytes = nf * sizeof(Dev), up_bytes = desc_bytes + 2 * (nf + 1) * 4;
-    if (batch_pinned(totals_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    uint64_t *totals = (uint64_t *)g.batch_pin;
-    Dev *hd = (Dev *)((char *)g.batch_pin + totals_bytes);
-    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes), *task_start = tile_start + nf + 1;
-    const Dev *dd = (const Dev *)g.batch_desc.p;
-    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes), *d_task_start = d_tile_start + nf + 1;
-    memset(totals, 0xff, totals_bytes);                   // (a slot nobody wrote reads as "no total": an error, not an answer)
+    if (batch_arena(g.fbatch_arena, items[hi - 1].end, BATCH_ARENA_BUDGET)) return -1;
+    // the block: [nf hit totals] read back; [nf descriptors][nf + 1 tile starts][nf + 1 task starts] uploaded in one copy
+    Block blk;
+    uint64_t *totals; Dev *hd, *dd; uint32_t *tile_start, *d_tile_start, *task_start, *d_task_start;
+    if (batch_block(blk, [&](Block &b) { b.back(totals, nf); b.up(hd, dd, nf); b.up(tile_start, d_tile_start, nf + 1); b.up(task_start, d_task_start, nf + 1); })) return -1;
+    memset(totals, 0xff, nf * 8);                         // (a slot nobody wrote reads as "no total": an error, not an answer)
     char *A = (char *)g.fbatch_arena.p;
     uint32_t tiles = 0, tasks = 0;
     for (size_t k = 0; k < nf; ++k) {
@@ -1824,7 +1856,7 @@ static int fbatch_chunk(D *qs, const std::vector<FBatchItem> &items, size_t lo, 
         tasks += q.d_out ? (t + 1) / 2 : 1;               // count only: one wave sums the tile counts, nothing else to do
     }
     tile_start[nf] = tiles; task_start[nf] = tasks;
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
     const uint32_t want = (tasks + 256 / WAVE - 1) / (256 / WAVE), cap = (uint32_t)g.cus * 32;      // grid-stride, as filter_write_grid
     fbatch_launch(dd, (uint32_t)nf, d_tile_start, tiles, d_task_start, want < cap ? want : cap);
     HIP_TRY(hipGetLastError());
@@ -1843,18 +1875,16 @@ static int fbatch_alone(rhj_filter_desc &q)
 {
     const uint64_t n = q.n, tiles = (n + FILTER_TILE - 1) / FILTER_TILE;
     if (tiles >= (1ull << 32)) return -2;
-    const size_t up_bytes = sizeof(FBatchDesc) + 2 * 4;
-    if (filter_workspace(n, tiles) || batch_pinned(up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    FBatchDesc *hd = (FBatchDesc *)g.batch_pin;
-    uint32_t *tile_start = (uint32_t *)(hd + 1);
+    Block blk;                                            // [the descriptor][2 tile starts], nothing read back
+    FBatchDesc *hd, *dd; uint32_t *tile_start, *d_tile_start;
+    if (filter_workspace(n, tiles) || batch_block(blk, [&](Block &b) { b.up(hd, dd, 1); b.up(tile_start, d_tile_start, 2); })) return -1;
     FBatchDesc d;
     fbatch_desc(q, (uint64_t *)g.fmask.p, (uint64_t *)g.ftile.p, nullptr, d);
     memcpy((void *)hd, (const void *)&d, sizeof(d));
     tile_start[0] = 0; tile_start[1] = (uint32_t)tiles;
     uint64_t *total = &((PlanSummary *)g.summary.p)->matches;
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
-    RHJ_LAUNCH(k_fbatch_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, (const FBatchDesc *)g.batch_desc.p,
-               (const uint32_t *)((const char *)g.batch_desc.p + sizeof(FBatchDesc)), 1u);
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
+    RHJ_LAUNCH(k_fbatch_mask, dim3((unsigned)tiles), dim3(256), 0, g.stream, dd, d_tile_start, 1u);
     uint64_t h = 0;
     if (q.d_out ? filter_write_out(n, tiles, total, q.d_out, &h) : filter_count_out(tiles, total, &h)) return -1;
     q.hits = h; q.path = 0;
@@ -1898,20 +1928,9 @@ static int filter_batch(D *qs, uint64_t n)
         it.idx = i; it.masks = it.counts = it.end = 0;
         items.push_back(it);
     }
-    for (size_t lo = 0; lo < items.size();) {
-        size_t hi = lo, at = 0;
-        while (hi < items.size() && hi - lo < FBATCH_MAX_FILTERS) {
-            const uint64_t rows_hi = qs[items[hi].idx].n;
-            const size_t masks = at, counts = masks + ((fbatch_mask_bytes(rows_hi) + 255) & ~(size_t)255);
-            const size_t end = counts + (((size_t)((rows_hi + FILTER_TILE - 1) / FILTER_TILE) * 8 + 255) & ~(size_t)255);
-            if (hi > lo && end > BATCH_ARENA_BUDGET) break;
-            items[hi].masks = masks; items[hi].counts = counts; items[hi].end = end;
-            at = end;
-            ++hi;
-        }
-        if (fbatch_chunk(qs, items, lo, hi)) return -1;
-        lo = hi;
-    }
+    const auto place = [&](size_t k, uint64_t at) { return fbatch_place(qs[items[k].idx].n, (size_t)at, items[k]); };
+    if (batch_cut(items.size(), FBATCH_MAX_FILTERS, BATCH_ARENA_BUDGET, place,
+                  [&](size_t lo, size_t hi, uint64_t) { return fbatch_chunk(qs, items, lo, hi); })) return -1;
     for (const uint64_t i : alone) {
         const int rc = fbatch_alone(qs[i]);
         if (rc < 0) { qs[i].rc = rc; return rc; }
@@ -1955,20 +1974,15 @@ static int apply_chunk(rhj_apply_desc *items, const std::vector<uint64_t> &which
     const size_t ni = hi - lo;
     size_t nsum = 0;
     for (size_t k = lo; k < hi; ++k) nsum += apply_sums(items[which[k]]);
-    // pinned block: [ni sum slots][ni descriptors][ni + 1 tile starts][accumulator and ticket words of the summing items, zero];
-    // all but the slots are uploaded in one copy
+    // the block: [ni sum slots] read back; [ni descriptors][ni + 1 tile starts][accumulator and ticket words of the summing
+    // items, zero] uploaded in one copy
     constexpr size_t WORDS = RHJ_APPLY_MAX_TERMS + 1;     // an item's accumulators and its ticket
-    const size_t slots_bytes = ni * APPLY_SLOT_WORDS * 8, desc_bytes = ni * sizeof(ApplyDesc), start_bytes = ((ni + 1) * 4 + 7) & ~(size_t)7;
-    const size_t words_bytes = nsum * WORDS * 8, up_bytes = desc_bytes + start_bytes + words_bytes;
-    if (batch_pinned(slots_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    uint64_t *slots = (uint64_t *)g.batch_pin;
-    ApplyDesc *hd = (ApplyDesc *)((char *)g.batch_pin + slots_bytes);
-    uint32_t *tile_start = (uint32_t *)((char *)hd + desc_bytes);
-    const ApplyDesc *dd = (const ApplyDesc *)g.batch_desc.p;
-    const uint32_t *d_tile_start = (const uint32_t *)((const char *)g.batch_desc.p + desc_bytes);
-    unsigned long long *d_words = (unsigned long long *)((char *)g.batch_desc.p + desc_bytes + start_bytes);
-    memset(slots, 0, slots_bytes);                        // (a summing item whose slot is not flagged done left no sums: an error)
-    memset((char *)hd + desc_bytes + start_bytes, 0, words_bytes);
+    static_assert(sizeof(ApplyDesc) % 8 == 0, "the words' padding is that of the tile starts alone");
+    Block blk;
+    uint64_t *slots; ApplyDesc *hd, *dd; uint32_t *tile_start, *d_tile_start; unsigned long long *words, *d_words;
+    if (batch_block(blk, [&](Block &b) { b.back(slots, ni * APPLY_SLOT_WORDS); b.up(hd, dd, ni); b.up(tile_start, d_tile_start, ni + 1); b.up(words, d_words, nsum * WORDS); })) return -1;
+    memset(slots, 0, ni * APPLY_SLOT_WORDS * 8);          // (a summing item whose slot is not flagged done left no sums: an error)
+    memset(words, 0, nsum * WORDS * 8);
     uint32_t tiles = 0;
     size_t s = 0;
     for (size_t k = 0; k < ni; ++k) {
@@ -1992,13 +2006,13 @@ static int apply_chunk(rhj_apply_desc *items, const std::vector<uint64_t> &which
         tiles += d.tiles;
     }
     tile_start[ni] = tiles;
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, hd, up_bytes, hipMemcpyHostToDevice, g.stream));
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
     RHJ_LAUNCH(k_apply_batch, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)ni);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
     for (size_t k = 0; k < ni; ++k) {
         rhj_apply_desc &q = items[which[lo + k]];
-        q.path = 8;
+        q.path = PATH_BATCH_APPLY;
         if (!apply_sums(q)) continue;
         const volatile uint64_t *h = (const volatile uint64_t *)slots + k * APPLY_SLOT_WORDS;     // written by the item's last workgroup out (system scope)
         if (h[RHJ_APPLY_MAX_TERMS] != 1) { fprintf(stderr, "rhj: batched apply item %zu left no sums\n", (size_t)which[lo + k]); return -1; }
@@ -2024,21 +2038,12 @@ static int apply_batch(rhj_apply_desc *items, uint64_t n)
         rows += items[i].n;
         if (items[i].n) which.push_back(i);               // an empty item: nothing to launch
     }
-    for (size_t lo = 0; lo < which.size();) {
-        size_t hi = lo;
-        uint64_t tiles = 0;
-        while (hi < which.size() && hi - lo < APPLY_MAX_ITEMS) {
-            const uint64_t t = (items[which[hi]].n + APPLY_TILE - 1) / APPLY_TILE;
-            if (tiles + t > APPLY_MAX_TILES) break;       // (one item never has more: apply_valid)
-            tiles += t;
-            ++hi;
-        }
-        if (apply_chunk(items, which, lo, hi)) return -1;
-        lo = hi;
-    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + (items[which[k]].n + APPLY_TILE - 1) / APPLY_TILE; };   // (one item never has more than the limit: apply_valid)
+    if (batch_cut(which.size(), APPLY_MAX_ITEMS, APPLY_MAX_TILES, tiles,
+                  [&](size_t lo, size_t hi, uint64_t) { return apply_chunk(items, which, lo, hi); })) return -1;
     rhj_stats st = {};
     st.n_r = rows; st.units = which.size();
-    st.reserved = 8;
+    st.reserved = PATH_BATCH_APPLY;
     return batch_close(timed, st);
 }
 
@@ -2046,8 +2051,8 @@ static int apply_batch(rhj_apply_desc *items, uint64_t n)
 // rhj_column_stats_batch_device: every column of at least one row runs in the launches of its chunk (path 11); there is no
 // run-alone class.  A chunk holds at most STATS_MAX_COLUMNS columns and STATS_MAX_TILES tiles (conditions, as the apply
 // batch's) and STATS_ARENA_BYTES of bitmaps (the widest column's is 6.25 MB), and a batch beyond any of them is cut in call
-// order.  How many bitmap bytes a column needs is known only after pass 1, so stats_pass1 runs k_statsbatch_minmax over the
-// columns the first two limits admit, and stats_chunk then marks and counts them in runs that fit the arena: the first run
+// order.  How many bitmap bytes a column needs is known only after pass 1, so stats_group runs k_statsbatch_minmax over the
+// columns the first two limits admit, and then marks and counts them in runs that fit the arena: the first run
 // is the chunk that pass 1 belongs to (three launches, two stream waits), and the columns that did not fit keep their
 // extremes and make up the following chunks (two launches, one wait each).  The uploaded block is
 //   [3 words a column: ~0, 0, 0][descriptors][columns + 1 row-tile starts][columns + 1 word-tile starts]
@@ -2068,116 +2073,78 @@ static uint64_t stats_flags(uint64_t l, uint64_t u)
 
 static inline size_t stats_bitmap_bytes(uint64_t flags) { return (size_t)((flags + 31) / 32) * 4; }
 
-// the arena grows to what a chunk needs, at least doubling, and never beyond STATS_ARENA_BYTES
-static int stats_arena(size_t bytes)
+// One group: the nc columns cols[which[0, nc)], every one valid and of at least one row.  Pass 1 leaves their extremes in the
+// caller's descriptors; passes 2 and 3 then take them in runs whose bitmaps fit the arena together, one chunk a run.
+static int stats_group(rhj_colstats_desc *cols, const uint64_t *which, size_t nc)
 {
-    Buf &b = g.stats_arena;
-    if (bytes <= b.cap) return 0;
-    size_t want = 2 * b.cap > bytes ? 2 * b.cap : bytes;
-    if (want > STATS_ARENA_BYTES) want = STATS_ARENA_BYTES;
-    if (b.p) HIP_TRY(hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    HIP_TRY(hipMalloc(&b.p, want));
-    b.cap = want;
-    return 0;
-}
-
-struct StatsBlock {                                       // where the parts of a pass-1 group's block lie, host and device side
-    size_t              nc, words_bytes, desc_bytes, start_bytes;
-    unsigned long long *back;                             // pinned: what is read back (3 words a column)
-    char               *up;                               // pinned: what is uploaded
-    StatsDesc *hd() const { return (StatsDesc *)(up + words_bytes); }
-    uint32_t *tile_start() const { return (uint32_t *)(up + words_bytes + desc_bytes); }
-    uint32_t *wtile_start() const { return (uint32_t *)(up + words_bytes + desc_bytes + start_bytes); }
-    unsigned long long *d_words() const { return (unsigned long long *)g.batch_desc.p; }
-    const StatsDesc *dd() const { return (const StatsDesc *)((const char *)g.batch_desc.p + words_bytes); }
-    const uint32_t *d_tile_start() const { return (const uint32_t *)((const char *)g.batch_desc.p + words_bytes + desc_bytes); }
-    const uint32_t *d_wtile_start() const { return (const uint32_t *)((const char *)g.batch_desc.p + words_bytes + desc_bytes + start_bytes); }
-};
-
-// Pass 1 of cols[which[lo, hi)], every one valid and of at least one row: the extremes into the descriptors of the caller.
-static int stats_pass1(rhj_colstats_desc *cols, const std::vector<uint64_t> &which, size_t lo, size_t hi, StatsBlock &B)
-{
-    B.nc = hi - lo;
-    B.words_bytes = B.nc * 24; B.desc_bytes = B.nc * sizeof(StatsDesc); B.start_bytes = ((B.nc + 1) * 4 + 7) & ~(size_t)7;
-    const size_t up_bytes = B.words_bytes + B.desc_bytes + 2 * B.start_bytes;
-    if (batch_pinned(B.words_bytes + up_bytes) || ensure(g.batch_desc, up_bytes)) return -1;
-    B.back = (unsigned long long *)g.batch_pin;
-    B.up = (char *)g.batch_pin + B.words_bytes;
-    unsigned long long *words = (unsigned long long *)B.up;
-    StatsDesc *hd = B.hd();
-    uint32_t *tile_start = B.tile_start();
+    static_assert(sizeof(StatsDesc) % 8 == 0, "the tile starts follow the descriptors without padding");
+    const size_t starts = (nc + 2) & ~(size_t)1;          // uint32_t elements of either array of nc + 1 tile starts: an even number, as this block has always had them
+    Block blk;
+    unsigned long long *back, *words, *d_words; StatsDesc *hd, *dd; uint32_t *tile_start, *d_tile_start, *wtile_start, *d_wtile_start;
+    const auto pieces = [&](Block &b) { b.back(back, 3 * nc); b.up(words, d_words, 3 * nc); b.up(hd, dd, nc); b.up(tile_start, d_tile_start, starts); b.up(wtile_start, d_wtile_start, starts); };
+    if (batch_block(blk, pieces)) return -1;
     uint32_t tiles = 0;
-    for (size_t k = 0; k < B.nc; ++k) {
-        const rhj_colstats_desc &q = cols[which[lo + k]];
+    for (size_t k = 0; k < nc; ++k) {
+        const rhj_colstats_desc &q = cols[which[k]];
         words[3 * k] = ~0ull; words[3 * k + 1] = 0; words[3 * k + 2] = 0;
         StatsDesc d;
         memset((void *)&d, 0, sizeof(d));
-        d.col = q.d_col; d.n = q.n; d.words = B.d_words() + 3 * k;
+        d.col = q.d_col; d.n = q.n; d.words = d_words + 3 * k;
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
         tile_start[k] = tiles;
         tiles += (uint32_t)((q.n + STATS_TILE - 1) / STATS_TILE);
     }
-    tile_start[B.nc] = tiles;
-    HIP_TRY(hipMemcpyAsync(g.batch_desc.p, B.up, B.words_bytes + B.desc_bytes + B.start_bytes, hipMemcpyHostToDevice, g.stream));
-    RHJ_LAUNCH(k_statsbatch_minmax, dim3(tiles), dim3(256), 0, g.stream, B.dd(), B.d_tile_start(), (uint32_t)B.nc);
+    tile_start[nc] = tiles;
+    if (batch_upload(blk, words, wtile_start)) return -1; // the words, the descriptors, the row-tile starts
+    RHJ_LAUNCH(k_statsbatch_minmax, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)nc);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(B.back, B.d_words(), B.words_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(back, d_words, nc * 24, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
-    for (size_t k = 0; k < B.nc; ++k) {
-        rhj_colstats_desc &q = cols[which[lo + k]];
-        q.l = B.back[3 * k]; q.u = B.back[3 * k + 1];
-        if (q.l > q.u) { fprintf(stderr, "rhj: batched statistics column %zu left no extremes\n", (size_t)which[lo + k]); return -1; }
+    for (size_t k = 0; k < nc; ++k) {
+        rhj_colstats_desc &q = cols[which[k]];
+        q.l = back[3 * k]; q.u = back[3 * k + 1];
+        if (q.l > q.u) { fprintf(stderr, "rhj: batched statistics column %zu left no extremes\n", (size_t)which[k]); return -1; }
     }
-    return 0;
-}
-
-// Passes 2 and 3 of columns [a, b) of the group pass 1 ran (their extremes are in the caller's descriptors, their bitmaps
-// fit the arena together): one chunk.
-static int stats_chunk(rhj_colstats_desc *cols, const std::vector<uint64_t> &which, size_t lo, const StatsBlock &B, size_t a, size_t b)
-{
-    StatsDesc *hd = B.hd();
-    uint32_t *tile_start = B.tile_start(), *wtile_start = B.wtile_start();      // of this run: both begin at 0
-    size_t at = 0;
-    for (size_t k = a; k < b; ++k) at += stats_bitmap_bytes(stats_flags(cols[which[lo + k]].l, cols[which[lo + k]].u));
-    if (stats_arena(at)) return -1;
-    at = 0;
-    uint32_t tiles = 0, wtiles = 0;
-    for (size_t k = a; k < b; ++k) {
-        const rhj_colstats_desc &q = cols[which[lo + k]];
-        const uint64_t flags = stats_flags(q.l, q.u);
-        StatsDesc d;
-        memcpy((void *)&d, (const void *)&hd[k], sizeof(d));
-        d.bits = (uint32_t *)((char *)g.stats_arena.p + at);
-        d.lo = q.l;
-        d.fold = q.u - q.l + 1 == flags ? 0 : (uint32_t)STATS_FOLD;
-        d.nwords = (uint32_t)((flags + 31) / 32);
-        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
-        at += stats_bitmap_bytes(flags);
-        tile_start[k - a] = tiles;
-        tiles += (uint32_t)((q.n + STATS_TILE - 1) / STATS_TILE);
-        wtile_start[k - a] = wtiles;
-        wtiles += (d.nwords + STATS_WORD_TILE - 1) / STATS_WORD_TILE;
-    }
-    tile_start[b - a] = tiles;
-    wtile_start[b - a] = wtiles;
-    const uint32_t nc = (uint32_t)(b - a);
-    // the placement: the descriptors, both arrays of tile starts (the columns' words stay as the device has them)
-    HIP_TRY(hipMemcpyAsync((char *)g.batch_desc.p + B.words_bytes, B.up + B.words_bytes, B.desc_bytes + 2 * B.start_bytes, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(hipMemsetAsync(g.stats_arena.p, 0, at, g.stream));
-    RHJ_LAUNCH(k_statsbatch_mark, dim3(tiles), dim3(256), 0, g.stream, B.dd() + a, B.d_tile_start(), nc);
-    RHJ_LAUNCH(k_statsbatch_count, dim3(wtiles), dim3(256), 0, g.stream, B.dd() + a, B.d_wtile_start(), nc);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(B.back, B.d_words(), B.words_bytes, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    for (size_t k = a; k < b; ++k) {
-        rhj_colstats_desc &q = cols[which[lo + k]];
-        q.d = (double)B.back[3 * k + 2];
-        q.path = 11;
-    }
-    ++g_stats_info.chunks;
-    g_stats_info.columns += nc;
-    return 0;
+    const auto bitmap = [&](size_t k) { return stats_bitmap_bytes(stats_flags(cols[which[k]].l, cols[which[k]].u)); };
+    // passes 2 and 3 of columns [a, b), whose bitmaps take `bytes` together: one chunk
+    const auto chunk = [&](size_t a, size_t b, uint64_t bytes) {
+        if (batch_arena(g.stats_arena, (size_t)bytes, STATS_ARENA_BYTES)) return -1;
+        size_t at = 0;
+        uint32_t tiles = 0, wtiles = 0;                   // of this run: both arrays of tile starts begin at 0
+        for (size_t k = a; k < b; ++k) {
+            const rhj_colstats_desc &q = cols[which[k]];
+            const uint64_t flags = stats_flags(q.l, q.u);
+            StatsDesc d;
+            memcpy((void *)&d, (const void *)&hd[k], sizeof(d));
+            d.bits = (uint32_t *)((char *)g.stats_arena.p + at);
+            d.lo = q.l;
+            d.fold = q.u - q.l + 1 == flags ? 0 : (uint32_t)STATS_FOLD;
+            d.nwords = (uint32_t)((flags + 31) / 32);
+            memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+            at += bitmap(k);
+            tile_start[k - a] = tiles;
+            tiles += (uint32_t)((q.n + STATS_TILE - 1) / STATS_TILE);
+            wtile_start[k - a] = wtiles;
+            wtiles += (d.nwords + STATS_WORD_TILE - 1) / STATS_WORD_TILE;
+        }
+        tile_start[b - a] = tiles; wtile_start[b - a] = wtiles;
+        // the placement: the descriptors, both arrays of tile starts (the columns' words stay as the device has them)
+        if (batch_upload(blk, hd, blk.host_end())) return -1;
+        HIP_TRY(hipMemsetAsync(g.stats_arena.p, 0, at, g.stream));
+        RHJ_LAUNCH(k_statsbatch_mark, dim3(tiles), dim3(256), 0, g.stream, dd + a, d_tile_start, (uint32_t)(b - a));
+        RHJ_LAUNCH(k_statsbatch_count, dim3(wtiles), dim3(256), 0, g.stream, dd + a, d_wtile_start, (uint32_t)(b - a));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(back, d_words, nc * 24, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        for (size_t k = a; k < b; ++k) {
+            cols[which[k]].d = (double)back[3 * k + 2];
+            cols[which[k]].path = PATH_BATCH_STATS;
+        }
+        ++g_stats_info.chunks;
+        g_stats_info.columns += (uint32_t)(b - a);
+        return 0;
+    };
+    return batch_cut(nc, nc, STATS_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + bitmap(k); }, chunk);   // (one column's bitmap alone always fits)
 }
 
 static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
@@ -2194,33 +2161,12 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
         if (cols[i].n) which.push_back(i);
         else { cols[i].l = cols[i].u = 0; cols[i].d = 0; }   // an empty column: nothing to launch
     }
-    for (size_t lo = 0; lo < which.size();) {
-        size_t hi = lo;
-        uint64_t tiles = 0;
-        while (hi < which.size() && hi - lo < STATS_MAX_COLUMNS) {
-            const uint64_t t = (cols[which[hi]].n + STATS_TILE - 1) / STATS_TILE;
-            if (tiles + t > STATS_MAX_TILES) break;       // (one column never has more: the validation)
-            tiles += t;
-            ++hi;
-        }
-        StatsBlock B;
-        if (stats_pass1(cols, which, lo, hi, B)) return -1;
-        for (size_t a = 0; a < B.nc;) {
-            size_t b = a, bytes = 0;
-            while (b < B.nc) {
-                const size_t mine = stats_bitmap_bytes(stats_flags(cols[which[lo + b]].l, cols[which[lo + b]].u));
-                if (bytes + mine > STATS_ARENA_BYTES) break;  // (one column alone always fits)
-                bytes += mine;
-                ++b;
-            }
-            if (stats_chunk(cols, which, lo, B, a, b)) return -1;
-            a = b;
-        }
-        lo = hi;
-    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + (cols[which[k]].n + STATS_TILE - 1) / STATS_TILE; };   // (one column never has more than the limit: the validation)
+    if (batch_cut(which.size(), STATS_MAX_COLUMNS, STATS_MAX_TILES, tiles,
+                  [&](size_t lo, size_t hi, uint64_t) { return stats_group(cols, which.data() + lo, hi - lo); })) return -1;
     rhj_stats st = {};
     st.n_r = rows; st.units = which.size();
-    st.reserved = 11;
+    st.reserved = PATH_BATCH_STATS;
     return batch_close(timed, st);
 }
 
@@ -2286,9 +2232,24 @@ struct QueryState {
     bool            alive;                                // neither finished nor empty
 };
 
-struct QueryBump {                                        // byte offsets of 16-byte aligned pieces of one buffer
-    size_t at = 0;
-    size_t take(uint64_t words) { const size_t o = at; at += (size_t)((words + 1) / 2 * 2) * 8; return o; }
+struct TwoNodes {                                         // the nodes a level's predicate joins, and a binding's place in them
+    int na, nb;
+    TwoNodes(const QueryState &s, const rhj_query_join &p) : na(s.node[p.relA]), nb(s.node[p.relB]) {}
+    bool has(const QueryState &s, int x) const { return s.node[x] == na || s.node[x] == nb; }
+    int side(const QueryState &s, int x) const { return s.node[x] == nb && na != nb; }     // the word of an index row
+};
+
+struct QueryBump {                                        // 16-byte aligned pieces of one buffer: who gets each (take), their addresses once it has its size (resolve)
+    struct Piece { size_t item; int sub; size_t off; };
+    size_t             at = 0;
+    std::vector<Piece> pieces;
+    void take(size_t item, int sub, uint64_t words) { pieces.push_back({item, sub, at}); at += (size_t)((words + 1) / 2 * 2) * 8; }
+    template <class Set> int resolve(Buf &b, Set set) const
+    {
+        if (ensure(b, at)) return -1;
+        for (const Piece &p : pieces) set(p.item, p.sub, (char *)b.p + p.off);
+        return 0;
+    }
 };
 
 struct QueryTimingOff {                                   // the inner batches record and wait for no events of their own
@@ -2298,6 +2259,189 @@ struct QueryTimingOff {                                   // the inner batches r
 };
 
 rhj_query_batch_info g_query_info = {};
+
+struct QueryRun {                                         // what the stages of one call share
+    const rhj_device_relation      *rels;
+    rhj_query_desc                 *queries;
+    uint64_t                        n;
+    std::vector<QueryState>         st;
+    std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
+    std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins) ...
+    std::vector<size_t>             where;                // ... and its descriptor in ed / jd
+    std::vector<rhj_eq2_desc>       ed;
+    std::vector<rhj_join_cols_desc> jd;
+    std::vector<rhj_apply_desc>     ad;
+    auto column(const rhj_query_desc &q, int b, int c) const { return rels[q.rels[b]].d_columns[c]; }
+    bool finishes(uint64_t i, int l) const { return queries[i].njoins == 0 || l == queries[i].njoins - 1; }
+};
+
+// The filters of all queries: all of one binding are one conjunction, all of them over all queries one call.
+static int query_filters(QueryRun &R)
+{
+    std::vector<rhj_filter_desc> fd;
+    std::vector<std::pair<uint64_t, int>> fwho;           // (query, binding) of a descriptor
+    QueryBump fb;
+    for (uint64_t i = 0; i < R.n; ++i) {
+        const rhj_query_desc &q = R.queries[i];
+        QueryState &s = R.st[i];
+        s.alive = true;
+        for (int b = 0; b < q.nrels; ++b) {
+            s.vec[b] = nullptr; s.node[b] = b; s.rows[b] = R.rels[q.rels[b]].num_tuples;
+            if (s.rows[b] == 0) s.alive = false;          // an empty relation: every result it takes part in is empty
+        }
+        if (!s.alive) continue;
+        for (int b = 0; b < q.nrels; ++b) {
+            rhj_filter_desc d = {};
+            for (int f = 0; f < q.nfilters; ++f) {
+                const rhj_query_filter &p = q.filters[f];
+                if (p.rel != b) continue;
+                rhj_filter_term &t = d.terms[d.nterms++];
+                t.d_col = R.column(q, b, p.col); t.value = p.value; t.op = p.op;
+            }
+            if (d.nterms == 0) continue;                  // no filter: the binding stays its whole relation
+            d.n = s.rows[b];
+            fb.take(fd.size(), 0, d.n);
+            fd.push_back(d); fwho.emplace_back(i, b);
+        }
+    }
+    if (fd.empty()) return 0;
+    if (fb.resolve(g_qb.filt, [&](size_t k, int, char *p) { fd[k].d_out = (uint64_t *)p; })) return -1;
+    ++g_query_info.filter_calls;
+    if (const int rc = filter_batch(fd.data(), fd.size())) return rc;     // (0 or an error)
+    for (size_t k = 0; k < fd.size(); ++k) {
+        QueryState &s = R.st[fwho[k].first];
+        const int b = fwho[k].second;
+        s.vec[b] = fd[k].d_out; s.rows[b] = fd[k].hits;
+        if (fd[k].hits == 0) s.alive = false;             // a filter without a hit: rows = 0
+    }
+    return 0;
+}
+
+// The joins whose fan-out passed the guess, again: the counts are known now.
+static int query_rerun_short(QueryRun &R)
+{
+    std::vector<rhj_join_cols_desc> jd2;
+    std::vector<size_t> short_k;
+    QueryBump rb;
+    for (size_t k = 0; k < R.jd.size(); ++k) {
+        if (R.jd[k].rc != 1) continue;
+        rhj_join_cols_desc d = R.jd[k];
+        d.out_capacity = d.matches;
+        rb.take(jd2.size(), 0, 2 * d.out_capacity);
+        short_k.push_back(k); jd2.push_back(d);
+    }
+    if (rb.resolve(g_qb.idx2, [&](size_t k, int, char *p) { jd2[k].d_out = (rhj_result_tuple *)p; })) return -1;
+    ++g_query_info.join_reruns;
+    const int rc = join_batch(jd2.data(), jd2.size());
+    if (rc < 0) return rc;
+    if (rc != 0) { fprintf(stderr, "rhj: a join run again with room for its count was short once more\n"); return -1; }
+    for (size_t k = 0; k < jd2.size(); ++k) R.jd[short_k[k]] = jd2[k];
+    return 0;
+}
+
+// Level l's predicates: at most one batch of two-column equalities (both bindings in one node) and one of joins on columns.
+static int query_level_joins(QueryRun &R, int l)
+{
+    QueryBump ib;
+    R.active.clear(); R.kind.clear(); R.where.clear(); R.ed.clear(); R.jd.clear(); R.ad.clear(); R.awho.clear();   // the level before
+    for (uint64_t i = 0; i < R.n; ++i) {
+        const rhj_query_desc &q = R.queries[i];
+        const QueryState &s = R.st[i];
+        if (!s.alive || (q.njoins <= l && (l || q.njoins))) continue;
+        R.active.push_back(i);
+        if (q.njoins == 0) { R.kind.push_back(2); R.where.push_back(0); continue; }     // no predicate at all: level 0 sums its views
+        const rhj_query_join &p = q.joins[l];
+        const TwoNodes two(s, p);
+        R.kind.push_back(two.na == two.nb);
+        if (two.na == two.nb) {                           // the two-column equality over the node's rows
+            rhj_eq2_desc d = {};
+            d.d_colA = R.column(q, p.relA, p.colA); d.d_selA = s.vec[p.relA];
+            d.d_colB = R.column(q, p.relB, p.colB); d.d_selB = s.vec[p.relB];
+            d.n = s.rows[two.na];
+            ib.take(R.ed.size(), 1, d.n);
+            R.where.push_back(R.ed.size()); R.ed.push_back(d);
+        } else {
+            rhj_join_cols_desc d = {};
+            d.d_colR = R.column(q, p.relA, p.colA); d.d_selR = s.vec[p.relA]; d.nR = s.rows[two.na];
+            d.d_colS = R.column(q, p.relB, p.colB); d.d_selS = s.vec[p.relB]; d.nS = s.rows[two.nb];
+            d.out_capacity = d.nR > d.nS ? d.nR : d.nS;
+            ib.take(R.jd.size(), 0, 2 * d.out_capacity);
+            R.where.push_back(R.jd.size()); R.jd.push_back(d);
+        }
+    }
+    const auto set = [&](size_t k, int eq, char *p) { if (eq) R.ed[k].d_out = (uint64_t *)p; else R.jd[k].d_out = (rhj_result_tuple *)p; };
+    if (ib.resolve(g_qb.idx, set)) return -1;
+    if (!R.ed.empty()) {
+        ++g_query_info.eq2_calls;
+        if (const int rc = filter_batch(R.ed.data(), R.ed.size())) return rc;
+    }
+    if (!R.jd.empty()) {
+        ++g_query_info.join_calls;
+        const int rc = join_batch(R.jd.data(), R.jd.size());
+        if (rc < 0) return rc;
+        if (rc == 1) return query_rerun_short(R);
+    }
+    return 0;
+}
+
+// Level l's apply batch: the queries that go on rebuild the vectors of the two nodes, those that finish sum their views.
+static int query_level_apply(QueryRun &R, int l)
+{
+    QueryBump vb;
+    for (size_t a = 0; a < R.active.size(); ++a) {
+        const uint64_t i = R.active[a];
+        const rhj_query_desc &q = R.queries[i];
+        QueryState &s = R.st[i];
+        const TwoNodes two(s, q.njoins ? q.joins[l] : rhj_query_join{});       // (no predicate: the one binding, side 0)
+        rhj_apply_desc d = {};
+        if (R.kind[a] == 2)      { d.n = s.rows[0]; d.idx_stride = 1; }        // the views through the binding's own vector
+        else if (R.kind[a] == 1) { d.d_idx = R.ed[R.where[a]].d_out; d.n = R.ed[R.where[a]].hits; d.idx_stride = 1; }
+        else                     { d.d_idx = (const uint64_t *)R.jd[R.where[a]].d_out; d.n = R.jd[R.where[a]].matches; d.idx_stride = 2; }
+        if (d.n == 0) { s.alive = false; continue; }      // an empty list: rows = 0, no item
+        if (R.finishes(i, l)) {
+            for (int v = 0; v < q.nviews; ++v) {
+                const int x = q.views[v].rel;
+                rhj_apply_term &t = d.terms[d.nterms++];
+                t.side = two.side(s, x); t.d_src = s.vec[x]; t.d_col = R.column(q, x, q.views[v].col);
+            }
+        } else {
+            for (int x = 0; x < q.nrels; ++x) {
+                if (!two.has(s, x)) continue;
+                vb.take(R.ad.size(), d.nterms, d.n);      // the rebuilt vector
+                rhj_apply_term &t = d.terms[d.nterms++];
+                t.side = two.side(s, x); t.d_src = s.vec[x];
+            }
+        }
+        R.ad.push_back(d); R.awho.push_back(i);
+    }
+    if (R.active.empty()) return 0;                       // nobody alive at this level
+    if (vb.resolve(g_qb.level[l], [&](size_t a, int t, char *p) { R.ad[a].terms[t].d_dst = (uint64_t *)p; })) return -1;
+    ++g_query_info.apply_calls;
+    return apply_batch(R.ad.data(), R.ad.size());         // (0 or an error)
+}
+
+// What level l's apply batch left: the sums and rows of the queries that finished, the two nodes of the others merged into A's.
+static void query_take_back(QueryRun &R, int l)
+{
+    for (size_t a = 0; a < R.ad.size(); ++a) {
+        rhj_query_desc &q = R.queries[R.awho[a]];
+        QueryState &s = R.st[R.awho[a]];
+        const rhj_apply_desc &d = R.ad[a];
+        if (R.finishes(R.awho[a], l)) {
+            for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.terms[v].sum;
+            q.rows = d.n;
+            s.alive = false;                              // finished
+            continue;
+        }
+        const TwoNodes two(s, q.joins[l]);
+        int t = 0;
+        for (int x = 0; x < q.nrels; ++x) {
+            if (!two.has(s, x)) continue;
+            s.vec[x] = d.terms[t++].d_dst; s.node[x] = two.na;
+        }
+        s.rows[two.na] = d.n;
+    }
+}
 
 static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
@@ -2318,197 +2462,17 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     const bool timed = g.timing >= 1;
     if (timed && !g_qb.ev[1]) for (auto &ev : g_qb.ev) HIP_TRY(hipEventCreate(&ev));
     if (timed) HIP_TRY(hipEventRecord(g_qb.ev[0], g.stream));
-    rhj_query_batch_info &info = g_query_info;
-    info.levels = (uint32_t)maxl;
-    const auto column = [&](const rhj_query_desc &q, int b, int c) { return rels[q.rels[b]].d_columns[c]; };
+    g_query_info.levels = (uint32_t)maxl;
     {
         QueryTimingOff inner_untimed;
-        std::vector<QueryState> st(n);
-
-        // the filters: all of one binding are one conjunction, all of them over all queries one call
-        std::vector<rhj_filter_desc> fd;
-        std::vector<std::pair<uint64_t, int>> fwho;       // (query, binding) of a descriptor
-        std::vector<size_t> foff;
-        QueryBump fb;
-        for (uint64_t i = 0; i < n; ++i) {
-            const rhj_query_desc &q = queries[i];
-            QueryState &s = st[i];
-            s.alive = true;
-            for (int b = 0; b < q.nrels; ++b) {
-                s.vec[b] = nullptr; s.node[b] = b; s.rows[b] = rels[q.rels[b]].num_tuples;
-                if (s.rows[b] == 0) s.alive = false;      // an empty relation: every result it takes part in is empty
-            }
-            if (!s.alive) continue;
-            for (int b = 0; b < q.nrels; ++b) {
-                rhj_filter_desc d;
-                memset(&d, 0, sizeof(d));
-                for (int f = 0; f < q.nfilters; ++f) {
-                    const rhj_query_filter &p = q.filters[f];
-                    if (p.rel != b) continue;
-                    rhj_filter_term &t = d.terms[d.nterms++];
-                    t.d_col = column(q, b, p.col); t.value = p.value; t.op = p.op;
-                }
-                if (d.nterms == 0) continue;              // no filter: the binding stays its whole relation
-                d.n = s.rows[b];
-                fd.push_back(d); fwho.emplace_back(i, b); foff.push_back(fb.take(d.n));
-            }
-        }
-        if (!fd.empty()) {
-            if (ensure(g_qb.filt, fb.at)) return -1;
-            for (size_t k = 0; k < fd.size(); ++k) fd[k].d_out = (uint64_t *)((char *)g_qb.filt.p + foff[k]);
-            ++info.filter_calls;
-            const int rc = filter_batch(fd.data(), fd.size());
-            if (rc < 0) return rc;
-            for (size_t k = 0; k < fd.size(); ++k) {
-                QueryState &s = st[fwho[k].first];
-                const int b = fwho[k].second;
-                s.vec[b] = fd[k].d_out; s.rows[b] = fd[k].hits;
-                if (fd[k].hits == 0) s.alive = false;     // a filter without a hit: rows = 0
-            }
-        }
-
+        QueryRun R = {rels, queries, n, std::vector<QueryState>(n)};
+        if (const int rc = query_filters(R)) return rc;
         // the levels.  (Level 0 also runs when no query has a join: the queries without one sum their views in its apply call.)
         if (g_qb.level.size() < (size_t)(maxl > 1 ? maxl : 1)) g_qb.level.resize((size_t)(maxl > 1 ? maxl : 1));
-        std::vector<rhj_eq2_desc> ed;
-        std::vector<rhj_join_cols_desc> jd, jd2;
-        std::vector<rhj_apply_desc> ad;
-        std::vector<uint64_t> active, awho, short_k;
-        std::vector<size_t> eoff, joff, where, voff;
-        std::vector<int> kind;
         for (int l = 0; l < maxl || l == 0; ++l) {
-            ed.clear(); jd.clear(); jd2.clear(); ad.clear(); active.clear(); awho.clear(); short_k.clear();
-            eoff.clear(); joff.clear(); where.clear(); voff.clear(); kind.clear();
-            QueryBump ib;
-            for (uint64_t i = 0; i < n; ++i) {
-                const rhj_query_desc &q = queries[i];
-                const QueryState &s = st[i];
-                if (!s.alive || q.njoins <= l) continue;
-                const rhj_query_join &p = q.joins[l];
-                const int na = s.node[p.relA], nb = s.node[p.relB];
-                active.push_back(i);
-                kind.push_back(na == nb);
-                if (na == nb) {                           // both bindings in one node: the two-column equality over its rows
-                    rhj_eq2_desc d;
-                    memset(&d, 0, sizeof(d));
-                    d.d_colA = column(q, p.relA, p.colA); d.d_selA = s.vec[p.relA];
-                    d.d_colB = column(q, p.relB, p.colB); d.d_selB = s.vec[p.relB];
-                    d.n = s.rows[na];
-                    where.push_back(ed.size());
-                    ed.push_back(d); eoff.push_back(ib.take(d.n));
-                } else {
-                    rhj_join_cols_desc d;
-                    memset(&d, 0, sizeof(d));
-                    d.d_colR = column(q, p.relA, p.colA); d.d_selR = s.vec[p.relA]; d.nR = s.rows[na];
-                    d.d_colS = column(q, p.relB, p.colB); d.d_selS = s.vec[p.relB]; d.nS = s.rows[nb];
-                    d.out_capacity = d.nR > d.nS ? d.nR : d.nS;
-                    where.push_back(jd.size());
-                    jd.push_back(d); joff.push_back(ib.take(2 * d.out_capacity));
-                }
-            }
-            if (ensure(g_qb.idx, ib.at)) return -1;
-            for (size_t k = 0; k < ed.size(); ++k) ed[k].d_out = (uint64_t *)((char *)g_qb.idx.p + eoff[k]);
-            for (size_t k = 0; k < jd.size(); ++k) jd[k].d_out = (rhj_result_tuple *)((char *)g_qb.idx.p + joff[k]);
-            if (!ed.empty()) {
-                ++info.eq2_calls;
-                const int rc = filter_batch(ed.data(), ed.size());
-                if (rc < 0) return rc;
-            }
-            if (!jd.empty()) {
-                ++info.join_calls;
-                const int rc = join_batch(jd.data(), jd.size());
-                if (rc < 0) return rc;
-                if (rc == 1) {                            // fan-out above the guess: the counts are known now
-                    QueryBump rb;
-                    joff.clear();
-                    for (size_t k = 0; k < jd.size(); ++k) {
-                        if (jd[k].rc != 1) continue;
-                        rhj_join_cols_desc d = jd[k];
-                        d.out_capacity = d.matches;
-                        short_k.push_back(k); jd2.push_back(d); joff.push_back(rb.take(2 * d.out_capacity));
-                    }
-                    if (ensure(g_qb.idx2, rb.at)) return -1;
-                    for (size_t k = 0; k < jd2.size(); ++k) jd2[k].d_out = (rhj_result_tuple *)((char *)g_qb.idx2.p + joff[k]);
-                    ++info.join_reruns;
-                    const int rc2 = join_batch(jd2.data(), jd2.size());
-                    if (rc2 < 0) return rc2;
-                    if (rc2 != 0) { fprintf(stderr, "rhj: a join run again with room for its count was short once more\n"); return -1; }
-                    for (size_t k = 0; k < jd2.size(); ++k) jd[short_k[k]] = jd2[k];
-                }
-            }
-
-            // one apply batch: the queries that go on rebuild the vectors of the two nodes, those that finish sum their views
-            QueryBump vb;
-            for (size_t a = 0; a < active.size(); ++a) {
-                const uint64_t i = active[a];
-                const rhj_query_desc &q = queries[i];
-                QueryState &s = st[i];
-                const rhj_query_join &p = q.joins[l];
-                const int na = s.node[p.relA], nb = s.node[p.relB];
-                rhj_apply_desc d;
-                memset(&d, 0, sizeof(d));
-                if (kind[a]) { d.d_idx = ed[where[a]].d_out; d.n = ed[where[a]].hits; d.idx_stride = 1; }
-                else         { d.d_idx = (const uint64_t *)jd[where[a]].d_out; d.n = jd[where[a]].matches; d.idx_stride = 2; }
-                if (d.n == 0) { s.alive = false; continue; }              // an empty list: rows = 0, no item
-                if (l == q.njoins - 1) {
-                    for (int v = 0; v < q.nviews; ++v) {
-                        const int x = q.views[v].rel;
-                        rhj_apply_term &t = d.terms[d.nterms++];
-                        t.side = s.node[x] == nb && na != nb; t.d_src = s.vec[x]; t.d_col = column(q, x, q.views[v].col);
-                    }
-                } else {
-                    for (int x = 0; x < q.nrels; ++x) {
-                        if (s.node[x] != na && s.node[x] != nb) continue;
-                        rhj_apply_term &t = d.terms[d.nterms++];
-                        t.side = s.node[x] == nb && na != nb; t.d_src = s.vec[x];
-                        voff.push_back(vb.take(d.n));
-                    }
-                }
-                ad.push_back(d); awho.push_back(i);
-            }
-            if (l == 0) {
-                for (uint64_t i = 0; i < n; ++i) {        // no join predicate: the views through the one binding's vector
-                    const rhj_query_desc &q = queries[i];
-                    if (!st[i].alive || q.njoins != 0) continue;
-                    rhj_apply_desc d;
-                    memset(&d, 0, sizeof(d));
-                    d.n = st[i].rows[0]; d.idx_stride = 1;
-                    for (int v = 0; v < q.nviews; ++v) {
-                        rhj_apply_term &t = d.terms[d.nterms++];
-                        t.d_src = st[i].vec[0]; t.d_col = column(q, 0, q.views[v].col);
-                    }
-                    ad.push_back(d); awho.push_back(i);
-                }
-            }
-            if (active.empty() && ad.empty()) continue;   // nobody alive at this level
-            if (ensure(g_qb.level[l], vb.at)) return -1;
-            size_t vk = 0;
-            for (size_t a = 0; a < ad.size(); ++a) {
-                const rhj_query_desc &q = queries[awho[a]];
-                if (q.njoins == 0 || l == q.njoins - 1) continue;
-                for (int t = 0; t < ad[a].nterms; ++t) ad[a].terms[t].d_dst = (uint64_t *)((char *)g_qb.level[l].p + voff[vk++]);
-            }
-            ++info.apply_calls;
-            const int rc = apply_batch(ad.data(), ad.size());
-            if (rc < 0) return rc;
-            for (size_t a = 0; a < ad.size(); ++a) {
-                rhj_query_desc &q = queries[awho[a]];
-                QueryState &s = st[awho[a]];
-                const rhj_apply_desc &d = ad[a];
-                if (q.njoins == 0 || l == q.njoins - 1) {
-                    for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.terms[v].sum;
-                    q.rows = d.n;
-                    s.alive = false;                      // finished
-                    continue;
-                }
-                const rhj_query_join &p = q.joins[l];
-                const int na = s.node[p.relA], nb = s.node[p.relB];
-                int t = 0;
-                for (int x = 0; x < q.nrels; ++x) {
-                    if (s.node[x] != na && s.node[x] != nb) continue;
-                    s.vec[x] = d.terms[t++].d_dst; s.node[x] = na;
-                }
-                s.rows[na] = d.n;
-            }
+            if (const int rc = query_level_joins(R, l)) return rc;
+            if (const int rc = query_level_apply(R, l)) return rc;
+            query_take_back(R, l);
         }
     }
     uint64_t rows = 0;
@@ -2516,7 +2480,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     rhj_stats &stt = g.stats;
     memset(&stt, 0, sizeof(stt));
     stt.n_r = n; stt.matches = rows;
-    stt.reserved = 10;
+    stt.reserved = PATH_QUERY_BATCH;
     if (timed) {
         HIP_TRY(hipEventRecord(g_qb.ev[1], g.stream));
         HIP_TRY(hipEventSynchronize(g_qb.ev[1]));

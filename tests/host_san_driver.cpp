@@ -5,6 +5,7 @@
 // rhj_move_blocks through a ring of staging buffers, the way rhj_device.hip hands it the D2H copies.
 #include "rhj.h"
 #include "rhj_internal.h"
+#include "rhj_block.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -116,8 +117,98 @@ static uint64_t list_digest(rhj_result *res, uint64_t *count)
     return h;
 }
 
+// ---- csrc/rhj_block.h: the block of a batched chunk, at the layouts rhj_device.hip declares ------------------------------
+// Stand-ins of the device descriptors' sizeof and alignof (the real ones need HIP): BatchJoin, FBatchDesc, Eq2BatchDesc,
+// ApplyDesc, StatsDesc.
+template <size_t N> struct alignas(8) DescOf { char bytes[N]; };
+using JoinD = DescOf<704>; using FilterD = DescOf<152>; using Eq2D = DescOf<80>; using ApplyD = DescOf<312>; using StatsD = DescOf<48>;
+
+struct PieceAt { char *host, *dev; size_t bytes, align; };           // dev nullptr: read back only
+alignas(16) static char g_pin[1 << 14], g_dev[1 << 14];
+template <class T> static PieceAt piece(T *host, T *dev, size_t count) { return {(char *)host, (char *)dev, count * sizeof(T), alignof(T)}; }
+
+// every piece aligned to its type, the pieces disjoint, in the order declared and no further apart than alignment asks, the
+// read-back pieces in front, both sides of an uploaded piece the same offset from where the uploaded part begins
+static void check_pieces(const Block &b, const std::vector<PieceAt> &ps, size_t total, size_t uploaded)
+{
+    CHECK(b.bytes() == total && b.up_bytes() == uploaded && total <= sizeof(g_pin) && b.host_end() == g_pin + total);
+    char *end = g_pin, *up_host = nullptr;
+    for (const PieceAt &p : ps) {
+        CHECK(p.host >= end && (size_t)(p.host - end) < p.align && (uintptr_t)p.host % p.align == 0);
+        if (p.dev) {
+            if (!up_host) { up_host = p.host; CHECK(p.dev == g_dev && p.host == g_pin + (total - uploaded)); }
+            CHECK(p.dev - g_dev == p.host - up_host && (uintptr_t)p.dev % p.align == 0 && b.mirror(p.host) == p.dev);
+        } else CHECK(!up_host);
+        end = p.host + p.bytes;
+    }
+    CHECK(end == g_pin + total);
+}
+
+static void check_block_layouts()
+{
+    static_assert(alignof(JoinD) == 8 && sizeof(StatsD) == 48, "the stand-ins");
+    uint64_t *back; unsigned long long *words, *d_words; uint32_t *t0, *d_t0, *t1, *d_t1;
+    for (size_t n = 1; n <= 3; ++n) {
+        const size_t start_bytes = ((n + 1) * 4 + 7) & ~(size_t)7;     // n + 1 tile starts, to 8 bytes
+        {   // join batch: [n slots of 16 words] | [n descriptors][3 lists of n]
+            Block b(g_pin, g_dev), sizes; JoinD *hd, *dd;
+            const auto pieces = [&](Block &x) { x.back(back, n * 16); x.up(hd, dd, n); x.up(t0, d_t0, 3 * n); };
+            pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+            CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+            check_pieces(b, {piece(back, (uint64_t *)nullptr, n * 16), piece(hd, dd, n), piece(t0, d_t0, 3 * n)},
+                         n * 16 * 8 + n * sizeof(JoinD) + 3 * n * 4, n * sizeof(JoinD) + 3 * n * 4);
+        }
+        {   // filter batch: [n totals] | [n descriptors][n + 1 tile starts][n + 1 task starts]
+            Block b(g_pin, g_dev), sizes; FilterD *hd, *dd;
+            const auto pieces = [&](Block &x) { x.back(back, n); x.up(hd, dd, n); x.up(t0, d_t0, n + 1); x.up(t1, d_t1, n + 1); };
+            pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+            CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+            check_pieces(b, {piece(back, (uint64_t *)nullptr, n), piece(hd, dd, n), piece(t0, d_t0, n + 1), piece(t1, d_t1, n + 1)},
+                         n * 8 + n * sizeof(FilterD) + 2 * (n + 1) * 4, n * sizeof(FilterD) + 2 * (n + 1) * 4);
+            CHECK(t1 == t0 + n + 1);
+        }
+        {   // equality batch: the same over its descriptor
+            Block b(g_pin, g_dev), sizes; Eq2D *hd, *dd;
+            const auto pieces = [&](Block &x) { x.back(back, n); x.up(hd, dd, n); x.up(t0, d_t0, n + 1); x.up(t1, d_t1, n + 1); };
+            pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+            CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+            check_pieces(b, {piece(back, (uint64_t *)nullptr, n), piece(hd, dd, n), piece(t0, d_t0, n + 1), piece(t1, d_t1, n + 1)},
+                         n * 8 + n * sizeof(Eq2D) + 2 * (n + 1) * 4, n * sizeof(Eq2D) + 2 * (n + 1) * 4);
+        }
+        for (size_t nsum = 0; nsum <= n; ++nsum) {   // apply batch: [n slots of 9 words] | [n descriptors][n + 1 tile starts][9 words a summing item]
+            Block b(g_pin, g_dev), sizes; ApplyD *hd, *dd;
+            const auto pieces = [&](Block &x) { x.back(back, n * 9); x.up(hd, dd, n); x.up(t0, d_t0, n + 1); x.up(words, d_words, nsum * 9); };
+            pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+            CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+            const size_t up = n * sizeof(ApplyD) + start_bytes + nsum * 9 * 8;
+            check_pieces(b, {piece(back, (uint64_t *)nullptr, n * 9), piece(hd, dd, n), piece(t0, d_t0, n + 1), piece(words, d_words, nsum * 9)}, n * 9 * 8 + up, up);
+            CHECK((char *)words - (char *)t0 == (ptrdiff_t)start_bytes);
+        }
+        {   // statistics batch: [3 words a column] | [3 words a column][n descriptors][2 arrays of n + 1 tile starts, each to 8 bytes]
+            Block b(g_pin, g_dev), sizes; StatsD *hd, *dd; unsigned long long *sback;
+            const size_t starts = (n + 2) & ~(size_t)1, up = n * 24 + n * sizeof(StatsD) + 2 * start_bytes;
+            const auto pieces = [&](Block &x) { x.back(sback, 3 * n); x.up(words, d_words, 3 * n); x.up(hd, dd, n); x.up(t0, d_t0, starts); x.up(t1, d_t1, starts); };
+            pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+            CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+            check_pieces(b, {piece(sback, (unsigned long long *)nullptr, 3 * n), piece(words, d_words, 3 * n), piece(hd, dd, n), piece(t0, d_t0, starts), piece(t1, d_t1, starts)},
+                         n * 24 + up, up);
+            CHECK((char *)t1 - (char *)words == (ptrdiff_t)(n * 24 + n * sizeof(StatsD) + start_bytes));     // pass 1's upload
+            CHECK(b.host_end() - (char *)hd == (ptrdiff_t)(n * sizeof(StatsD) + 2 * start_bytes));           // a run's upload
+            CHECK((char *)dd == g_dev + n * 24);
+        }
+    }
+    {   // a filter alone: nothing read back, [the descriptor][2 tile starts]
+        Block b(g_pin, g_dev), sizes; FilterD *hd, *dd;
+        const auto pieces = [&](Block &x) { x.up(hd, dd, 1); x.up(t0, d_t0, 2); };
+        pieces(sizes); pieces(b);                             // as batch_block() does: once for the sizes, once bound
+        CHECK(sizes.bytes() == b.bytes() && sizes.up_bytes() == b.up_bytes());
+        check_pieces(b, {piece(hd, dd, 1), piece(t0, d_t0, 2)}, sizeof(FilterD) + 2 * 4, sizeof(FilterD) + 2 * 4);
+    }
+}
+
 int main()
 {
+    check_block_layouts();
     // 1. result-list API (results.c behaviour): appends across node boundaries, lookups, free
     {
         rhj_result *head = nullptr;
