@@ -1,9 +1,19 @@
 """What rhj_query_batch_device (include/rhj_inter.h) computes, restated without the library: the query lines of a work file, the
-node tracking that decides between a join and a two-column equality, and a plain numpy executor (masks, a sort-merge join, sums
-modulo 2^64).  A query is (relations, joins [(a, ca, b, cb)], filters [(a, ca, op, value)], views [(a, c)]) with a, b bindings."""
+node tracking that decides between a join and a two-column equality, a plain numpy executor (masks, a sort-merge join, sums
+modulo 2^64), and call_counts: the calls the driver in csrc/rhj_device.hip must issue for a batch, from that executor alone.
+A query is (relations, joins [(a, ca, b, cb)], filters [(a, ca, op, value)], views [(a, c)]) with a, b bindings."""
+import os
 import re
+from collections import namedtuple
 
 import numpy as np
+
+from source_constants import c_int, one
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sigmod-2018_amd", "csrc")
+SOURCES = ("rhj_common.hip.h", "rhj_partition.hip.h", "rhj_small.hip.h", "rhj_batch.hip.h", "rhj_join_fused.hip.h", "rhj_filter.hip.h",
+           "rhj_apply_batch.hip.h", "rhj_device.hip")
 
 
 def parse_work(lines):
@@ -48,18 +58,25 @@ def _match(ka, kb):
     return ia, order[np.repeat(lo, cnt) + within]
 
 
-def run_query(cols, query):
-    """(sums, rows) of one query over cols[r][c] (u64 numpy columns): Python ints below 2^64, all 0 when there is no row"""
+def trace_query(cols, query):
+    """(sums, rows, filtered, steps) of one query over cols[r][c] (u64 numpy columns).  sums are Python ints below 2^64, all 0
+    when there is no row; filtered[b] is (rows of the relation, hits) of a binding with filters and None of one without; steps
+    has per predicate (kind, rows of A's node, rows of B's node, rows of the result), kind as track_kinds has it, both node
+    sizes the one node's for an equality."""
     rels, joins, filters, views = query
     ids = {}                                             # binding -> row ids, aligned within a node
     node = list(range(len(rels)))
+    filtered = []
     for b, r in enumerate(rels):
-        keep = np.ones(len(cols[r][0]), dtype=bool)
-        for a, c, op, v in filters:
-            if a == b:
-                x, v = cols[r][c], np.uint64(int(v) & ((1 << 64) - 1))
-                keep &= (x < v) if op == "<" else (x > v) if op == ">" else (x == v)
+        n = len(cols[r][0])
+        keep = np.ones(n, dtype=bool)
+        mine = [f for f in filters if f[0] == b]
+        for a, c, op, v in mine:
+            x, v = cols[r][c], np.uint64(int(v) & ((1 << 64) - 1))
+            keep &= (x < v) if op == "<" else (x > v) if op == ">" else (x == v)
         ids[b] = np.flatnonzero(keep)
+        filtered.append((n, len(ids[b])) if mine else None)
+    steps = []
     for a, ca, b, cb in joins:
         ka, kb = cols[rels[a]][ca][ids[a]], cols[rels[b]][cb][ids[b]]
         na, nb = node[a], node[b]
@@ -68,6 +85,7 @@ def run_query(cols, query):
             for x in range(len(rels)):
                 if node[x] == na:
                     ids[x] = ids[x][keep]
+            steps.append((1, len(ka), len(kb), len(keep)))
         else:
             ia, ib = _match(ka, kb)
             for x in range(len(rels)):
@@ -76,6 +94,182 @@ def run_query(cols, query):
                 elif node[x] == nb:
                     ids[x] = ids[x][ib]
             node = [na if x == nb else x for x in node]
+            steps.append((0, len(ka), len(kb), len(ia)))
     assert len(set(node)) == 1
     rows = len(ids[0])
-    return [int(cols[rels[a]][c][ids[a]].sum(dtype=np.uint64)) if rows else 0 for a, c in views], rows
+    return [int(cols[rels[a]][c][ids[a]].sum(dtype=np.uint64)) if rows else 0 for a, c in views], rows, filtered, steps
+
+
+def run_query(cols, query):
+    """(sums, rows) of one query over cols[r][c] (u64 numpy columns): Python ints below 2^64, all 0 when there is no row"""
+    return tuple(trace_query(cols, query)[:2])
+
+
+# ---- the driver's calls ------------------------------------------------------------------------------------------------------------
+# The limits of the inner batches, read out of the sources: which items a batch runs in its shared launches and which alone, and
+# where it cuts a call into chunks.
+
+Limits = namedtuple("Limits", ("PT_MAX_BITS", "MAX_BITS", "JOIN_MAX_TUPLES", "FILTER_MAX_ROWS", "FILTER_MAX_ITEMS", "APPLY_MAX_ITEMS", "APPLY_MAX_TERMS",
+                               "FILTER_MAX_TERMS", "QUERY_MAX_RELS", "QUERY_MAX_VIEWS", "ARENA_BUDGET", "JOIN_ARENA_FLOOR", "TUPLE_BYTES"))
+
+
+def _one(pattern, text, what):
+    return one(pattern, text, what, "tests/query_model.py")
+
+
+def parse_limits():
+    text = {}
+    for n in SOURCES:
+        with open(os.path.join(CSRC, n)) as f:
+            text[n] = f.read()
+    names = {}
+    for n in SOURCES:
+        for m in re.finditer(r"constexpr\s+(?:int|uint32_t|uint64_t|size_t)\s+(\w+)\s*=\s*([^;]+);", text[n]):
+            try:
+                names[m.group(1)] = c_int(m.group(2), names)
+            except (ValueError, NameError, SyntaxError, TypeError, ZeroDivisionError):
+                pass
+    with open(os.path.join(ROOT, "include", "rhj_inter.h")) as f:
+        inter = f.read()
+    with open(os.path.join(ROOT, "include", "rhj.h")) as f:
+        inter += f.read()
+    for d in ("RHJ_APPLY_MAX_TERMS", "RHJ_FILTER_MAX_TERMS", "RHJ_QUERY_MAX_RELS", "RHJ_QUERY_MAX_VIEWS"):
+        names[d] = int(_one(r"#define\s+%s\s+(\d+)" % d, inter, d).group(1))
+    dev, fj = text["rhj_device.hip"], text["rhj_join_fused.hip.h"]
+    missing = [n for n in ("PT_MAX_BITS", "MAX_BITS", "BJ_MAX_TILES", "SM_TILE", "BJ_WGS", "FBATCH_MAX_ROWS", "FBATCH_MAX_FILTERS", "APPLY_MAX_ITEMS") if n not in names]
+    if missing:
+        raise AssertionError("tests/query_model.py no longer finds %s in the sources" % missing)
+    # the rules call_counts restates, as the code words them: a change there must be looked at here
+    for pat, what in ((r"if \(bits < 1 \|\| bits > PT_MAX_BITS \|\| nR == 0 \|\| nS == 0\) return 0;", "batch_takes' radix rule"),
+                      (r"if \(nR > \(uint64_t\)BJ_MAX_TILES \* SM_TILE \|\| nS > \(uint64_t\)BJ_MAX_TILES \* SM_TILE\) return 0;", "batch_takes' size rule"),
+                      (r"return !g\.no_small && !g\.no_fused && !g\.force_hbm && !g\.stamps;", "batch_takes' switches"),
+                      (r"filter_batch_takes\(uint64_t rows\) \{ return rows >= 1 && rows <= FBATCH_MAX_ROWS; \}", "filter_batch_takes"),
+                      (r"batch_cut\(items\.size\(\), FBATCH_MAX_FILTERS, BATCH_ARENA_BUDGET, place,", "the filter batch's cut"),
+                      (r"batch_cut\(which\.size\(\), APPLY_MAX_ITEMS, APPLY_MAX_TILES, tiles,", "the apply batch's cut"),
+                      (r"batch_cut\(items\.size\(\), BATCH_MAX_JOINS, BATCH_ARENA_BUDGET, place,", "the join batch's cut"),
+                      (r"d\.out_capacity = d\.nR > d\.nS \? d\.nR : d\.nS;", "the first join call's capacity"),
+                      (r"q\.rc = q\.d_out && plan\.matches > q\.out_capacity \? 1 : 0;", "a batched join's short rule"),
+                      (r"L\.partR = take\(nR \* sizeof\(rhj_tuple\)\);\s*L\.partS = take\(nS \* sizeof\(rhj_tuple\)\);", "batch_place's partitions"),
+                      (r"L\.ovf = take\(fj_ovf_bytes\(BJ_WGS\)\);", "batch_place's overflow regions")):
+        _one(pat, dev, what)
+    budget = 1 << int(_one(r"BATCH_ARENA_BUDGET = \(size_t\)1 << (\d+);", dev, "the arena budget").group(1))
+    # a join's arena is never less than its overflow regions' first term and its two partitioned relations (batch_place has more)
+    ovf = _one(r"fj_ovf_bytes\(size_t wgs\) \{ return wgs \* ([^;+]+) \+", fj, "fj_ovf_bytes").group(1)
+    floor = names["BJ_WGS"] * c_int(ovf.replace("(size_t)", ""), names)
+    return Limits(names["PT_MAX_BITS"], names["MAX_BITS"], names["BJ_MAX_TILES"] * names["SM_TILE"], names["FBATCH_MAX_ROWS"], names["FBATCH_MAX_FILTERS"],
+                  names["APPLY_MAX_ITEMS"], names["RHJ_APPLY_MAX_TERMS"], names["RHJ_FILTER_MAX_TERMS"], names["RHJ_QUERY_MAX_RELS"],
+                  names["RHJ_QUERY_MAX_VIEWS"], budget, floor, 16)
+
+
+LIMITS = parse_limits()
+
+
+def auto_radix_bits(nR, nS):
+    """auto_radix_bits (csrc/rhj_device.hip): the radix order mode "any" picks for a join"""
+    nmin, nmax = min(nR, nS), max(nR, nS)
+    target = 6500 if nmax >= 4 * nmin else 16000
+    b = 0
+    while b < LIMITS.MAX_BITS and (nmin >> b) > target:
+        b += 1
+    while b < LIMITS.PT_MAX_BITS and (nmin >> (b + 1)) >= 512:
+        b += 1
+    if b == 13 and nmax < 4 * nmin and (nmin >> 12) <= 28000:
+        b = 12
+    return max(b, 1)
+
+
+def join_takes(bits=4, small=True, order_any=False):
+    """batch_takes (csrc/rhj_device.hip) at the given settings, as a function of (nR, nS): whether a join of a batch goes into the
+    batched launches.  (Its small_tiles rule, 512 tiles, lies far above the size rule and is not restated.)"""
+    def takes(nR, nS):
+        b = auto_radix_bits(nR, nS) if order_any else bits
+        return bool(small and 1 <= b <= LIMITS.PT_MAX_BITS and nR and nS and max(nR, nS) <= LIMITS.JOIN_MAX_TUPLES)
+    return takes
+
+
+def join_in_size(nR, nS):
+    """batch_takes' size rule alone"""
+    return max(nR, nS) <= LIMITS.JOIN_MAX_TUPLES
+
+
+def filter_takes(rows):
+    return 1 <= rows <= LIMITS.FILTER_MAX_ROWS
+
+
+def join_chunks_at_least(joins):
+    """a lower bound of the chunks the arena cuts a join call's batched items [(nR, nS)] into: every chunk but a one-item one
+    stays within the budget, and a join needs at least JOIN_ARENA_FLOOR bytes and its partitioned relations"""
+    need = sum(LIMITS.JOIN_ARENA_FLOOR + LIMITS.TUPLE_BYTES * (nR + nS) for nR, nS in joins)
+    return -(-need // LIMITS.ARENA_BUDGET)
+
+
+def count_chunks(items, most):
+    """chunks of a call cut by the item count alone"""
+    return -(-items // most)
+
+
+INFO_FIELDS = ("levels", "filter_calls", "eq2_calls", "join_calls", "join_reruns", "apply_calls")
+
+
+def call_counts(cols, queries, takes=None):
+    """What rhj_query_batch_last_info() must say after the batch, as a dict of INFO_FIELDS, from the numpy executor alone, and
+    the detail behind it.  The rules, as the driver has them: a query is alive until it finishes, binds an empty relation, or
+    gets an empty filter, hit list or pair list; a level has an equality call if an alive query's predicate there is inside one
+    node, a join call if one joins two nodes, a second join call if any such join has more pairs than max(nR, nS), and an apply
+    call if any query took part (one whose list then turns out empty still did); level 0 always runs.  takes(nR, nS) is
+    batch_takes at the call's settings (join_takes(); default 4 bits).
+
+    Returns (info, detail).  detail["filters"] is {"items": [(query, binding, rows, hits)], "alone": [positions in items]};
+    detail["levels"][l] is a dict of
+        "eq":     [(query, rows, hits)]            the equality call's items,         "eq_alone":   positions in it that run alone
+        "joins":  [(query, nR, nS, pairs)]         the first join call's items,       "join_alone": positions in it that run alone
+        "short":  positions in "joins" that run again, in the second call's order,    "rerun_alone": positions in "short" that run alone
+        "apply":  [(query, rows, terms)]           the apply call's items"""
+    takes = takes or join_takes()
+    traces = [trace_query(cols, q) for q in queries]
+    alive = [all(len(cols[r][0]) if len(cols[r]) else 0 for r in q[0]) for q in queries]
+    fitems = [(i, b, f[0], f[1]) for i, t in enumerate(traces) if alive[i] for b, f in enumerate(t[2]) if f is not None]
+    info = dict.fromkeys(INFO_FIELDS, 0)
+    info["levels"] = max(len(q[1]) for q in queries)
+    info["filter_calls"] = int(bool(fitems))
+    for i, _, _, hits in fitems:
+        if hits == 0:
+            alive[i] = False
+    detail = {"filters": {"items": fitems, "alone": [k for k, it in enumerate(fitems) if not filter_takes(it[2])]}, "levels": []}
+    for l in range(max(info["levels"], 1)):
+        lv = {"eq": [], "joins": [], "apply": []}
+        active = [i for i, q in enumerate(queries) if alive[i] and (len(q[1]) > l or (l == 0 and not q[1]))]
+        for i in active:
+            rels, joins, _, views = queries[i]
+            _, rows, filtered, steps = traces[i]
+            if not joins:
+                out = rows                               # the views through the binding's own vector
+            else:
+                kind, nA, nB, out = steps[l]
+                if kind == 1:
+                    lv["eq"].append((i, nA, out))
+                else:
+                    lv["joins"].append((i, nA, nB, out))
+            if out == 0:
+                alive[i] = False                         # an empty list: no item
+                continue
+            if not joins or l == len(joins) - 1:
+                terms = len(views)
+                alive[i] = False                         # finished
+            else:                                        # the vectors of every binding of the two nodes
+                node = list(range(len(rels)))
+                for a, _, b, _ in joins[:l]:
+                    node = [node[a] if x == node[b] else x for x in node]
+                a, _, b, _ = joins[l]
+                terms = sum(node[x] in (node[a], node[b]) for x in range(len(rels)))
+            lv["apply"].append((i, out, terms))
+        lv["eq_alone"] = [k for k, it in enumerate(lv["eq"]) if not filter_takes(it[1])]
+        lv["join_alone"] = [k for k, it in enumerate(lv["joins"]) if not takes(it[1], it[2])]
+        lv["short"] = [k for k, it in enumerate(lv["joins"]) if it[3] > max(it[1], it[2])]
+        lv["rerun_alone"] = [k for k, j in enumerate(lv["short"]) if not takes(lv["joins"][j][1], lv["joins"][j][2])]
+        info["eq2_calls"] += bool(lv["eq"])
+        info["join_calls"] += bool(lv["joins"])
+        info["join_reruns"] += bool(lv["short"])
+        info["apply_calls"] += bool(active)
+        detail["levels"].append(lv)
+    return info, detail

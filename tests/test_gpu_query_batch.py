@@ -7,11 +7,10 @@ import importlib
 import numpy as np
 import pytest
 
-from query_model import parse_work, run_query, track_kinds
+from query_model import call_counts, parse_work, run_query, track_kinds
+from query_shapes import CASES, ROWS, synthetic_relations
 
 pytestmark = pytest.mark.gpu
-
-B63 = 1 << 63
 
 
 @pytest.fixture(scope="module")
@@ -36,8 +35,16 @@ def dev(rhj, a):
 
 # ---- the `small` workload ---------------------------------------------------------------------------------------------------------
 
+@pytest.fixture(scope="module")
+def small_counts(golden):
+    """what rhj_query_batch_last_info() must say after the `small` workload, at any radix width and order mode: the counts are of
+    calls, not of launches"""
+    rels = golden.small_relations
+    return call_counts([rels["r%d" % r] for r in range(len(rels))], parse_work(golden.small["work_lines"]))[0]
+
+
 @pytest.mark.parametrize("order", ("4 bits", "any"))
-def test_small_workload_in_one_call(rhj, golden, order):
+def test_small_workload_in_one_call(rhj, golden, small_counts, order):
     rels = golden.small_relations
     cols = [[dev(rhj, c) for c in rels["r%d" % r]] for r in range(len(rels))]
     queries = parse_work(golden.small["work_lines"])
@@ -52,57 +59,19 @@ def test_small_workload_in_one_call(rhj, golden, order):
     assert lines == golden.small["result_lines"]
     assert all((rows == 0) == ("NULL" in line) for (_, rows), line in zip(res, golden.small["result_lines"]))
     assert info["levels"] == 3 and info["filter_calls"] == 1 and info["apply_calls"] == 3
-    assert info["eq2_calls"] <= 3 and info["join_calls"] <= 3 and info["join_reruns"] <= 3
+    assert info == small_counts         # every count, from the numpy executor alone
     assert info["eq2_calls"] >= 1                        # (six of its predicates are equalities inside a node)
     st = rhj.stats()
     assert st["path"] == "query_batch" and st["n_r"] == 50 and st["matches"] == sum(rows for _, rows in res) and st["ms_total"] > 0
 
 
 # ---- synthetic queries ---------------------------------------------------------------------------------------------------------------
-# Relation r has ROWS[r] rows and three columns: c0 a key with many duplicates (a join on it fans out beyond max(nR, nS)), c1
-# unique and near 2^63 (sums wrap), c2 equal to c0 in about half of the rows (the self-join) and a small number otherwise.
-
-ROWS = (1, 100, 5000)
-
+# The relations (1, 100 and 5000 rows) and the 24 CASES live in query_shapes.py: test_gpu_query_batch_edges.py runs them again at
+# other settings.
 
 @pytest.fixture(scope="module")
 def relations():
-    rng = np.random.default_rng(10001)
-    out = []
-    for n in ROWS:
-        c0 = rng.integers(0, max(n // 100, 1) * 5 if n > 1 else 1, size=n, dtype=np.uint64)
-        c1 = rng.permutation(n).astype(np.uint64) + np.uint64(B63)
-        c2 = np.where(rng.integers(0, 2, size=n) == 1, c0, rng.integers(0, 8, size=n, dtype=np.uint64)).astype(np.uint64)
-        out.append([c0, c1, c2])
-    return out
-
-
-CASES = {
-    "no filter": ([1, 2], [(0, 1, 1, 1)], [], [(0, 2), (1, 0)]),
-    "four filters on one binding": ([2, 1], [(0, 1, 1, 1)], [(0, 0, ">", 5), (0, 0, "<", 200), (0, 2, ">", 1), (0, 1, "<", B63 + 4000)], [(0, 2), (1, 2)]),
-    "filters on two bindings": ([1, 2], [(0, 0, 1, 0)], [(0, 1, "<", B63 + 50), (1, 1, "<", B63 + 2500)], [(0, 1), (1, 1), (1, 2)]),
-    "no join, views through a filter": ([2], [], [(0, 0, "=", 7)], [(0, 1), (0, 2)]),
-    "no join, two filters": ([1], [], [(0, 0, "<", 3), (0, 1, ">", B63 + 10)], [(0, 1)]),
-    "no join and no filter": ([2], [], [], [(0, 2), (0, 0), (0, 1)]),
-    "no join and no filter, one row": ([0], [], [], [(0, 1)]),
-    "a filter without a hit": ([1, 2], [(0, 1, 1, 1)], [(1, 0, ">", 100000)], [(0, 0)]),
-    "a filter without a hit, no join": ([1], [], [(0, 0, "=", 99)], [(0, 0), (0, 1)]),
-    "no match at the first level": ([1, 2, 2], [(0, 1, 1, 0), (1, 1, 2, 1)], [], [(0, 0), (2, 2)]),
-    "no match at the last level": ([1, 2, 2], [(0, 1, 1, 1), (1, 1, 2, 0)], [], [(0, 0), (2, 2)]),
-    "a self-join first": ([2, 1], [(0, 0, 0, 2), (0, 1, 1, 1)], [], [(0, 2), (1, 2), (0, 1)]),
-    "a self-join last": ([1, 2], [(0, 1, 1, 1), (1, 0, 1, 2)], [], [(0, 1), (1, 1)]),
-    "a self-join alone": ([2], [(0, 2, 0, 0)], [(0, 1, "<", B63 + 3000)], [(0, 1)]),
-    "a self-join without a match": ([2], [(0, 1, 0, 0)], [], [(0, 1)]),
-    "a relation bound twice": ([2, 2], [(0, 0, 1, 0)], [(0, 1, "<", B63 + 100), (1, 1, "<", B63 + 200)], [(0, 1), (1, 1)]),
-    "a relation bound twice, no filter": ([1, 1], [(0, 0, 1, 0)], [], [(0, 1), (1, 1), (1, 2)]),
-    "two predicates between two bindings": ([1, 2], [(0, 1, 1, 1), (0, 0, 1, 2)], [], [(0, 2), (1, 0)]),
-    "two two-binding nodes merge": ([1, 2, 1, 2], [(0, 1, 1, 1), (2, 1, 3, 1), (1, 0, 2, 0)], [], [(0, 1), (1, 1), (2, 1), (3, 1)]),
-    "two nodes merge, then an equality": ([1, 2, 1, 2], [(0, 1, 1, 1), (2, 1, 3, 1), (1, 0, 2, 0), (0, 2, 3, 2)], [], [(3, 1), (0, 0)]),
-    "eight bindings in a chain": ([1, 2, 1, 2, 1, 2, 1, 2], [(k, 1, k + 1, 1) for k in range(7)], [(7, 0, "<", 40)], [(k, (k + 1) % 3) for k in range(8)]),
-    "one row joins": ([0, 1], [(0, 0, 1, 0)], [], [(0, 1), (1, 1)]),
-    "fan-out on the large relation": ([2, 2], [(0, 0, 1, 0)], [(0, 1, "<", B63 + 300)], [(0, 1), (1, 1), (1, 2)]),
-    "five bindings, four levels": ([1, 2, 2, 1, 2], [(0, 1, 1, 1), (1, 1, 2, 1), (3, 1, 2, 1), (2, 0, 4, 2)], [(4, 1, "<", B63 + 500)], [(4, 1), (0, 2)]),
-}
+    return synthetic_relations()
 
 
 def test_synthetic_queries_against_the_numpy_executor(rhj, relations):
@@ -126,6 +95,7 @@ def test_synthetic_queries_against_the_numpy_executor(rhj, relations):
     for k, got in zip(names, res):
         assert (list(got[0]), got[1]) == (want[k][0], want[k][1]), k
     assert info["levels"] == 7 and info["filter_calls"] == 1 and info["apply_calls"] == 7
+    assert info == call_counts(relations, queries)[0]    # every count, from the numpy executor alone
     assert info["eq2_calls"] >= 2 and info["join_calls"] == 7 and 1 <= info["join_reruns"] <= 7
     assert rhj.stats()["matches"] == sum(want[k][1] for k in names)
 
