@@ -275,6 +275,57 @@ uint64_t rhj_column_stats_flags(uint64_t l, uint64_t u);
 typedef struct rhj_colstats_batch_info { uint32_t chunks, columns; } rhj_colstats_batch_info;   /* of the last call: chunks run, columns that went through them */
 const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void);
 
+/* The row count and the view sums of many final joins in one call, without their pairs (csrc/rhj_join_sum_batch.hip.h): what a
+ * query's last join and the sums behind it need.  Per item, matches and every sum are, as integers, what
+ * rhj_join_cols_batch_device on the same four pointers with enough room, followed by rhj_apply_batch_device over its pairs
+ * (idx_stride 2, the same side, d_src and d_col, d_dst NULL) give: for a join on keyR(i) == keyS(j),
+ *     matches                = sum over keys k of cntR(k) * cntS(k)
+ *     sum of a term, side 0  = sum over i of cntS(keyR(i)) * d_col[d_src ? d_src[i] : i]
+ *     sum of a term, side 1  = sum over j of cntR(keyS(j)) * d_col[d_src ? d_src[j] : j]
+ * which is linear in nR + nS and needs no pair buffer, no capacity and no second call.  Sums are exact modulo 2^64; matches is
+ * exact (below 2^64: a side has fewer than 2^32 rows).  Neither depends on the radix width or the order mode.
+ *
+ * Every item with two non-empty sides runs in the launches of its chunk (path 12): three launches (insert the smaller side's
+ * keys into the item's hash table - R on a tie -, count the other side's, sum) and one stream synchronisation per chunk of at
+ * most 4096 items, 2^24 tiles of 2048 rows and 1 GiB of tables (16 bytes a slot, the smallest power of two of slots that is at
+ * least twice the smaller side's rows), in call order; a chunk takes its first item whatever that needs.  Inputs may be shared
+ * between items, between sides and between terms; every pointer needs 8-byte alignment and no more; the caller guarantees that
+ * every index indexes its array.  An item with an empty side has rc 0, matches 0, sums 0 and path 0 and launches nothing; a
+ * batch of 0 items returns 0 without touching a device.
+ *
+ * The whole batch is validated before anything is launched: a NULL key column with a non-zero size, nterms outside
+ * 0..RHJ_JOIN_SUM_MAX_TERMS, a side outside 0..1, a term with a NULL d_col, or a side of 2^32 rows or more give that item
+ * rc -3; then nothing runs, no matches or sum is written and the call returns -3.  Otherwise 0, or a negative value on a HIP
+ * error.  rhj_last_stats() afterwards: n_r and n_s the rows summed over the items, matches the pairs summed modulo 2^64, units
+ * the items launched, ms_total the whole call (timing level >= 1), reserved 12. */
+#define RHJ_JOIN_SUM_MAX_TERMS 8
+typedef struct rhj_join_sum_term {
+    const uint64_t *d_src;   /* NULL: q = p */
+    const uint64_t *d_col;   /* never NULL */
+    uint64_t        sum;     /* out */
+    int             side;    /* 0: p = i (R's position), 1: p = j (S's position) */
+} rhj_join_sum_term;
+typedef struct rhj_join_sum_desc {
+    const uint64_t *d_colR, *d_selR; uint64_t nR;     /* tuple i of R = { d_colR[d_selR ? d_selR[i] : i], i } */
+    const uint64_t *d_colS, *d_selS; uint64_t nS;
+    int               nterms;                          /* 0 .. RHJ_JOIN_SUM_MAX_TERMS; 0: count only */
+    rhj_join_sum_term terms[RHJ_JOIN_SUM_MAX_TERMS];
+    uint64_t matches;  /* out: number of pairs */
+    int      rc;       /* out */
+    int      path;     /* out: 12, or 0 when nothing was launched */
+} rhj_join_sum_desc;
+int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n);
+
+/* rhj_query_batch_device with the switch on (default off; environment RHJ_QUERY_SUM_LAST=1): a query whose LAST predicate joins
+ * two nodes is, at that level, an item of one rhj_join_sum_batch_device call - the key columns and vectors of its
+ * rhj_join_cols_desc, one term per view - and takes no pair buffer, no second join call and no apply item; sums and rows are
+ * the same.  Everything else keeps its stages.  rhj_query_batch_last_sum_info(): the sum calls and their items of the last
+ * rhj_query_batch_device (all zero with the switch off); with the switch on rhj_query_batch_info counts the pair-list calls
+ * only, and an apply call only for a level where some active query is not a sum item. */
+void rhj_set_query_sum_last(int on);
+typedef struct rhj_query_batch_sum_info { uint32_t sum_calls, sum_items; } rhj_query_batch_sum_info;
+const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

@@ -41,6 +41,7 @@ INTER_SYMBOLS = [
     "InitRelationMap", "FreeRelationMap", "PrintRelationMap", "rhj_column_stats_device", "rhj_apply_batch_device",
     "rhj_filter_eq2_batch_device", "rhj_query_batch_device", "rhj_query_levels", "rhj_query_batch_last_info",
     "rhj_column_stats_batch_device", "rhj_column_stats_flags", "rhj_column_stats_batch_last_info",
+    "rhj_join_sum_batch_device", "rhj_set_query_sum_last", "rhj_query_batch_last_sum_info",
 ]
 
 
@@ -176,6 +177,35 @@ class ColStatsBatchInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+JOIN_SUM_MAX_TERMS = 8                   # RHJ_JOIN_SUM_MAX_TERMS
+
+
+class JoinSumTerm(C.Structure):
+    """rhj_join_sum_term (include/rhj_inter.h): one term of a batched join-sum item"""
+    _fields_ = [("d_src", C.c_void_p), ("d_col", C.c_void_p), ("sum", C.c_uint64), ("side", C.c_int)]
+
+
+class JoinSumDesc(C.Structure):
+    """rhj_join_sum_desc (include/rhj_inter.h): one item of rhj_join_sum_batch_device"""
+    _fields_ = [("d_colR", C.c_void_p), ("d_selR", C.c_void_p), ("nR", C.c_uint64),
+                ("d_colS", C.c_void_p), ("d_selS", C.c_void_p), ("nS", C.c_uint64),
+                ("nterms", C.c_int), ("terms", JoinSumTerm * JOIN_SUM_MAX_TERMS),
+                ("matches", C.c_uint64), ("rc", C.c_int), ("path", C.c_int)]
+
+
+class QueryBatchSumInfo(C.Structure):
+    """rhj_query_batch_sum_info (include/rhj_inter.h): the sum calls the last rhj_query_batch_device issued, and their items"""
+    _fields_ = [("sum_calls", C.c_uint32), ("sum_items", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class QueryInfo(dict):
+    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info() as the dict in its attribute sum_info"""
+    sum_info = None
+
+
 def query_descs(queries):
     """(QueryDesc array, what keeps its pointers alive) of queries = [(relations, joins, filters, views), ...]: relations the
     relation index of every binding, joins [(a, ca, b, cb)], filters [(a, ca, op, value)], views [(a, c)], a and b bindings."""
@@ -201,7 +231,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -302,6 +332,11 @@ def load_library(path=None):
         L.rhj_column_stats_flags.argtypes = [C.c_uint64, C.c_uint64]
         L.rhj_column_stats_flags.restype = C.c_uint64
         L.rhj_column_stats_batch_last_info.restype = C.POINTER(ColStatsBatchInfo)
+    if hasattr(L, "rhj_join_sum_batch_device"):       # (A/B runs load earlier builds through this module too)
+        L.rhj_join_sum_batch_device.argtypes = [C.POINTER(JoinSumDesc), C.c_uint64]
+        L.rhj_set_query_sum_last.argtypes = [C.c_int]
+        L.rhj_set_query_sum_last.restype = None
+        L.rhj_query_batch_last_sum_info.restype = C.POINTER(QueryBatchSumInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -601,6 +636,32 @@ class RHJ:
                         for k, a in enumerate(places[i])])
         return (res, [arr[i].path for i in range(n)]) if with_info else res
 
+    def join_sum_batch_device(self, items, with_info=False):
+        """The row counts and view sums of many final joins in one call, without their pairs (rhj_join_sum_batch_device,
+        include/rhj_inter.h): items = [(colR, selR, colS, selS, terms), ...] as join_cols_batch_device takes the four, with
+        terms = [(side, src or None, col), ...] (0..8 of them; side 0: R's position, 1: S's).  Returns [(matches, sums), ...]:
+        the number of pairs and the wrap-around sums of col[src[p]] over them as Python ints below 2^64.  with_info: also the
+        list of the items' path ids (12: the batched launches, 0: an item with an empty side)."""
+        n = len(items)
+        arr = (JoinSumDesc * max(n, 1))()
+        for d, (cR, sR, cS, sS, terms) in zip(arr, items):
+            if len(terms) > JOIN_SUM_MAX_TERMS:
+                raise ValueError("an item has 0..%d terms, not %d" % (JOIN_SUM_MAX_TERMS, len(terms)))
+            d.d_colR, d.d_selR, d.nR = self._cols_side(cR, sR)
+            d.d_colS, d.d_selS, d.nS = self._cols_side(cS, sS)
+            d.nterms = len(terms)
+            for t, (side, src, col) in zip(d.terms, terms):
+                t.side, t.d_src, t.d_col = int(side), (src.data_ptr() if src is not None else None), col.data_ptr()
+        rc = self.lib.rhj_join_sum_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_join_sum_batch_device failed (%d)" % rc)
+        res = [(arr[i].matches, [arr[i].terms[t].sum for t in range(arr[i].nterms)]) for i in range(n)]
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def set_query_sum_last(self, on):
+        """query_batch_device takes every query's last join as its row count and view sums, without its pairs (default off)"""
+        self.lib.rhj_set_query_sum_last(1 if on else 0)
+
     def filter_eq2_batch_device(self, items, count_only=False, with_info=False):
         """Many two-column equalities in one call (rhj_filter_eq2_batch_device, include/rhj_inter.h): items =
         [(colA, selA, colB, selB, n), ...], int64 tensors, a vector may be None (the column's rows 0..n).  Returns
@@ -628,7 +689,8 @@ class RHJ:
         """A batch of queries run level by level (rhj_query_batch_device, include/rhj_inter.h): cols[r][c] the int64 column
         tensors of relation r, queries = [(relations, joins, filters, views), ...] as query_descs() takes them.  Returns per
         query (sums, rows): the views' wrap-around sums as Python ints below 2^64 and the rows of the final result (0: the
-        reference prints NULL for every view).  with_info: also rhj_query_batch_last_info() as a dict."""
+        reference prints NULL for every view).  with_info: also rhj_query_batch_last_info() as a dict, whose attribute sum_info
+        is rhj_query_batch_last_sum_info() as a dict."""
         rels, keep_rels = self.device_relations(cols)
         arr, keep = query_descs(queries)
         rc = self.lib.rhj_query_batch_device(rels, len(cols), arr, len(queries))
@@ -638,7 +700,11 @@ class RHJ:
             raise RuntimeError("rhj_query_batch_device failed (%d)" % rc)
         del keep_rels, keep
         res = [(list(arr[i].sums[:arr[i].nviews]), arr[i].rows) for i in range(len(queries))]
-        return (res, self.lib.rhj_query_batch_last_info().contents.as_dict()) if with_info else res
+        if not with_info:
+            return res
+        info = QueryInfo(self.lib.rhj_query_batch_last_info().contents.as_dict())
+        info.sum_info = self.lib.rhj_query_batch_last_sum_info().contents.as_dict()
+        return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):
         """The optimiser's statistics of many columns in one call (rhj_column_stats_batch_device, include/rhj_inter.h): cols

@@ -80,6 +80,7 @@ enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSE
     X(summary) X(ucount) X(ubase) X(uflag) X(tab32) X(tab64) X(stash_cnt) X(stash_row) X(status) X(dbg) X(bsum) X(digR)  \
     X(digS) X(ovf) X(ovf_base) X(runR) X(runS) X(walk) X(xrows) X(lr_tmp) X(lr_words) X(lr_status) X(stripR) X(stripS)   \
     X(slice_tot) X(sbase) X(sb_cnt) X(sb_meta) X(sb_map) X(batch_arena) X(batch_desc) X(fbatch_arena) X(stats_arena)      \
+    X(jsum_arena)                                                                                                          \
     X(inR) X(inS) X(out) X(fcol_sel) X(fmask) X(ftile) X(fbase) X(fout)                                                    \
     X(fcol)                                                      /* staging of an unregistered column (host Filter()) */
 
@@ -163,6 +164,7 @@ int g_ndev = 1;                      // devices a join is sharded over (rhj_set_
 int g_ndev_env = 0;                  // RHJ_DEVICES as read at load time (applied by the first call that can shard)
 int g_balance = 0;                   // rhj_join_devices: 1 cuts the bucket ranges by histR + histS instead of equal widths, 2 also cuts INSIDE hot buckets (rhj_set_devices_balance, env RHJ_DEVICES_BALANCE=hist / slice)
 int g_same_device = 0;               // RHJ_DEVICES_SAME=1 (tests): every context on the library's own device — n streams and workspaces on one GPU
+int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
 struct EnvDefaults {
@@ -191,6 +193,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_NO_COUNT_IN_PASS1"))) g.no_count_in_pass1 = atoi(e);
         g.stamps = getenv("RHJ_STAMPS") != nullptr;
         if ((e = getenv("RHJ_TIMING"))) g.timing = atoi(e);
+        if ((e = getenv("RHJ_QUERY_SUM_LAST"))) g_query_sum_last = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1355,7 +1358,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2170,6 +2173,114 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
     return batch_close(timed, st);
 }
 
+// ---- batched final joins: the row count and the view sums without the pairs (rhj_join_sum_batch.hip.h) -------------------------
+// rhj_join_sum_batch_device: every item with two non-empty sides runs in the three launches of its chunk (path 12); there is no
+// run-alone class.  A chunk holds at most JSUM_MAX_ITEMS items and JSUM_MAX_TILES tiles of its third launch (conditions, as the
+// apply batch's) and JSUM_ARENA_BYTES of tables, and a batch beyond any of them is cut in call order: by the first two into
+// groups, a group by the third into chunks.  A chunk takes its first item whatever its table needs.  A chunk is one upload, one
+// memset of its tables, three launches, one copy of its accumulator words and one stream synchronisation; the uploaded block is
+//   [descriptors][items + 1 tile starts of the build sides][of the other sides][of both sides][JSUM_WORDS words an item, zero]
+constexpr size_t JSUM_MAX_ITEMS = 4096;
+constexpr uint64_t JSUM_MAX_TILES = 1ull << 24;
+constexpr uint64_t JSUM_MAX_ROWS = 1ull << 32;            // a side has fewer rows than this: a slot's counts are 32-bit words
+constexpr size_t JSUM_ARENA_BYTES = BATCH_ARENA_BUDGET;
+
+static inline uint64_t jsum_tiles(uint64_t rows) { return (rows + JSUM_TILE - 1) / JSUM_TILE; }
+static inline uint64_t jsum_table_bytes(const rhj_join_sum_desc &q) { return jsum_slots(jsum_build_side(q.nR, q.nS) ? q.nS : q.nR) * JSUM_SLOT_BYTES; }
+
+static bool jsum_valid(const rhj_join_sum_desc &q)
+{
+    if ((q.nR && !q.d_colR) || (q.nS && !q.d_colS) || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
+    if (q.nterms < 0 || q.nterms > RHJ_JOIN_SUM_MAX_TERMS) return false;
+    for (int t = 0; t < q.nterms; ++t)
+        if (q.terms[t].side < 0 || q.terms[t].side > 1 || !q.terms[t].d_col) return false;
+    return true;
+}
+
+// One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
+static int jsum_chunk(rhj_join_sum_desc *items, const uint64_t *which, size_t lo, size_t hi, uint64_t bytes)
+{
+    const size_t ni = hi - lo;
+    if (batch_arena(g.jsum_arena, (size_t)bytes, JSUM_ARENA_BYTES)) return -1;
+    static_assert(sizeof(JoinSumDesc) % 8 == 0, "the tile starts follow the descriptors without padding");
+    Block blk;
+    unsigned long long *back, *words, *d_words; JoinSumDesc *hd, *dd;
+    uint32_t *ts_ins, *d_ts_ins, *ts_cnt, *d_ts_cnt, *ts_sum, *d_ts_sum;
+    const auto pieces = [&](Block &b) {
+        b.back(back, ni * JSUM_WORDS);
+        b.up(hd, dd, ni); b.up(ts_ins, d_ts_ins, ni + 1); b.up(ts_cnt, d_ts_cnt, ni + 1); b.up(ts_sum, d_ts_sum, ni + 1); b.up(words, d_words, ni * JSUM_WORDS);
+    };
+    if (batch_block(blk, pieces)) return -1;
+    memset(words, 0, ni * JSUM_WORDS * 8);
+    uint32_t t_ins = 0, t_cnt = 0, t_sum = 0;
+    size_t at = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const rhj_join_sum_desc &q = items[which[lo + k]];
+        JoinSumDesc d;
+        memset((void *)&d, 0, sizeof(d));
+        d.col[0] = q.d_colR; d.sel[0] = q.d_selR; d.n[0] = q.nR;
+        d.col[1] = q.d_colS; d.sel[1] = q.d_selS; d.n[1] = q.nS;
+        d.build = jsum_build_side(q.nR, q.nS);
+        d.log2_slots = jsum_log2_slots(d.n[d.build]);
+        d.table = (unsigned long long *)((char *)g.jsum_arena.p + at);
+        at += (size_t)jsum_table_bytes(q);
+        d.words = d_words + k * JSUM_WORDS;
+        d.tilesR = (uint32_t)jsum_tiles(q.nR);
+        d.nterms = q.nterms;
+        for (int t = 0; t < q.nterms; ++t) { d.t[t].src = q.terms[t].d_src; d.t[t].col = q.terms[t].d_col; d.t[t].side = q.terms[t].side; }
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        ts_ins[k] = t_ins; ts_cnt[k] = t_cnt; ts_sum[k] = t_sum;
+        t_ins += (uint32_t)jsum_tiles(d.n[d.build]); t_cnt += (uint32_t)jsum_tiles(d.n[d.build ^ 1]); t_sum += (uint32_t)(jsum_tiles(q.nR) + jsum_tiles(q.nS));
+    }
+    ts_ins[ni] = t_ins; ts_cnt[ni] = t_cnt; ts_sum[ni] = t_sum;
+    if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of join sums were placed beyond its arena\n"); return -1; }
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
+    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every count 0
+    RHJ_LAUNCH(k_jsum_insert, dim3(t_ins), dim3(256), 0, g.stream, dd, d_ts_ins, (uint32_t)ni);
+    RHJ_LAUNCH(k_jsum_count, dim3(t_cnt), dim3(256), 0, g.stream, dd, d_ts_cnt, (uint32_t)ni);
+    RHJ_LAUNCH(k_jsum_sum, dim3(t_sum), dim3(256), 0, g.stream, dd, d_ts_sum, (uint32_t)ni);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, d_words, ni * JSUM_WORDS * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < ni; ++k) {
+        rhj_join_sum_desc &q = items[which[lo + k]];
+        const unsigned long long *h = back + k * JSUM_WORDS;
+        q.matches = h[JSUM_W_MATCHES];
+        for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = h[JSUM_W_SUM + t];
+        q.path = PATH_BATCH_JOIN_SUM;
+    }
+    return 0;
+}
+
+static int jsum_batch(rhj_join_sum_desc *items, uint64_t n)
+{
+    static_assert(JSUM_EMPTY == 0, "jsum_chunk clears the tables with a memset of zeros");
+    if (n == 0) return 0;
+    bool timed = false;
+    const auto reset = [](rhj_join_sum_desc &q) { q.rc = 0; q.path = 0; return jsum_valid(q); };      // (no matches or sum is written in a batch that is refused)
+    if (const int rc = batch_open(items, n, reset, timed)) return rc;
+    std::vector<uint64_t> which;
+    uint64_t rowsR = 0, rowsS = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_join_sum_desc &q = items[i];
+        q.matches = 0;
+        for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0;
+        rowsR += q.nR; rowsS += q.nS;
+        if (q.nR && q.nS) which.push_back(i);             // an empty side: no pair, nothing to launch
+    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].nR) + jsum_tiles(items[which[k]].nS); };   // (one item never has more than the limit: jsum_valid)
+    const auto group = [&](size_t lo, size_t hi, uint64_t) {
+        return batch_cut(hi - lo, hi - lo, JSUM_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + jsum_table_bytes(items[which[lo + k]]); },
+                         [&](size_t a, size_t b, uint64_t bytes) { return jsum_chunk(items, which.data() + lo, a, b, bytes); });
+    };
+    if (batch_cut(which.size(), JSUM_MAX_ITEMS, JSUM_MAX_TILES, tiles, group)) return -1;
+    rhj_stats st = {};
+    st.n_r = rowsR; st.n_s = rowsS; st.units = which.size();
+    for (uint64_t i = 0; i < n; ++i) st.matches += items[i].matches;
+    st.reserved = PATH_BATCH_JOIN_SUM;
+    return batch_close(timed, st);
+}
+
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
 // rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
 // equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
@@ -2259,6 +2370,7 @@ struct QueryTimingOff {                                   // the inner batches r
 };
 
 rhj_query_batch_info g_query_info = {};
+rhj_query_batch_sum_info g_query_sum_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
@@ -2266,11 +2378,12 @@ struct QueryRun {                                         // what the stages of 
     uint64_t                        n;
     std::vector<QueryState>         st;
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
-    std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins) ...
-    std::vector<size_t>             where;                // ... and its descriptor in ed / jd
+    std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
+    std::vector<size_t>             where;                // ... and its descriptor in ed / jd / sd
     std::vector<rhj_eq2_desc>       ed;
     std::vector<rhj_join_cols_desc> jd;
     std::vector<rhj_apply_desc>     ad;
+    std::vector<rhj_join_sum_desc>  sd;
     auto column(const rhj_query_desc &q, int b, int c) const { return rels[q.rels[b]].d_columns[c]; }
     bool finishes(uint64_t i, int l) const { return queries[i].njoins == 0 || l == queries[i].njoins - 1; }
 };
@@ -2343,7 +2456,7 @@ static int query_rerun_short(QueryRun &R)
 static int query_level_joins(QueryRun &R, int l)
 {
     QueryBump ib;
-    R.active.clear(); R.kind.clear(); R.where.clear(); R.ed.clear(); R.jd.clear(); R.ad.clear(); R.awho.clear();   // the level before
+    R.active.clear(); R.kind.clear(); R.where.clear(); R.ed.clear(); R.jd.clear(); R.ad.clear(); R.awho.clear(); R.sd.clear();   // the level before
     for (uint64_t i = 0; i < R.n; ++i) {
         const rhj_query_desc &q = R.queries[i];
         const QueryState &s = R.st[i];
@@ -2352,8 +2465,19 @@ static int query_level_joins(QueryRun &R, int l)
         if (q.njoins == 0) { R.kind.push_back(2); R.where.push_back(0); continue; }     // no predicate at all: level 0 sums its views
         const rhj_query_join &p = q.joins[l];
         const TwoNodes two(s, p);
-        R.kind.push_back(two.na == two.nb);
-        if (two.na == two.nb) {                           // the two-column equality over the node's rows
+        const bool as_sums = g_query_sum_last && two.na != two.nb && R.finishes(i, l) && s.rows[two.na] < JSUM_MAX_ROWS && s.rows[two.nb] < JSUM_MAX_ROWS;
+        R.kind.push_back(as_sums ? 3 : two.na == two.nb);
+        if (as_sums) {                                    // the last join: its row count and view sums, no pairs
+            rhj_join_sum_desc d = {};
+            d.d_colR = R.column(q, p.relA, p.colA); d.d_selR = s.vec[p.relA]; d.nR = s.rows[two.na];
+            d.d_colS = R.column(q, p.relB, p.colB); d.d_selS = s.vec[p.relB]; d.nS = s.rows[two.nb];
+            for (int v = 0; v < q.nviews; ++v) {
+                const int x = q.views[v].rel;
+                rhj_join_sum_term &t = d.terms[d.nterms++];
+                t.side = two.side(s, x); t.d_src = s.vec[x]; t.d_col = R.column(q, x, q.views[v].col);
+            }
+            R.where.push_back(R.sd.size()); R.sd.push_back(d);
+        } else if (two.na == two.nb) {                           // the two-column equality over the node's rows
             rhj_eq2_desc d = {};
             d.d_colA = R.column(q, p.relA, p.colA); d.d_selA = s.vec[p.relA];
             d.d_colB = R.column(q, p.relB, p.colB); d.d_selB = s.vec[p.relB];
@@ -2379,7 +2503,12 @@ static int query_level_joins(QueryRun &R, int l)
         ++g_query_info.join_calls;
         const int rc = join_batch(R.jd.data(), R.jd.size());
         if (rc < 0) return rc;
-        if (rc == 1) return query_rerun_short(R);
+        if (rc == 1) if (const int rc2 = query_rerun_short(R)) return rc2;
+    }
+    if (!R.sd.empty()) {
+        ++g_query_sum_info.sum_calls;
+        g_query_sum_info.sum_items += (uint32_t)R.sd.size();
+        if (const int rc = jsum_batch(R.sd.data(), R.sd.size())) return rc;
     }
     return 0;
 }
@@ -2388,10 +2517,19 @@ static int query_level_joins(QueryRun &R, int l)
 static int query_level_apply(QueryRun &R, int l)
 {
     QueryBump vb;
+    size_t sum_items = 0;
     for (size_t a = 0; a < R.active.size(); ++a) {
         const uint64_t i = R.active[a];
-        const rhj_query_desc &q = R.queries[i];
+        rhj_query_desc &q = R.queries[i];
         QueryState &s = R.st[i];
+        if (R.kind[a] == 3) {                             // finished by the sum batch: no item (matches == 0: rows = 0, as an empty list)
+            const rhj_join_sum_desc &d = R.sd[R.where[a]];
+            for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.terms[v].sum;
+            q.rows = d.matches;
+            s.alive = false;
+            ++sum_items;
+            continue;
+        }
         const TwoNodes two(s, q.njoins ? q.joins[l] : rhj_query_join{});       // (no predicate: the one binding, side 0)
         rhj_apply_desc d = {};
         if (R.kind[a] == 2)      { d.n = s.rows[0]; d.idx_stride = 1; }        // the views through the binding's own vector
@@ -2414,7 +2552,7 @@ static int query_level_apply(QueryRun &R, int l)
         }
         R.ad.push_back(d); R.awho.push_back(i);
     }
-    if (R.active.empty()) return 0;                       // nobody alive at this level
+    if (R.active.size() == sum_items) return 0;           // nobody alive at this level, or nobody but the sum batch's queries
     if (vb.resolve(g_qb.level[l], [&](size_t a, int t, char *p) { R.ad[a].terms[t].d_dst = (uint64_t *)p; })) return -1;
     ++g_query_info.apply_calls;
     return apply_batch(R.ad.data(), R.ad.size());         // (0 or an error)
@@ -2448,6 +2586,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     if (n == 0) return 0;
     if (!queries || (nrel > 0 && !rels)) return -1;
     memset(&g_query_info, 0, sizeof(g_query_info));
+    memset(&g_query_sum_info, 0, sizeof(g_query_sum_info));
     bool invalid = false;                                 // the whole batch is validated before a device is touched
     int maxl = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -3034,6 +3173,14 @@ int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_
 }
 int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds) { return query_levels(q, nrel, rels, kinds); }
 const rhj_query_batch_info *rhj_query_batch_last_info(void) { return &g_query_info; }
+const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void) { return &g_query_sum_info; }
+void rhj_set_query_sum_last(int on) { RhjApiLock api_lock; g_query_sum_last = on != 0; }
+
+int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return jsum_batch(items, n);
+}
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */
 

@@ -43,6 +43,8 @@
 //   rhj_eq2_batch.hip.h    many two-column equalities (colA[selA[i]] == colB[selB[i]]) in the same two launches.
 //   rhj_apply_batch.hip.h  many row-id rebuilds and view sums in one launch: an index list applied to up to 8 terms per item.
 //   rhj_stats_batch.hip.h  the statistics of many columns in three launches: min / max, one bit per flag, popcounts.
+//   rhj_join_sum_batch.hip.h  the row counts and view sums of many final joins in three launches, without their pairs: per
+//                          item a table of {key, count of R, count of S}.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -63,4 +65,5 @@
 #include "rhj_eq2_batch.hip.h"
 #include "rhj_apply_batch.hip.h"
 #include "rhj_stats_batch.hip.h"
+#include "rhj_join_sum_batch.hip.h"
 #include "rhj_diag.hip.h"
