@@ -326,6 +326,83 @@ void rhj_set_query_sum_last(int on);
 typedef struct rhj_query_batch_sum_info { uint32_t sum_calls, sum_items; } rhj_query_batch_sum_info;
 const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void);
 
+/* Many weighted join folds in one call (csrc/rhj_join_fold_batch.hip.h): the primitive that sums a query whose join predicates
+ * form a tree over its bindings without any intermediate result.  One item folds a child side S into a parent side R over
+ * keyR(i) == keyS(j), the keys read as rhj_join_sum_desc reads them (d_col[d_sel ? d_sel[p] : p]).  A factor stands for
+ *     f(p) = (d_w ? d_w[p] : 1) * (d_col ? d_col[d_src ? d_src[p] : p] : 1)          (mod 2^64, p the row's position in its side)
+ * The item has nvalues child values V_c, factors over S's positions, and nouts outputs, each a value index c and a factor P
+ * over R's positions:
+ *     A_c(k)      = sum of V_c(j) over the rows j of S with keyS(j) == k
+ *     d_out[i]    = P(i) * A_c(keyR(i))      for i < nR, when d_out is given; 0 where R's key is not in S (written, not left)
+ *     total       = sum over i of P(i) * A_c(keyR(i))
+ * everything exact modulo 2^64.  With every d_w NULL, a value and an output that are plain ones (d_col NULL too) give
+ * rhj_join_sum_batch_device's matches as the total, and an output {NULL, d_src, d_col} on that value its side-0 sum.
+ *
+ * Every item with two non-empty sides runs in the launches of its chunk (path 13): one memset of the chunk's tables, at most
+ * three launches (claim R's keys where R builds, add S's values, apply over R) and one stream synchronisation per chunk of at
+ * most 4096 items, 2^24 tiles of 2048 rows (both sides' together) and 1 GiB of tables (8 * (1 + nvalues) bytes a slot, the
+ * smallest power of two of slots that is at least twice the smaller side's rows; the smaller side claims the slots, R on a
+ * tie), in call order; a chunk takes its first item whatever that needs.  Every pointer needs 8-byte alignment and no more;
+ * inputs may be shared between items, sides and factors; outputs must not overlap each other or any input of the call; nothing
+ * at or beyond d_out[nR] is written; the caller guarantees that every index indexes its array.  An item with an empty side has
+ * rc 0, every total 0 and path 0, its d_outs are untouched and it launches nothing; a batch of 0 items returns 0 without
+ * touching a device.
+ *
+ * The whole batch is validated before anything is launched: a NULL key column with a non-zero size, nvalues outside
+ * 0..RHJ_FOLD_MAX_VALUES, nouts outside 0..RHJ_FOLD_MAX_OUTS, an output whose value index is outside 0..nvalues - 1, or a side
+ * of 2^32 rows or more give that item rc -3; then nothing runs, no total is written and the call returns -3.  Otherwise 0, or a
+ * negative value on a HIP error.  rhj_last_stats() afterwards: n_r and n_s the rows summed over the items, units the items
+ * launched, ms_total the whole call (timing level >= 1), reserved 13. */
+#define RHJ_FOLD_MAX_VALUES 9
+#define RHJ_FOLD_MAX_OUTS   9
+typedef struct rhj_fold_factor {
+    const uint64_t *d_w;     /* NULL: 1 */
+    const uint64_t *d_src;   /* NULL: q = p */
+    const uint64_t *d_col;   /* NULL: 1 (d_src is not read then) */
+} rhj_fold_factor;
+typedef struct rhj_fold_out {
+    rhj_fold_factor p;       /* over R's positions */
+    uint64_t       *d_out;   /* nR words, or NULL: the total only */
+    uint64_t        total;   /* out */
+    int             value;   /* 0 .. nvalues - 1 */
+} rhj_fold_out;
+typedef struct rhj_join_fold_desc {
+    const uint64_t *d_colR, *d_selR; uint64_t nR;     /* the parent side */
+    const uint64_t *d_colS, *d_selS; uint64_t nS;     /* the child side */
+    int             nvalues, nouts;
+    rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
+    rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
+    int rc;                  /* out */
+    int path;                /* out: 13, or 0 when nothing was launched */
+} rhj_join_fold_desc;
+int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n);
+
+/* The fold schedule of one query, a pure function that needs no device.  A query FOLDS when rhj_query_levels accepts it,
+ * njoins >= 1 and every step's kind is 0: each predicate joins two distinct nodes, so the predicates are a spanning tree of the
+ * bindings.  Returns the number of steps (njoins = nrels - 1), 0 for a valid query that does not fold, or -3 (as
+ * rhj_query_levels).  For a folding query *root is the root binding and steps[0 .. njoins) (room for RHJ_QUERY_MAX_RELS - 1) are
+ * the folds, ascending by round, then by child.  The rule: the tree is rooted; a child is folded into its parent only after all
+ * of its own children, in a later round than the last of them; a parent takes one child per round, among several ready children
+ * the lowest binding first; every fold happens in the first round these allow.  The root is the binding that gives the fewest
+ * rounds, on a tie the lowest binding.  root and steps may be NULL. */
+typedef struct rhj_fold_step { int child, parent, round; } rhj_fold_step;
+int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps);
+
+/* rhj_query_batch_device with the switch on (default off; environment RHJ_QUERY_FOLD=1): the filter batch runs as always; then
+ * the folding queries still alive (every binding below 2^32 rows) run round by round, all of them together, each round ONE
+ * rhj_join_fold_batch_device call, before the level loop of the others.  A binding carries its filter's hit list, a weight
+ * vector (the rows of its folded subtree's join that each row meets) and one vector per view of that subtree (the partial view
+ * sum per row); in the root's last fold nothing is written and the totals are rows and sums.  A weight total of 0 finishes the
+ * query with rows = 0 and sums 0.  Folding queries take no pair buffer, no second join call, no apply item and no sum item,
+ * whatever rhj_set_query_sum_last says; the other queries keep their stages and that switch.  sums are the same; rows is exact
+ * MODULO 2^64: the pair route could never exceed memory, this one can exceed 2^64 (eight bindings of 2^31 rows on one key).
+ * rhj_query_batch_last_fold_info(): the fold calls, their items and the queries that folded, of the last
+ * rhj_query_batch_device (all zero with the switch off); with the switch on rhj_query_batch_info counts the calls and levels of
+ * the other queries only (the one filter call serves all). */
+void rhj_set_query_fold(int on);
+typedef struct rhj_query_batch_fold_info { uint32_t fold_calls, fold_items, fold_queries; } rhj_query_batch_fold_info;
+const rhj_query_batch_fold_info *rhj_query_batch_last_fold_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

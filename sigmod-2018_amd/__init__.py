@@ -42,6 +42,7 @@ INTER_SYMBOLS = [
     "rhj_filter_eq2_batch_device", "rhj_query_batch_device", "rhj_query_levels", "rhj_query_batch_last_info",
     "rhj_column_stats_batch_device", "rhj_column_stats_flags", "rhj_column_stats_batch_last_info",
     "rhj_join_sum_batch_device", "rhj_set_query_sum_last", "rhj_query_batch_last_sum_info",
+    "rhj_join_fold_batch_device", "rhj_query_fold_plan", "rhj_set_query_fold", "rhj_query_batch_last_fold_info",
 ]
 
 
@@ -201,9 +202,48 @@ class QueryBatchSumInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FOLD_MAX_VALUES = 9                      # RHJ_FOLD_MAX_VALUES
+FOLD_MAX_OUTS = 9                        # RHJ_FOLD_MAX_OUTS
+
+
+class FoldFactor(C.Structure):
+    """rhj_fold_factor (include/rhj_inter.h): f(p) = (d_w ? d_w[p] : 1) * (d_col ? d_col[d_src ? d_src[p] : p] : 1)"""
+    _fields_ = [("d_w", C.c_void_p), ("d_src", C.c_void_p), ("d_col", C.c_void_p)]
+
+
+class FoldOut(C.Structure):
+    """rhj_fold_out (include/rhj_inter.h): one output of a batched join-fold item"""
+    _fields_ = [("p", FoldFactor), ("d_out", C.c_void_p), ("total", C.c_uint64), ("value", C.c_int)]
+
+
+class JoinFoldDesc(C.Structure):
+    """rhj_join_fold_desc (include/rhj_inter.h): one item of rhj_join_fold_batch_device"""
+    _fields_ = [("d_colR", C.c_void_p), ("d_selR", C.c_void_p), ("nR", C.c_uint64),
+                ("d_colS", C.c_void_p), ("d_selS", C.c_void_p), ("nS", C.c_uint64),
+                ("nvalues", C.c_int), ("nouts", C.c_int),
+                ("values", FoldFactor * FOLD_MAX_VALUES), ("outs", FoldOut * FOLD_MAX_OUTS),
+                ("rc", C.c_int), ("path", C.c_int)]
+
+
+class FoldStep(C.Structure):
+    """rhj_fold_step (include/rhj_inter.h): one fold of rhj_query_fold_plan's schedule"""
+    _fields_ = [("child", C.c_int), ("parent", C.c_int), ("round", C.c_int)]
+
+
+class QueryBatchFoldInfo(C.Structure):
+    """rhj_query_batch_fold_info (include/rhj_inter.h): the fold calls the last rhj_query_batch_device issued, their items and the
+    queries that went through them"""
+    _fields_ = [("fold_calls", C.c_uint32), ("fold_items", C.c_uint32), ("fold_queries", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class QueryInfo(dict):
-    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info() as the dict in its attribute sum_info"""
+    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info() and rhj_query_batch_last_fold_info() as the
+    dicts in its attributes sum_info and fold_info"""
     sum_info = None
+    fold_info = None
 
 
 def query_descs(queries):
@@ -231,7 +271,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -337,6 +377,12 @@ def load_library(path=None):
         L.rhj_set_query_sum_last.argtypes = [C.c_int]
         L.rhj_set_query_sum_last.restype = None
         L.rhj_query_batch_last_sum_info.restype = C.POINTER(QueryBatchSumInfo)
+    if hasattr(L, "rhj_join_fold_batch_device"):
+        L.rhj_join_fold_batch_device.argtypes = [C.POINTER(JoinFoldDesc), C.c_uint64]
+        L.rhj_query_fold_plan.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(C.c_int), C.POINTER(FoldStep)]
+        L.rhj_set_query_fold.argtypes = [C.c_int]
+        L.rhj_set_query_fold.restype = None
+        L.rhj_query_batch_last_fold_info.restype = C.POINTER(QueryBatchFoldInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -662,6 +708,56 @@ class RHJ:
         """query_batch_device takes every query's last join as its row count and view sums, without its pairs (default off)"""
         self.lib.rhj_set_query_sum_last(1 if on else 0)
 
+    def join_fold_batch_device(self, items, with_info=False):
+        """Many weighted join folds in one call (rhj_join_fold_batch_device, include/rhj_inter.h): items =
+        [(colR, selR, colS, selS, values, outs), ...] as join_cols_batch_device takes the four (R the parent side, S the
+        child), values = [(w, src, col), ...] (0..9 factors over S's positions, each of the three an int64 tensor or None) and
+        outs = [(value, (w, src, col), out), ...] (0..9 of them: a value index, a factor over R's positions, and out = None
+        for the total only, True for a vector of this call's, or an int64 tensor of at least nR elements to write into).
+        Returns per item a list of (vector or None, total): d_out[i] = P(i) * A_value(keyR(i)) and its sum, Python ints below
+        2^64.  The vectors this call makes are views of one allocation.  with_info: also the list of the items' path ids (13:
+        the batched launches, 0: an item with an empty side, whose vectors are left as they were)."""
+        torch = self.torch
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        n = len(items)
+        arr = (JoinFoldDesc * max(n, 1))()
+        places, at = [], 0
+        for d, (cR, sR, cS, sS, values, outs) in zip(arr, items):
+            if len(values) > FOLD_MAX_VALUES or len(outs) > FOLD_MAX_OUTS:
+                raise ValueError("an item has 0..%d values and 0..%d outputs, not %d and %d" % (FOLD_MAX_VALUES, FOLD_MAX_OUTS, len(values), len(outs)))
+            d.d_colR, d.d_selR, d.nR = self._cols_side(cR, sR)
+            d.d_colS, d.d_selS, d.nS = self._cols_side(cS, sS)
+            d.nvalues, d.nouts = len(values), len(outs)
+            for f, (w, src, col) in zip(d.values, values):
+                f.d_w, f.d_src, f.d_col = ptr(w), ptr(src), ptr(col)
+            mine = []
+            for o, (value, (w, src, col), out) in zip(d.outs, outs):
+                o.value, o.p.d_w, o.p.d_src, o.p.d_col = int(value), ptr(w), ptr(src), ptr(col)
+                if out is True:
+                    mine.append(at)
+                    at += (d.nR + 1) // 2 * 2                    # 16-byte aligned pieces
+                else:
+                    if out is not None and out.numel() < d.nR:
+                        raise ValueError("an output vector of %d words for %d rows" % (out.numel(), d.nR))
+                    mine.append(out)
+            places.append(mine)
+        buf = torch.zeros(max(at, 1), dtype=torch.int64, device=self.dev)
+        for d, mine in zip(arr, places):
+            for o, a in zip(d.outs, mine):
+                o.d_out = None if a is None else buf.data_ptr() + 8 * a if isinstance(a, int) else a.data_ptr()
+        rc = self.lib.rhj_join_fold_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_join_fold_batch_device failed (%d)" % rc)
+        res = []
+        for d, mine in zip(arr, places):
+            res.append([(None if a is None else buf[a:a + d.nR] if isinstance(a, int) else a[:d.nR], d.outs[k].total) for k, a in enumerate(mine)])
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def set_query_fold(self, on):
+        """query_batch_device sums the queries whose join predicates form a tree over their bindings by rounds of weighted join
+        folds, without any intermediate result (default off); their rows are exact modulo 2^64"""
+        self.lib.rhj_set_query_fold(1 if on else 0)
+
     def filter_eq2_batch_device(self, items, count_only=False, with_info=False):
         """Many two-column equalities in one call (rhj_filter_eq2_batch_device, include/rhj_inter.h): items =
         [(colA, selA, colB, selB, n), ...], int64 tensors, a vector may be None (the column's rows 0..n).  Returns
@@ -689,8 +785,8 @@ class RHJ:
         """A batch of queries run level by level (rhj_query_batch_device, include/rhj_inter.h): cols[r][c] the int64 column
         tensors of relation r, queries = [(relations, joins, filters, views), ...] as query_descs() takes them.  Returns per
         query (sums, rows): the views' wrap-around sums as Python ints below 2^64 and the rows of the final result (0: the
-        reference prints NULL for every view).  with_info: also rhj_query_batch_last_info() as a dict, whose attribute sum_info
-        is rhj_query_batch_last_sum_info() as a dict."""
+        reference prints NULL for every view).  with_info: also rhj_query_batch_last_info() as a dict, whose attributes sum_info
+        and fold_info are rhj_query_batch_last_sum_info() and rhj_query_batch_last_fold_info() as dicts."""
         rels, keep_rels = self.device_relations(cols)
         arr, keep = query_descs(queries)
         rc = self.lib.rhj_query_batch_device(rels, len(cols), arr, len(queries))
@@ -704,6 +800,7 @@ class RHJ:
             return res
         info = QueryInfo(self.lib.rhj_query_batch_last_info().contents.as_dict())
         info.sum_info = self.lib.rhj_query_batch_last_sum_info().contents.as_dict()
+        info.fold_info = self.lib.rhj_query_batch_last_fold_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

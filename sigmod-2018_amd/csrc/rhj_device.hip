@@ -13,6 +13,8 @@
 #include <atomic>
 #include <type_traits>
 #include <vector>
+#include <array>
+#include <climits>
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -164,6 +166,7 @@ int g_ndev = 1;                      // devices a join is sharded over (rhj_set_
 int g_ndev_env = 0;                  // RHJ_DEVICES as read at load time (applied by the first call that can shard)
 int g_balance = 0;                   // rhj_join_devices: 1 cuts the bucket ranges by histR + histS instead of equal widths, 2 also cuts INSIDE hot buckets (rhj_set_devices_balance, env RHJ_DEVICES_BALANCE=hist / slice)
 int g_same_device = 0;               // RHJ_DEVICES_SAME=1 (tests): every context on the library's own device — n streams and workspaces on one GPU
+int g_query_fold = 0;                // 1: rhj_query_batch_device sums the queries whose predicates are a tree by rounds of rhj_join_fold_batch_device items (rhj_set_query_fold, env RHJ_QUERY_FOLD)
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -194,6 +197,7 @@ struct EnvDefaults {
         g.stamps = getenv("RHJ_STAMPS") != nullptr;
         if ((e = getenv("RHJ_TIMING"))) g.timing = atoi(e);
         if ((e = getenv("RHJ_QUERY_SUM_LAST"))) g_query_sum_last = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_FOLD"))) g_query_fold = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1358,7 +1362,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2281,6 +2285,110 @@ static int jsum_batch(rhj_join_sum_desc *items, uint64_t n)
     return batch_close(timed, st);
 }
 
+// ---- batched weighted join folds (rhj_join_fold_batch.hip.h) --------------------------------------------------------------------
+// rhj_join_fold_batch_device: every item with two non-empty sides runs in the launches of its chunk (path 13).  Chunks are cut as
+// the join sums' are (by the tiles of both sides, so that neither the add nor the apply launch's grid passes the limit) and share
+// their arena.  A chunk is one upload, one memset of
+// its tables, at most three launches (the claim launch only when some item's R builds), one copy of its accumulator words and
+// one stream synchronisation; the uploaded block is
+//   [descriptors][items + 1 tile starts of the claim launch][of the add launch][of the apply launch][FOLD_WORDS words an item, zero]
+static inline uint64_t fold_table_bytes(const rhj_join_fold_desc &q) { return jsum_slots(jsum_build_side(q.nR, q.nS) ? q.nS : q.nR) * (uint64_t)(1 + q.nvalues) * 8; }
+
+static bool fold_valid(const rhj_join_fold_desc &q)
+{
+    if ((q.nR && !q.d_colR) || (q.nS && !q.d_colS) || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
+    if (q.nvalues < 0 || q.nvalues > RHJ_FOLD_MAX_VALUES || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS) return false;
+    for (int o = 0; o < q.nouts; ++o)
+        if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
+    return true;
+}
+
+// One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
+static int fold_chunk(rhj_join_fold_desc *items, const uint64_t *which, size_t lo, size_t hi, uint64_t bytes)
+{
+    const size_t ni = hi - lo;
+    if (batch_arena(g.jsum_arena, (size_t)bytes, JSUM_ARENA_BYTES)) return -1;
+    static_assert(sizeof(JoinFoldDesc) % 8 == 0, "the tile starts follow the descriptors without padding");
+    Block blk;
+    unsigned long long *back, *words, *d_words; JoinFoldDesc *hd, *dd;
+    uint32_t *ts_claim, *d_ts_claim, *ts_add, *d_ts_add, *ts_apply, *d_ts_apply;
+    const auto pieces = [&](Block &b) {
+        b.back(back, ni * FOLD_WORDS);
+        b.up(hd, dd, ni); b.up(ts_claim, d_ts_claim, ni + 1); b.up(ts_add, d_ts_add, ni + 1); b.up(ts_apply, d_ts_apply, ni + 1); b.up(words, d_words, ni * FOLD_WORDS);
+    };
+    if (batch_block(blk, pieces)) return -1;
+    memset(words, 0, ni * FOLD_WORDS * 8);
+    uint32_t t_claim = 0, t_add = 0, t_apply = 0;
+    size_t at = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const rhj_join_fold_desc &q = items[which[lo + k]];
+        JoinFoldDesc d;
+        memset((void *)&d, 0, sizeof(d));
+        d.col[0] = q.d_colR; d.sel[0] = q.d_selR; d.n[0] = q.nR;
+        d.col[1] = q.d_colS; d.sel[1] = q.d_selS; d.n[1] = q.nS;
+        d.build = jsum_build_side(q.nR, q.nS);
+        d.log2_slots = jsum_log2_slots(d.n[d.build]);
+        d.slot_words = (uint32_t)(1 + q.nvalues);
+        d.table = (unsigned long long *)((char *)g.jsum_arena.p + at);
+        at += (size_t)fold_table_bytes(q);
+        d.words = d_words + k * FOLD_WORDS;
+        d.nvalues = q.nvalues; d.nouts = q.nouts;
+        for (int c = 0; c < q.nvalues; ++c) d.v[c] = FoldFactor{q.values[c].d_w, q.values[c].d_src, q.values[c].d_col};
+        for (int o = 0; o < q.nouts; ++o) {
+            d.o[o].p = FoldFactor{q.outs[o].p.d_w, q.outs[o].p.d_src, q.outs[o].p.d_col};
+            d.o[o].out = q.outs[o].d_out; d.o[o].value = q.outs[o].value;
+        }
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        ts_claim[k] = t_claim; ts_add[k] = t_add; ts_apply[k] = t_apply;
+        if (d.build == 0) t_claim += (uint32_t)jsum_tiles(q.nR);          // (an item whose S builds has no tile there: fbatch_find passes over it)
+        t_add += (uint32_t)jsum_tiles(q.nS); t_apply += (uint32_t)jsum_tiles(q.nR);
+    }
+    ts_claim[ni] = t_claim; ts_add[ni] = t_add; ts_apply[ni] = t_apply;
+    if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of join folds were placed beyond its arena\n"); return -1; }
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
+    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every A_c 0
+    if (t_claim) RHJ_LAUNCH(k_fold_claim, dim3(t_claim), dim3(256), 0, g.stream, dd, d_ts_claim, (uint32_t)ni);
+    RHJ_LAUNCH(k_fold_add, dim3(t_add), dim3(256), 0, g.stream, dd, d_ts_add, (uint32_t)ni);
+    RHJ_LAUNCH(k_fold_apply, dim3(t_apply), dim3(256), 0, g.stream, dd, d_ts_apply, (uint32_t)ni);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, d_words, ni * FOLD_WORDS * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < ni; ++k) {
+        rhj_join_fold_desc &q = items[which[lo + k]];
+        const unsigned long long *h = back + k * FOLD_WORDS;
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[FOLD_W_TOTAL + o];
+        q.path = PATH_BATCH_JOIN_FOLD;
+    }
+    return 0;
+}
+
+static int fold_batch(rhj_join_fold_desc *items, uint64_t n)
+{
+    static_assert(JSUM_EMPTY == 0, "fold_chunk clears the tables with a memset of zeros");
+    if (n == 0) return 0;
+    bool timed = false;
+    const auto reset = [](rhj_join_fold_desc &q) { q.rc = 0; q.path = 0; return fold_valid(q); };      // (no total is written in a batch that is refused)
+    if (const int rc = batch_open(items, n, reset, timed)) return rc;
+    std::vector<uint64_t> which;
+    uint64_t rowsR = 0, rowsS = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_join_fold_desc &q = items[i];
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0;
+        rowsR += q.nR; rowsS += q.nS;
+        if (q.nR && q.nS) which.push_back(i);             // an empty side: nothing to launch, no d_out touched
+    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].nR) + jsum_tiles(items[which[k]].nS); };   // (both sides': no launch's grid passes the limit; one item never has more: fold_valid)
+    const auto group = [&](size_t lo, size_t hi, uint64_t) {
+        return batch_cut(hi - lo, hi - lo, JSUM_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + fold_table_bytes(items[which[lo + k]]); },
+                         [&](size_t a, size_t b, uint64_t bytes) { return fold_chunk(items, which.data() + lo, a, b, bytes); });
+    };
+    if (batch_cut(which.size(), JSUM_MAX_ITEMS, JSUM_MAX_TILES, tiles, group)) return -1;
+    rhj_stats st = {};
+    st.n_r = rowsR; st.n_s = rowsS; st.units = which.size();
+    st.reserved = PATH_BATCH_JOIN_FOLD;
+    return batch_close(timed, st);
+}
+
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
 // rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
 // equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
@@ -2289,10 +2397,11 @@ static int jsum_batch(rhj_join_sum_desc *items, uint64_t n)
 //   g_qb.idx        the level's index lists (equalities' hits, joins' pairs); dead once the level's apply batch has run
 //   g_qb.idx2       the pairs of the joins run a second time (the first call's lists of the others are still needed)
 //   g_qb.level[l]   the vectors level l rebuilds: read by any later level, so every level has its own
+//   g_qb.fold[r]    the weight and view vectors fold round r writes: read by any later round, so every round has its own
 // They belong to the library's own context (the entry point runs on no other), grow and stay, and go with rhj_release().
 struct QueryWorkspace {
     Buf              filt, idx, idx2;
-    std::vector<Buf> level;
+    std::vector<Buf> level, fold;
     hipEvent_t       ev[2] = {};     // the whole call (its inner batches run untimed); created by the first timed call
 } g_qb;
 
@@ -2301,6 +2410,8 @@ static void query_release()
     for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
     for (Buf &b : g_qb.level) if (b.p) (void)hipFree(b.p);
     g_qb.level.clear();
+    for (Buf &b : g_qb.fold) if (b.p) (void)hipFree(b.p);
+    g_qb.fold.clear();
 }
 
 static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds)
@@ -2371,12 +2482,14 @@ struct QueryTimingOff {                                   // the inner batches r
 
 rhj_query_batch_info g_query_info = {};
 rhj_query_batch_sum_info g_query_sum_info = {};
+rhj_query_batch_fold_info g_query_fold_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
     rhj_query_desc                 *queries;
     uint64_t                        n;
     std::vector<QueryState>         st;
+    std::vector<char>               folds;                // a query that takes the fold route (empty: none does)
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
     std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
     std::vector<size_t>             where;                // ... and its descriptor in ed / jd / sd
@@ -2581,19 +2694,176 @@ static void query_take_back(QueryRun &R, int l)
     }
 }
 
+// ---- the fold route: a query whose predicates are a tree, summed by weighted folds (include/rhj_inter.h) --------
+constexpr int FOLD_MAX_STEPS = RHJ_QUERY_MAX_RELS - 1;
+
+// The schedule of the tree rooted at `root`: steps ascending by round, then by child; returns the rounds.
+static int fold_schedule(const rhj_query_desc &q, int root, rhj_fold_step *steps)
+{
+    const int nb = q.nrels;
+    int parent[RHJ_QUERY_MAX_RELS], waits[RHJ_QUERY_MAX_RELS] = {}, order[RHJ_QUERY_MAX_RELS], seen = 1;
+    bool folded[RHJ_QUERY_MAX_RELS] = {};
+    for (int b = 0; b < nb; ++b) parent[b] = -1;
+    order[0] = root; parent[root] = root;
+    for (int at = 0; at < seen; ++at)                     // breadth first from the root over the predicates
+        for (int l = 0; l < q.njoins; ++l) {
+            const rhj_query_join &p = q.joins[l];
+            const int other = p.relA == order[at] ? p.relB : p.relB == order[at] ? p.relA : -1;
+            if (other < 0 || parent[other] >= 0) continue;
+            parent[other] = order[at]; ++waits[order[at]]; order[seen++] = other;
+        }
+    int nsteps = 0, round = 0;
+    for (; nsteps < nb - 1; ++round) {
+        bool taken[RHJ_QUERY_MAX_RELS] = {};
+        const int first = nsteps;
+        for (int c = 0; c < nb; ++c) {                    // the lowest ready child of every parent (ready by the rounds before this one)
+            if (c == root || folded[c] || waits[c] || taken[parent[c]]) continue;
+            taken[parent[c]] = true;
+            steps[nsteps++] = rhj_fold_step{c, parent[c], round};
+        }
+        for (int k = first; k < nsteps; ++k) { folded[steps[k].child] = true; --waits[steps[k].parent]; }
+    }
+    return round;
+}
+
+static int query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps)
+{
+    if (!q) return -3;
+    std::vector<int> kinds((size_t)(q->njoins > 0 ? q->njoins : 0));
+    const int lv = query_levels(q, nrel, rels, kinds.data());
+    if (lv < 0) return -3;
+    if (lv == 0) return 0;
+    for (int l = 0; l < lv; ++l) if (kinds[l]) return 0;  // an equality inside a node: the predicates are no tree
+    int best = -1, best_root = 0;                         // (every step merged two nodes into one: nrels - 1 predicates, a spanning tree)
+    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
+    for (int r = 0; r < q->nrels; ++r) {
+        const int rounds = fold_schedule(*q, r, mine);
+        if (best >= 0 && rounds >= best) continue;
+        best = rounds; best_root = r;
+        memcpy(kept, mine, sizeof(kept));
+    }
+    if (root) *root = best_root;
+    if (steps) memcpy(steps, kept, (size_t)lv * sizeof(rhj_fold_step));
+    return lv;
+}
+
+struct FoldQuery {                                        // a query on the fold route
+    uint64_t        i;
+    int             root, nsteps, next;                   // next: the first step not yet run
+    rhj_fold_step   steps[FOLD_MAX_STEPS];
+    const uint64_t *w[RHJ_QUERY_MAX_RELS];                // binding -> its weight vector; nullptr: ones
+    const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // binding, view -> the view's partial sums per row, when the binding carries the view
+};
+
+// The folding queries still alive after the filters, round by round: every round is one fold_batch call over all of them.
+static int query_folds(QueryRun &R)
+{
+    std::vector<FoldQuery> fq;
+    int rounds = 0;
+    for (uint64_t i = 0; i < R.n && !R.folds.empty(); ++i) {
+        if (!R.folds[i] || !R.st[i].alive) continue;
+        FoldQuery f = {};
+        f.i = i;
+        f.nsteps = query_fold_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);      // (validated already)
+        if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
+        if (f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
+        fq.push_back(f);
+    }
+    g_query_fold_info.fold_queries = (uint32_t)fq.size();
+    if (g_qb.fold.size() < (size_t)rounds) g_qb.fold.resize((size_t)rounds);
+    std::vector<rhj_join_fold_desc> fd;
+    std::vector<size_t> who;                              // an item's query in fq
+    std::vector<int> par;                                 // an item's parent binding
+    std::vector<std::array<int, RHJ_FOLD_MAX_OUTS>> view; // an item's outputs: the view each belongs to, -1 the weight
+    for (int r = 0; r < rounds; ++r) {
+        QueryBump ob;
+        fd.clear(); who.clear(); par.clear(); view.clear();
+        for (size_t k = 0; k < fq.size(); ++k) {
+            FoldQuery &f = fq[k];
+            const rhj_query_desc &q = R.queries[f.i];
+            const QueryState &s = R.st[f.i];
+            for (; s.alive && f.next < f.nsteps && f.steps[f.next].round == r; ++f.next) {
+                const int S = f.steps[f.next].child, P = f.steps[f.next].parent;
+                const bool last = f.next == f.nsteps - 1;  // the root's last fold: totals only
+                rhj_join_fold_desc d = {};
+                std::array<int, RHJ_FOLD_MAX_OUTS> ov;
+                for (int l = 0; l < q.njoins; ++l) {       // the predicate between the two
+                    const rhj_query_join &p = q.joins[l];
+                    if (p.relA == P && p.relB == S)      { d.d_colR = R.column(q, P, p.colA); d.d_colS = R.column(q, S, p.colB); }
+                    else if (p.relA == S && p.relB == P) { d.d_colR = R.column(q, P, p.colB); d.d_colS = R.column(q, S, p.colA); }
+                }
+                d.d_selR = s.vec[P]; d.nR = s.rows[P];
+                d.d_selS = s.vec[S]; d.nS = s.rows[S];
+                int value_of[RHJ_QUERY_MAX_VIEWS];
+                d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
+                for (int v = 0; v < q.nviews; ++v) {
+                    value_of[v] = -1;
+                    if (q.views[v].rel == S) d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], s.vec[S], R.column(q, S, q.views[v].col)};
+                    else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
+                }
+                const auto out = [&](int value, rhj_fold_factor p, int v) {
+                    if (!last) ob.take(fd.size(), d.nouts, d.nR);
+                    ov[(size_t)d.nouts] = v;
+                    rhj_fold_out &o = d.outs[d.nouts++];
+                    o.value = value; o.p = p;
+                };
+                out(0, rhj_fold_factor{f.w[P], nullptr, nullptr}, -1);                         // the parent's new weight
+                for (int v = 0; v < q.nviews; ++v) {
+                    if (value_of[v] >= 0)                    out(value_of[v], rhj_fold_factor{f.w[P], nullptr, nullptr}, v);      // a view coming from the child
+                    else if (f.acc[P][v])                    out(0, rhj_fold_factor{f.acc[P][v], nullptr, nullptr}, v);           // a view the parent carried
+                    else if (last && q.views[v].rel == P)    out(0, rhj_fold_factor{f.w[P], s.vec[P], R.column(q, P, q.views[v].col)}, v);   // a view on the root: lazy until now
+                }
+                who.push_back(k); par.push_back(P); view.push_back(ov); fd.push_back(d);
+            }
+        }
+        if (fd.empty()) continue;
+        if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { fd[a].outs[o].d_out = (uint64_t *)p; })) return -1;
+        ++g_query_fold_info.fold_calls;
+        g_query_fold_info.fold_items += (uint32_t)fd.size();
+        if (const int rc = fold_batch(fd.data(), fd.size())) return rc;      // (0 or an error: the items are valid)
+        for (size_t a = 0; a < fd.size(); ++a) {
+            FoldQuery &f = fq[who[a]];
+            rhj_query_desc &q = R.queries[f.i];
+            QueryState &s = R.st[f.i];
+            const rhj_join_fold_desc &d = fd[a];
+            if (!s.alive) continue;                       // (finished by another item of this round)
+            if (d.outs[0].total == 0) { s.alive = false; continue; }         // the subtree's join is empty: rows = 0, sums 0
+            const bool last = d.outs[0].d_out == nullptr;
+            if (last) {
+                q.rows = d.outs[0].total;
+                for (int o = 1; o < d.nouts; ++o) q.sums[view[a][(size_t)o]] = d.outs[o].total;
+                s.alive = false;                          // finished
+                continue;
+            }
+            const int P = par[a];                         // the parent's new weight and what it carries now
+            f.w[P] = d.outs[0].d_out;
+            for (int o = 1; o < d.nouts; ++o) f.acc[P][view[a][(size_t)o]] = d.outs[o].d_out;
+        }
+    }
+    return 0;
+}
+
 static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     if (n == 0) return 0;
     if (!queries || (nrel > 0 && !rels)) return -1;
     memset(&g_query_info, 0, sizeof(g_query_info));
     memset(&g_query_sum_info, 0, sizeof(g_query_sum_info));
+    memset(&g_query_fold_info, 0, sizeof(g_query_fold_info));
     bool invalid = false;                                 // the whole batch is validated before a device is touched
     int maxl = 0;
+    std::vector<char> folds;
+    if (g_query_fold) folds.assign(n, 0);
     for (uint64_t i = 0; i < n; ++i) {
         const int lv = query_levels(&queries[i], nrel, rels, nullptr);
         queries[i].rc = lv < 0 ? -3 : 0;
         invalid |= lv < 0;
-        if (lv > maxl) maxl = lv;
+        if (g_query_fold && lv > 0 && query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0) {
+            bool fits = true;                             // a fold's sides have fewer than 2^32 rows
+            for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
+            folds[i] = fits;
+        }
+        if (lv > maxl && !(g_query_fold && folds[i])) maxl = lv;       // (the levels of the queries that run by levels)
     }
     if (invalid) return -3;
     for (uint64_t i = 0; i < n; ++i) { memset(queries[i].sums, 0, sizeof(queries[i].sums)); queries[i].rows = 0; }
@@ -2605,7 +2875,9 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     {
         QueryTimingOff inner_untimed;
         QueryRun R = {rels, queries, n, std::vector<QueryState>(n)};
+        R.folds.swap(folds);
         if (const int rc = query_filters(R)) return rc;
+        if (const int rc = query_folds(R)) return rc;     // the fold route's queries: all finished before the levels
         // the levels.  (Level 0 also runs when no query has a join: the queries without one sum their views in its apply call.)
         if (g_qb.level.size() < (size_t)(maxl > 1 ? maxl : 1)) g_qb.level.resize((size_t)(maxl > 1 ? maxl : 1));
         for (int l = 0; l < maxl || l == 0; ++l) {
@@ -3175,11 +3447,20 @@ int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relatio
 const rhj_query_batch_info *rhj_query_batch_last_info(void) { return &g_query_info; }
 const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void) { return &g_query_sum_info; }
 void rhj_set_query_sum_last(int on) { RhjApiLock api_lock; g_query_sum_last = on != 0; }
+const rhj_query_batch_fold_info *rhj_query_batch_last_fold_info(void) { return &g_query_fold_info; }
+void rhj_set_query_fold(int on) { RhjApiLock api_lock; g_query_fold = on != 0; }
+int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps) { return query_fold_plan(q, nrel, rels, root, steps); }
 
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
     return jsum_batch(items, n);
+}
+
+int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return fold_batch(items, n);
 }
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */

@@ -45,6 +45,8 @@
 //   rhj_stats_batch.hip.h  the statistics of many columns in three launches: min / max, one bit per flag, popcounts.
 //   rhj_join_sum_batch.hip.h  the row counts and view sums of many final joins in three launches, without their pairs: per
 //                          item a table of {key, count of R, count of S}.
+//   rhj_join_fold_batch.hip.h many weighted join folds in three launches: a child side's values summed per key in the same
+//                          table, then multiplied into per-row u64 weights of the parent side.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -66,4 +68,5 @@
 #include "rhj_apply_batch.hip.h"
 #include "rhj_stats_batch.hip.h"
 #include "rhj_join_sum_batch.hip.h"
+#include "rhj_join_fold_batch.hip.h"
 #include "rhj_diag.hip.h"
