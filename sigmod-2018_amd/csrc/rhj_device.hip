@@ -2177,215 +2177,186 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
     return batch_close(timed, st);
 }
 
-// ---- batched final joins: the row count and the view sums without the pairs (rhj_join_sum_batch.hip.h) -------------------------
-// rhj_join_sum_batch_device: every item with two non-empty sides runs in the three launches of its chunk (path 12); there is no
-// run-alone class.  A chunk holds at most JSUM_MAX_ITEMS items and JSUM_MAX_TILES tiles of its third launch (conditions, as the
-// apply batch's) and JSUM_ARENA_BYTES of tables, and a batch beyond any of them is cut in call order: by the first two into
-// groups, a group by the third into chunks.  A chunk takes its first item whatever its table needs.  A chunk is one upload, one
-// memset of its tables, three launches, one copy of its accumulator words and one stream synchronisation; the uploaded block is
-//   [descriptors][items + 1 tile starts of the build sides][of the other sides][of both sides][JSUM_WORDS words an item, zero]
+// ---- the table batches: batched final joins and weighted join folds (rhj_join_sum_batch.hip.h, rhj_join_fold_batch.hip.h) --------
+// rhj_join_sum_batch_device (path 12) and rhj_join_fold_batch_device (path 13) are ONE scheme over two descriptors (templates over
+// rhj_join_sum_desc / rhj_join_fold_desc, as filter_batch is over its two).  Every item with two non-empty sides runs in the
+// launches of its chunk; there is no run-alone class.  Every item has a hash table in the arena g.jsum_arena, which both share.
+// A chunk holds at most JSUM_MAX_ITEMS items and JSUM_MAX_TILES tiles of both sides together, so that no launch's grid passes the
+// limit (conditions, as the apply batch's), and JSUM_ARENA_BYTES of tables, and a batch beyond any of them is cut in call order:
+// by the first two into groups, a group by the third into chunks.  A chunk takes its first item whatever its table needs.  A
+// chunk is one upload, one memset of exactly its tables, three launches (the folds' first only when some item's R builds), one
+// copy of its accumulator words and one stream synchronisation; the uploaded block is
+//   [descriptors][items + 1 tile starts of the first launch][of the second][of the third][the item's accumulator words, zero]
 constexpr size_t JSUM_MAX_ITEMS = 4096;
 constexpr uint64_t JSUM_MAX_TILES = 1ull << 24;
 constexpr uint64_t JSUM_MAX_ROWS = 1ull << 32;            // a side has fewer rows than this: a slot's counts are 32-bit words
 constexpr size_t JSUM_ARENA_BYTES = BATCH_ARENA_BUDGET;
 
 static inline uint64_t jsum_tiles(uint64_t rows) { return (rows + JSUM_TILE - 1) / JSUM_TILE; }
-static inline uint64_t jsum_table_bytes(const rhj_join_sum_desc &q) { return jsum_slots(jsum_build_side(q.nR, q.nS) ? q.nS : q.nR) * JSUM_SLOT_BYTES; }
+template <class D> static inline uint64_t tbatch_slots(const D &q) { return jsum_slots(jsum_build_side(q.nR, q.nS) ? q.nS : q.nR); }
+// a non-empty side has a column, and both sides have fewer than JSUM_MAX_ROWS rows
+template <class D> static inline bool tbatch_sides_valid(const D &q) { return !(q.nR && !q.d_colR) && !(q.nS && !q.d_colS) && q.nR < JSUM_MAX_ROWS && q.nS < JSUM_MAX_ROWS; }
 
-static bool jsum_valid(const rhj_join_sum_desc &q)
+// What differs between the two: the device descriptor and its accumulator words, the validity rule, the results and how they are
+// zeroed and taken, a table's bytes, how a descriptor is filled and what tiles the item adds to the three launches, the three
+// kernels, the path id, the noun of the error text, and whether the statistics count matches.
+template <class D> struct tbatch_dev;
+template <> struct tbatch_dev<rhj_join_sum_desc> { using type = JoinSumDesc; static constexpr size_t words = JSUM_WORDS; };
+template <> struct tbatch_dev<rhj_join_fold_desc> { using type = JoinFoldDesc; static constexpr size_t words = FOLD_WORDS; };
+
+static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
-    if ((q.nR && !q.d_colR) || (q.nS && !q.d_colS) || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
-    if (q.nterms < 0 || q.nterms > RHJ_JOIN_SUM_MAX_TERMS) return false;
+    if (!tbatch_sides_valid(q) || q.nterms < 0 || q.nterms > RHJ_JOIN_SUM_MAX_TERMS) return false;
     for (int t = 0; t < q.nterms; ++t)
         if (q.terms[t].side < 0 || q.terms[t].side > 1 || !q.terms[t].d_col) return false;
     return true;
 }
-
-// One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
-static int jsum_chunk(rhj_join_sum_desc *items, const uint64_t *which, size_t lo, size_t hi, uint64_t bytes)
+static bool tbatch_valid(const rhj_join_fold_desc &q)
 {
-    const size_t ni = hi - lo;
-    if (batch_arena(g.jsum_arena, (size_t)bytes, JSUM_ARENA_BYTES)) return -1;
-    static_assert(sizeof(JoinSumDesc) % 8 == 0, "the tile starts follow the descriptors without padding");
-    Block blk;
-    unsigned long long *back, *words, *d_words; JoinSumDesc *hd, *dd;
-    uint32_t *ts_ins, *d_ts_ins, *ts_cnt, *d_ts_cnt, *ts_sum, *d_ts_sum;
-    const auto pieces = [&](Block &b) {
-        b.back(back, ni * JSUM_WORDS);
-        b.up(hd, dd, ni); b.up(ts_ins, d_ts_ins, ni + 1); b.up(ts_cnt, d_ts_cnt, ni + 1); b.up(ts_sum, d_ts_sum, ni + 1); b.up(words, d_words, ni * JSUM_WORDS);
-    };
-    if (batch_block(blk, pieces)) return -1;
-    memset(words, 0, ni * JSUM_WORDS * 8);
-    uint32_t t_ins = 0, t_cnt = 0, t_sum = 0;
-    size_t at = 0;
-    for (size_t k = 0; k < ni; ++k) {
-        const rhj_join_sum_desc &q = items[which[lo + k]];
-        JoinSumDesc d;
-        memset((void *)&d, 0, sizeof(d));
-        d.col[0] = q.d_colR; d.sel[0] = q.d_selR; d.n[0] = q.nR;
-        d.col[1] = q.d_colS; d.sel[1] = q.d_selS; d.n[1] = q.nS;
-        d.build = jsum_build_side(q.nR, q.nS);
-        d.log2_slots = jsum_log2_slots(d.n[d.build]);
-        d.table = (unsigned long long *)((char *)g.jsum_arena.p + at);
-        at += (size_t)jsum_table_bytes(q);
-        d.words = d_words + k * JSUM_WORDS;
-        d.tilesR = (uint32_t)jsum_tiles(q.nR);
-        d.nterms = q.nterms;
-        for (int t = 0; t < q.nterms; ++t) { d.t[t].src = q.terms[t].d_src; d.t[t].col = q.terms[t].d_col; d.t[t].side = q.terms[t].side; }
-        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
-        ts_ins[k] = t_ins; ts_cnt[k] = t_cnt; ts_sum[k] = t_sum;
-        t_ins += (uint32_t)jsum_tiles(d.n[d.build]); t_cnt += (uint32_t)jsum_tiles(d.n[d.build ^ 1]); t_sum += (uint32_t)(jsum_tiles(q.nR) + jsum_tiles(q.nS));
-    }
-    ts_ins[ni] = t_ins; ts_cnt[ni] = t_cnt; ts_sum[ni] = t_sum;
-    if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of join sums were placed beyond its arena\n"); return -1; }
-    if (batch_upload(blk, hd, blk.host_end())) return -1;
-    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every count 0
-    RHJ_LAUNCH(k_jsum_insert, dim3(t_ins), dim3(256), 0, g.stream, dd, d_ts_ins, (uint32_t)ni);
-    RHJ_LAUNCH(k_jsum_count, dim3(t_cnt), dim3(256), 0, g.stream, dd, d_ts_cnt, (uint32_t)ni);
-    RHJ_LAUNCH(k_jsum_sum, dim3(t_sum), dim3(256), 0, g.stream, dd, d_ts_sum, (uint32_t)ni);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(back, d_words, ni * JSUM_WORDS * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    for (size_t k = 0; k < ni; ++k) {
-        rhj_join_sum_desc &q = items[which[lo + k]];
-        const unsigned long long *h = back + k * JSUM_WORDS;
-        q.matches = h[JSUM_W_MATCHES];
-        for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = h[JSUM_W_SUM + t];
-        q.path = PATH_BATCH_JOIN_SUM;
-    }
-    return 0;
-}
-
-static int jsum_batch(rhj_join_sum_desc *items, uint64_t n)
-{
-    static_assert(JSUM_EMPTY == 0, "jsum_chunk clears the tables with a memset of zeros");
-    if (n == 0) return 0;
-    bool timed = false;
-    const auto reset = [](rhj_join_sum_desc &q) { q.rc = 0; q.path = 0; return jsum_valid(q); };      // (no matches or sum is written in a batch that is refused)
-    if (const int rc = batch_open(items, n, reset, timed)) return rc;
-    std::vector<uint64_t> which;
-    uint64_t rowsR = 0, rowsS = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        rhj_join_sum_desc &q = items[i];
-        q.matches = 0;
-        for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0;
-        rowsR += q.nR; rowsS += q.nS;
-        if (q.nR && q.nS) which.push_back(i);             // an empty side: no pair, nothing to launch
-    }
-    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].nR) + jsum_tiles(items[which[k]].nS); };   // (one item never has more than the limit: jsum_valid)
-    const auto group = [&](size_t lo, size_t hi, uint64_t) {
-        return batch_cut(hi - lo, hi - lo, JSUM_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + jsum_table_bytes(items[which[lo + k]]); },
-                         [&](size_t a, size_t b, uint64_t bytes) { return jsum_chunk(items, which.data() + lo, a, b, bytes); });
-    };
-    if (batch_cut(which.size(), JSUM_MAX_ITEMS, JSUM_MAX_TILES, tiles, group)) return -1;
-    rhj_stats st = {};
-    st.n_r = rowsR; st.n_s = rowsS; st.units = which.size();
-    for (uint64_t i = 0; i < n; ++i) st.matches += items[i].matches;
-    st.reserved = PATH_BATCH_JOIN_SUM;
-    return batch_close(timed, st);
-}
-
-// ---- batched weighted join folds (rhj_join_fold_batch.hip.h) --------------------------------------------------------------------
-// rhj_join_fold_batch_device: every item with two non-empty sides runs in the launches of its chunk (path 13).  Chunks are cut as
-// the join sums' are (by the tiles of both sides, so that neither the add nor the apply launch's grid passes the limit) and share
-// their arena.  A chunk is one upload, one memset of
-// its tables, at most three launches (the claim launch only when some item's R builds), one copy of its accumulator words and
-// one stream synchronisation; the uploaded block is
-//   [descriptors][items + 1 tile starts of the claim launch][of the add launch][of the apply launch][FOLD_WORDS words an item, zero]
-static inline uint64_t fold_table_bytes(const rhj_join_fold_desc &q) { return jsum_slots(jsum_build_side(q.nR, q.nS) ? q.nS : q.nR) * (uint64_t)(1 + q.nvalues) * 8; }
-
-static bool fold_valid(const rhj_join_fold_desc &q)
-{
-    if ((q.nR && !q.d_colR) || (q.nS && !q.d_colS) || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
-    if (q.nvalues < 0 || q.nvalues > RHJ_FOLD_MAX_VALUES || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS) return false;
+    if (!tbatch_sides_valid(q) || q.nvalues < 0 || q.nvalues > RHJ_FOLD_MAX_VALUES || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS) return false;
     for (int o = 0; o < q.nouts; ++o)
         if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
     return true;
 }
 
-// One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
-static int fold_chunk(rhj_join_fold_desc *items, const uint64_t *which, size_t lo, size_t hi, uint64_t bytes)
+static void tbatch_zero(rhj_join_sum_desc &q) { q.matches = 0; for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0; }
+static void tbatch_zero(rhj_join_fold_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
+
+static inline uint64_t tbatch_table_bytes(const rhj_join_sum_desc &q) { return tbatch_slots(q) * JSUM_SLOT_BYTES; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+
+// the fields both device descriptors have
+template <class D, class Dev>
+static void tbatch_common(const D &q, unsigned long long *table, unsigned long long *words, Dev &d)
 {
+    memset((void *)&d, 0, sizeof(d));
+    d.col[0] = q.d_colR; d.sel[0] = q.d_selR; d.n[0] = q.nR;
+    d.col[1] = q.d_colS; d.sel[1] = q.d_selS; d.n[1] = q.nS;
+    d.build = jsum_build_side(q.nR, q.nS);
+    d.log2_slots = jsum_log2_slots(d.n[d.build]);
+    d.table = table; d.words = words;
+}
+
+// fills d and adds the item's tiles to the three launches' counts: the build side's, the other side's, both sides'
+static void tbatch_fill(const rhj_join_sum_desc &q, unsigned long long *table, unsigned long long *words, JoinSumDesc &d, uint32_t (&t)[3])
+{
+    tbatch_common(q, table, words, d);
+    d.tilesR = (uint32_t)jsum_tiles(q.nR);
+    d.nterms = q.nterms;
+    for (int k = 0; k < q.nterms; ++k) { d.t[k].src = q.terms[k].d_src; d.t[k].col = q.terms[k].d_col; d.t[k].side = q.terms[k].side; }
+    t[0] += (uint32_t)jsum_tiles(d.n[d.build]); t[1] += (uint32_t)jsum_tiles(d.n[d.build ^ 1]); t[2] += (uint32_t)(jsum_tiles(q.nR) + jsum_tiles(q.nS));
+}
+// the claim launch's (R's where R builds), the add launch's (S's), the apply launch's (R's)
+static void tbatch_fill(const rhj_join_fold_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldDesc &d, uint32_t (&t)[3])
+{
+    tbatch_common(q, table, words, d);
+    d.slot_words = (uint32_t)(1 + q.nvalues);
+    d.nvalues = q.nvalues; d.nouts = q.nouts;
+    for (int c = 0; c < q.nvalues; ++c) d.v[c] = FoldFactor{q.values[c].d_w, q.values[c].d_src, q.values[c].d_col};
+    for (int o = 0; o < q.nouts; ++o) {
+        d.o[o].p = FoldFactor{q.outs[o].p.d_w, q.outs[o].p.d_src, q.outs[o].p.d_col};
+        d.o[o].out = q.outs[o].d_out; d.o[o].value = q.outs[o].value;
+    }
+    if (d.build == 0) t[0] += (uint32_t)jsum_tiles(q.nR);               // (an item whose S builds has no tile there: fbatch_find passes over it)
+    t[1] += (uint32_t)jsum_tiles(q.nS); t[2] += (uint32_t)jsum_tiles(q.nR);
+}
+
+static void tbatch_launch(const rhj_join_sum_desc &, const JoinSumDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
+{
+    RHJ_LAUNCH(k_jsum_insert, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
+    RHJ_LAUNCH(k_jsum_count, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_jsum_sum, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
+}
+static void tbatch_launch(const rhj_join_fold_desc &, const JoinFoldDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
+{
+    if (t[0]) RHJ_LAUNCH(k_fold_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
+    RHJ_LAUNCH(k_fold_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_fold_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
+}
+
+static void tbatch_take(rhj_join_sum_desc &q, const unsigned long long *h)
+{
+    q.matches = h[JSUM_W_MATCHES];
+    for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = h[JSUM_W_SUM + t];
+}
+static void tbatch_take(rhj_join_fold_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[FOLD_W_TOTAL + o]; }
+
+static inline int tbatch_path(const rhj_join_sum_desc &) { return PATH_BATCH_JOIN_SUM; }
+static inline int tbatch_path(const rhj_join_fold_desc &) { return PATH_BATCH_JOIN_FOLD; }
+static inline const char *tbatch_noun(const rhj_join_sum_desc &) { return "join sums"; }
+static inline const char *tbatch_noun(const rhj_join_fold_desc &) { return "join folds"; }
+static inline uint64_t tbatch_matches(const rhj_join_sum_desc &q) { return q.matches; }
+static inline uint64_t tbatch_matches(const rhj_join_fold_desc &) { return 0; }           // (the folds' statistics have no matches)
+
+// One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
+template <class D>
+static int tbatch_chunk(D *items, const uint64_t *which, size_t lo, size_t hi, uint64_t bytes)
+{
+    using Dev = typename tbatch_dev<D>::type;
+    constexpr size_t WORDS = tbatch_dev<D>::words;
+    static_assert(sizeof(Dev) % 8 == 0, "the tile starts follow the descriptors without padding");
+    static_assert(JSUM_EMPTY == 0, "the tables are cleared with a memset of zeros");
     const size_t ni = hi - lo;
     if (batch_arena(g.jsum_arena, (size_t)bytes, JSUM_ARENA_BYTES)) return -1;
-    static_assert(sizeof(JoinFoldDesc) % 8 == 0, "the tile starts follow the descriptors without padding");
     Block blk;
-    unsigned long long *back, *words, *d_words; JoinFoldDesc *hd, *dd;
-    uint32_t *ts_claim, *d_ts_claim, *ts_add, *d_ts_add, *ts_apply, *d_ts_apply;
+    unsigned long long *back, *words, *d_words; Dev *hd, *dd;
+    uint32_t *ts[3], *d_ts[3];
     const auto pieces = [&](Block &b) {
-        b.back(back, ni * FOLD_WORDS);
-        b.up(hd, dd, ni); b.up(ts_claim, d_ts_claim, ni + 1); b.up(ts_add, d_ts_add, ni + 1); b.up(ts_apply, d_ts_apply, ni + 1); b.up(words, d_words, ni * FOLD_WORDS);
+        b.back(back, ni * WORDS);
+        b.up(hd, dd, ni); b.up(ts[0], d_ts[0], ni + 1); b.up(ts[1], d_ts[1], ni + 1); b.up(ts[2], d_ts[2], ni + 1); b.up(words, d_words, ni * WORDS);
     };
     if (batch_block(blk, pieces)) return -1;
-    memset(words, 0, ni * FOLD_WORDS * 8);
-    uint32_t t_claim = 0, t_add = 0, t_apply = 0;
+    memset(words, 0, ni * WORDS * 8);
+    uint32_t t[3] = {0, 0, 0};
     size_t at = 0;
     for (size_t k = 0; k < ni; ++k) {
-        const rhj_join_fold_desc &q = items[which[lo + k]];
-        JoinFoldDesc d;
-        memset((void *)&d, 0, sizeof(d));
-        d.col[0] = q.d_colR; d.sel[0] = q.d_selR; d.n[0] = q.nR;
-        d.col[1] = q.d_colS; d.sel[1] = q.d_selS; d.n[1] = q.nS;
-        d.build = jsum_build_side(q.nR, q.nS);
-        d.log2_slots = jsum_log2_slots(d.n[d.build]);
-        d.slot_words = (uint32_t)(1 + q.nvalues);
-        d.table = (unsigned long long *)((char *)g.jsum_arena.p + at);
-        at += (size_t)fold_table_bytes(q);
-        d.words = d_words + k * FOLD_WORDS;
-        d.nvalues = q.nvalues; d.nouts = q.nouts;
-        for (int c = 0; c < q.nvalues; ++c) d.v[c] = FoldFactor{q.values[c].d_w, q.values[c].d_src, q.values[c].d_col};
-        for (int o = 0; o < q.nouts; ++o) {
-            d.o[o].p = FoldFactor{q.outs[o].p.d_w, q.outs[o].p.d_src, q.outs[o].p.d_col};
-            d.o[o].out = q.outs[o].d_out; d.o[o].value = q.outs[o].value;
-        }
+        const D &q = items[which[lo + k]];
+        ts[0][k] = t[0]; ts[1][k] = t[1]; ts[2][k] = t[2];
+        Dev d;
+        tbatch_fill(q, (unsigned long long *)((char *)g.jsum_arena.p + at), d_words + k * WORDS, d, t);
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
-        ts_claim[k] = t_claim; ts_add[k] = t_add; ts_apply[k] = t_apply;
-        if (d.build == 0) t_claim += (uint32_t)jsum_tiles(q.nR);          // (an item whose S builds has no tile there: fbatch_find passes over it)
-        t_add += (uint32_t)jsum_tiles(q.nS); t_apply += (uint32_t)jsum_tiles(q.nR);
+        at += (size_t)tbatch_table_bytes(q);
     }
-    ts_claim[ni] = t_claim; ts_add[ni] = t_add; ts_apply[ni] = t_apply;
-    if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of join folds were placed beyond its arena\n"); return -1; }
+    ts[0][ni] = t[0]; ts[1][ni] = t[1]; ts[2][ni] = t[2];
+    if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of %s were placed beyond its arena\n", tbatch_noun(items[which[lo]])); return -1; }
     if (batch_upload(blk, hd, blk.host_end())) return -1;
-    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every A_c 0
-    if (t_claim) RHJ_LAUNCH(k_fold_claim, dim3(t_claim), dim3(256), 0, g.stream, dd, d_ts_claim, (uint32_t)ni);
-    RHJ_LAUNCH(k_fold_add, dim3(t_add), dim3(256), 0, g.stream, dd, d_ts_add, (uint32_t)ni);
-    RHJ_LAUNCH(k_fold_apply, dim3(t_apply), dim3(256), 0, g.stream, dd, d_ts_apply, (uint32_t)ni);
+    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every count and every A_c 0
+    tbatch_launch(items[which[lo]], dd, (uint32_t)ni, d_ts, t);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(back, d_words, ni * FOLD_WORDS * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(back, d_words, ni * WORDS * 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     for (size_t k = 0; k < ni; ++k) {
-        rhj_join_fold_desc &q = items[which[lo + k]];
-        const unsigned long long *h = back + k * FOLD_WORDS;
-        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[FOLD_W_TOTAL + o];
-        q.path = PATH_BATCH_JOIN_FOLD;
+        D &q = items[which[lo + k]];
+        tbatch_take(q, back + k * WORDS);
+        q.path = tbatch_path(q);
     }
     return 0;
 }
 
-static int fold_batch(rhj_join_fold_desc *items, uint64_t n)
+template <class D>
+static int table_batch(D *items, uint64_t n)
 {
-    static_assert(JSUM_EMPTY == 0, "fold_chunk clears the tables with a memset of zeros");
     if (n == 0) return 0;
     bool timed = false;
-    const auto reset = [](rhj_join_fold_desc &q) { q.rc = 0; q.path = 0; return fold_valid(q); };      // (no total is written in a batch that is refused)
+    const auto reset = [](D &q) { q.rc = 0; q.path = 0; return tbatch_valid(q); };      // (no result is written in a batch that is refused)
     if (const int rc = batch_open(items, n, reset, timed)) return rc;
     std::vector<uint64_t> which;
-    uint64_t rowsR = 0, rowsS = 0;
+    rhj_stats st = {};
     for (uint64_t i = 0; i < n; ++i) {
-        rhj_join_fold_desc &q = items[i];
-        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0;
-        rowsR += q.nR; rowsS += q.nS;
-        if (q.nR && q.nS) which.push_back(i);             // an empty side: nothing to launch, no d_out touched
+        D &q = items[i];
+        tbatch_zero(q);
+        st.n_r += q.nR; st.n_s += q.nS;
+        if (q.nR && q.nS) which.push_back(i);             // an empty side: no pair, nothing to launch, no d_out touched
     }
-    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].nR) + jsum_tiles(items[which[k]].nS); };   // (both sides': no launch's grid passes the limit; one item never has more: fold_valid)
+    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].nR) + jsum_tiles(items[which[k]].nS); };   // (one item never has more than the limit: tbatch_sides_valid)
     const auto group = [&](size_t lo, size_t hi, uint64_t) {
-        return batch_cut(hi - lo, hi - lo, JSUM_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + fold_table_bytes(items[which[lo + k]]); },
-                         [&](size_t a, size_t b, uint64_t bytes) { return fold_chunk(items, which.data() + lo, a, b, bytes); });
+        return batch_cut(hi - lo, hi - lo, JSUM_ARENA_BYTES, [&](size_t k, uint64_t bytes) { return bytes + tbatch_table_bytes(items[which[lo + k]]); },
+                         [&](size_t a, size_t b, uint64_t bytes) { return tbatch_chunk(items, which.data() + lo, a, b, bytes); });
     };
     if (batch_cut(which.size(), JSUM_MAX_ITEMS, JSUM_MAX_TILES, tiles, group)) return -1;
-    rhj_stats st = {};
-    st.n_r = rowsR; st.n_s = rowsS; st.units = which.size();
-    st.reserved = PATH_BATCH_JOIN_FOLD;
+    st.units = which.size();
+    for (uint64_t i = 0; i < n; ++i) st.matches += tbatch_matches(items[i]);
+    st.reserved = tbatch_path(items[0]);
     return batch_close(timed, st);
 }
 
@@ -2621,7 +2592,7 @@ static int query_level_joins(QueryRun &R, int l)
     if (!R.sd.empty()) {
         ++g_query_sum_info.sum_calls;
         g_query_sum_info.sum_items += (uint32_t)R.sd.size();
-        if (const int rc = jsum_batch(R.sd.data(), R.sd.size())) return rc;
+        if (const int rc = table_batch(R.sd.data(), R.sd.size())) return rc;
     }
     return 0;
 }
@@ -2755,7 +2726,7 @@ struct FoldQuery {                                        // a query on the fold
     const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // binding, view -> the view's partial sums per row, when the binding carries the view
 };
 
-// The folding queries still alive after the filters, round by round: every round is one fold_batch call over all of them.
+// The folding queries still alive after the filters, round by round: every round is one table_batch call over all of them.
 static int query_folds(QueryRun &R)
 {
     std::vector<FoldQuery> fq;
@@ -2820,7 +2791,7 @@ static int query_folds(QueryRun &R)
         if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { fd[a].outs[o].d_out = (uint64_t *)p; })) return -1;
         ++g_query_fold_info.fold_calls;
         g_query_fold_info.fold_items += (uint32_t)fd.size();
-        if (const int rc = fold_batch(fd.data(), fd.size())) return rc;      // (0 or an error: the items are valid)
+        if (const int rc = table_batch(fd.data(), fd.size())) return rc;      // (0 or an error: the items are valid)
         for (size_t a = 0; a < fd.size(); ++a) {
             FoldQuery &f = fq[who[a]];
             rhj_query_desc &q = R.queries[f.i];
@@ -3454,13 +3425,13 @@ int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_rela
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    return jsum_batch(items, n);
+    return table_batch(items, n);
 }
 
 int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    return fold_batch(items, n);
+    return table_batch(items, n);
 }
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */

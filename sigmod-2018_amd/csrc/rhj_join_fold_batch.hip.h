@@ -15,13 +15,10 @@
 //                                                     atomic add of V_c(j) into the slot; where R builds a miss adds nothing
 //   k_fold_apply    grid = R's tiles of every item:   find the slot once per row; per output load A_c, multiply by P(i),
 //                                                     store (lane = row) and reduce the total
-// The table is rhj_join_sum_batch.hip.h's (jsum_hash, jsum_slots, jsum_build_side, one compare-and-swap to claim a slot, the
-// empty key word) with slots of 1 + nvalues u64 words {key, A_0 ...}: the slot size is per item.  The side that
+// The table and its protocol are rhj_join_sum_batch.hip.h's (jsum_hash, jsum_slots, jsum_build_side, jsum_find, jsum_claim; read
+// there why nobody waits) with slots of 1 + nvalues u64 words {key, A_0 ...}: the slot size is per item.  The side that
 // jsum_build_side names claims the slots, and the slot count comes from that side's rows, so a table is bounded by twice the
-// smaller side's rows.
-//
-// Nobody waits and there are no flags: a key word changes once, from empty; the adds are atomics whose results nobody reads in
-// the same launch; a phase has what it needs by the launch boundary; every probe loop runs at most `slots` steps.
+// smaller side's rows.  The adds into a slot are atomics whose results nobody reads in the same launch.
 //
 // Rows whose key is JSUM_EMPTY never enter the table: S's such rows add their values to nvalues words of the item's own
 // (words FOLD_W_EMPTY + c), R's such rows read those words in the apply launch.
@@ -43,8 +40,7 @@ namespace rhj {
 constexpr int FOLD_W_EMPTY = 0;                      // an item's words: the empty key's A_c ...
 constexpr int FOLD_W_TOTAL = RHJ_FOLD_MAX_VALUES;    // ... then the outputs' totals
 constexpr int FOLD_WORDS = RHJ_FOLD_MAX_VALUES + RHJ_FOLD_MAX_OUTS;
-constexpr uint64_t FOLD_NONE = ~(uint64_t)0;         // no slot: the key is not in the table
-constexpr uint64_t FOLD_OUTSIDE = FOLD_NONE - 1;     // no slot: the empty key, kept in the item's words
+constexpr uint64_t FOLD_OUTSIDE = JSUM_NONE - 1;     // no slot: the empty key, kept in the item's words
 
 struct FoldFactor {
     const uint64_t *w;           // nullptr: 1
@@ -74,36 +70,6 @@ struct JoinFoldDesc {
     FoldOutDesc         o[RHJ_FOLD_MAX_OUTS];
 };
 
-// the slot of `key` (!= JSUM_EMPTY) in a table of `sw` words a slot: found or claimed, at most `slots` steps (a free slot is
-// always met: at most half are taken); FOLD_NONE only if the table were full
-__device__ __forceinline__ uint64_t fold_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
-{
-    const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
-    uint64_t s = jsum_hash(key, log2_slots);
-    for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen == JSUM_EMPTY) {
-            // one exchange; on failure `seen` is the key somebody else put there, which stays
-            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) seen = key;
-        }
-        if (seen == key) return s;
-    }
-    return FOLD_NONE;
-}
-
-// the slot that holds `key` (!= JSUM_EMPTY), or FOLD_NONE: at most `slots` steps
-__device__ __forceinline__ uint64_t fold_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
-{
-    const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
-    uint64_t s = jsum_hash(key, log2_slots);
-    for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-        const uint64_t k = table[sw * s];
-        if (k == key) return s;
-        if (k == JSUM_EMPTY) break;
-    }
-    return FOLD_NONE;
-}
-
 // a factor over the thread's 8 rows: the loads of a stage go out together (pos[k] is in bounds for every k)
 __device__ __forceinline__ void fold_factor(const FoldFactor &f, const uint64_t (&pos)[JSUM_ROUNDS], uint64_t (&v)[JSUM_ROUNDS])
 {
@@ -125,13 +91,6 @@ __device__ __forceinline__ void fold_factor(const FoldFactor &f, const uint64_t 
     }
 }
 
-__device__ __forceinline__ unsigned long long fold_wave_sum(unsigned long long x)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void k_fold_claim(const JoinFoldDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
@@ -146,7 +105,7 @@ __global__ __launch_bounds__(256) void k_fold_claim(const JoinFoldDesc *__restri
 #pragma unroll
     for (int k = 0; k < JSUM_ROUNDS; ++k) {
         if (base + (uint64_t)k * 256 >= n || key[k] == JSUM_EMPTY) continue;
-        (void)fold_claim(table, sw, log2_slots, key[k]);
+        (void)jsum_claim(table, sw, log2_slots, key[k]);
     }
 }
 
@@ -171,10 +130,10 @@ __global__ __launch_bounds__(256) void k_fold_add(const JoinFoldDesc *__restrict
         for (int k = 0; k < JSUM_ROUNDS; ++k) {
             const uint64_t i = base + (uint64_t)k * 256;
             pos[k] = i < n ? i : 0;
-            slot[k] = FOLD_NONE;
+            slot[k] = JSUM_NONE;
             if (i < n) {
                 if (key[k] == JSUM_EMPTY) slot[k] = FOLD_OUTSIDE;
-                else slot[k] = claims ? fold_claim(table, sw, log2_slots, key[k]) : fold_find(table, sw, log2_slots, key[k]);
+                else slot[k] = claims ? jsum_claim(table, sw, log2_slots, key[k]) : jsum_find(table, sw, log2_slots, key[k]);
             }
             const uint64_t have = __ballot(slot[k] < FOLD_OUTSIDE);
             const uint32_t first = have ? (uint32_t)__ffsll((unsigned long long)have) - 1u : 0u;
@@ -192,13 +151,13 @@ __global__ __launch_bounds__(256) void k_fold_add(const JoinFoldDesc *__restrict
             const bool in_table = slot[k] < FOLD_OUTSIDE;
             if (slot[k] == FOLD_OUTSIDE) outside += v[k];
             if (lead[k] < 64u) {                         // (wave-uniform)
-                const unsigned long long sum = fold_wave_sum(in_table ? v[k] : 0);
+                const unsigned long long sum = jsum_wave_sum(in_table ? v[k] : 0);
                 if (lane == lead[k] && sum) __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if (in_table && v[k]) {
                 __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], (unsigned long long)v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        outside = fold_wave_sum(outside);
+        outside = jsum_wave_sum(outside);
         if (lane == 0 && outside) __hip_atomic_fetch_add(&d.words[FOLD_W_EMPTY + c], outside, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -223,8 +182,8 @@ __global__ __launch_bounds__(256) void k_fold_apply(const JoinFoldDesc *__restri
         for (int k = 0; k < JSUM_ROUNDS; ++k) {
             const uint64_t i = base + (uint64_t)k * 256;
             pos[k] = i < n ? i : 0;
-            slot[k] = FOLD_NONE;
-            if (i < n) slot[k] = key[k] == JSUM_EMPTY ? FOLD_OUTSIDE : fold_find(table, sw, log2_slots, key[k]);
+            slot[k] = JSUM_NONE;
+            if (i < n) slot[k] = key[k] == JSUM_EMPTY ? FOLD_OUTSIDE : jsum_find(table, sw, log2_slots, key[k]);
         }
     }
     for (int o = 0; o < nouts; ++o) {
@@ -245,7 +204,7 @@ __global__ __launch_bounds__(256) void k_fold_apply(const JoinFoldDesc *__restri
                 total += x;
             }
         }
-        total = fold_wave_sum(total);
+        total = jsum_wave_sum(total);
         if (lane == 0) part[o][wv] = total;
     }
     __syncthreads();

@@ -43,6 +43,8 @@ constexpr uint64_t JSUM_EMPTY = 0;                   // the key word of an empty
 constexpr uint64_t JSUM_HASH_MUL = 0x9E3779B97F4A7C15ull;       // odd: key -> key * MUL is a bijection of the 64-bit keys
 constexpr uint64_t JSUM_SLOTS_PER_ROW = 2;           // slots >= this many times the build side's rows
 constexpr uint64_t JSUM_SLOT_BYTES = 16;             // {u64 key, u32 build count, u32 other count}
+constexpr uint32_t JSUM_SLOT_WORDS = 2;              // the same in u64 words: what these kernels pass the table's functions
+constexpr uint64_t JSUM_NONE = ~(uint64_t)0;         // no slot: the key is not in the table
 constexpr int JSUM_W_MATCHES = 0, JSUM_W_SUM = 1, JSUM_W_EMPTY = 1 + RHJ_JOIN_SUM_MAX_TERMS;
 constexpr int JSUM_WORDS = 12;                       // an item's accumulator words: matches, the sums, the empty key's rows of R and of S, one spare
 
@@ -59,6 +61,7 @@ constexpr uint64_t jsum_hash(uint64_t key, uint32_t log2_slots) { return (key * 
 // R builds unless S is strictly smaller
 constexpr int jsum_build_side(uint64_t nR, uint64_t nS) { return nS < nR ? 1 : 0; }
 static_assert(jsum_slots(1) == 2 && jsum_slots(1024) == 2048 && jsum_slots(1025) == 4096 && jsum_build_side(5, 5) == 0, "the table's rule");
+static_assert(JSUM_SLOT_WORDS * 8 == JSUM_SLOT_BYTES, "one slot size");
 
 struct JoinSumTermDesc {
     const uint64_t *src;         // nullptr: q = p
@@ -99,24 +102,50 @@ __device__ __forceinline__ void jsum_keys(fb_gcu64 col, fb_gcu64 sel, uint64_t n
     for (int k = 0; k < JSUM_ROUNDS; ++k) key[k] = col[key[k]];
 }
 
-// the slot that holds `key` (!= JSUM_EMPTY), or ~0 when the table has none: at most `slots` steps
-__device__ __forceinline__ uint64_t jsum_find(jsum_gull table, uint32_t log2_slots, uint64_t key)
+// The table's two functions, over slots of `sw` u64 words whose first is the key (`key` != JSUM_EMPTY).
+// jsum_find: the slot that holds `key`, or JSUM_NONE when the table has none: at most `slots` steps
+__device__ __forceinline__ uint64_t jsum_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
     uint64_t s = jsum_hash(key, log2_slots);
     for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-        const uint64_t k = table[2 * s];
+        const uint64_t k = table[sw * s];
         if (k == key) return s;
         if (k == JSUM_EMPTY) break;
     }
-    return ~(uint64_t)0;
+    return JSUM_NONE;
+}
+
+// jsum_claim: the slot of `key`, found or claimed, at most `slots` steps (a free slot is always met: at most half are taken);
+// JSUM_NONE only if the table were full
+__device__ __forceinline__ uint64_t jsum_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
+{
+    const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
+    uint64_t s = jsum_hash(key, log2_slots);
+    for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
+        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == JSUM_EMPTY) {
+            // one exchange; on failure `seen` is the key somebody else put there, which stays
+            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) seen = key;
+        }
+        if (seen == key) return s;
+    }
+    return JSUM_NONE;
+}
+
+// the sum of a wave's 64 values of x, in every lane (T: the 32-bit sums shuffle one register, the 64-bit ones two)
+template <class T>
+__device__ __forceinline__ T jsum_wave_sum(T x)
+{
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
+    return x;
 }
 
 // adds a side's rows with the empty key to the item's word of that side: one atomic a wave
 __device__ __forceinline__ void jsum_count_empty(unsigned long long *words, int side, uint32_t mine)
 {
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) mine += __shfl_xor(mine, x, 64);
+    mine = jsum_wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) __hip_atomic_fetch_add(&words[JSUM_W_EMPTY + side], (unsigned long long)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -129,7 +158,6 @@ __global__ __launch_bounds__(256) void k_jsum_insert(const JoinSumDesc *__restri
     const uint64_t n = d.n[side];
     const uint64_t base = (uint64_t)tile * JSUM_TILE + threadIdx.x;
     const uint32_t log2_slots = d.log2_slots;
-    const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
     const jsum_gull table = (jsum_gull)d.table;
     uint64_t key[JSUM_ROUNDS];
     jsum_keys((fb_gcu64)d.col[side], (fb_gcu64)d.sel[side], n, base, key);
@@ -139,18 +167,8 @@ __global__ __launch_bounds__(256) void k_jsum_insert(const JoinSumDesc *__restri
         if (base + (uint64_t)k * 256 >= n) continue;
         const uint64_t mine = key[k];
         if (mine == JSUM_EMPTY) { ++empty; continue; }
-        uint64_t s = jsum_hash(mine, log2_slots);
-        for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {      // (a free slot is always met: at most half are taken)
-            unsigned long long seen = __hip_atomic_load(&table[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (seen == JSUM_EMPTY) {
-                // one exchange; on failure `seen` is the key somebody else put there, which stays
-                if (__hip_atomic_compare_exchange_strong(&table[2 * s], &seen, (unsigned long long)mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) seen = mine;
-            }
-            if (seen == mine) {
-                __hip_atomic_fetch_add((jsum_gu32)(table + 2 * s + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        const uint64_t s = jsum_claim(table, JSUM_SLOT_WORDS, log2_slots, mine);
+        if (s != JSUM_NONE) __hip_atomic_fetch_add((jsum_gu32)(table + JSUM_SLOT_WORDS * s + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     jsum_count_empty(d.words, side, empty);
 }
@@ -173,8 +191,8 @@ __global__ __launch_bounds__(256) void k_jsum_count(const JoinSumDesc *__restric
         if (base + (uint64_t)k * 256 >= n) continue;
         const uint64_t mine = key[k];
         if (mine == JSUM_EMPTY) { ++empty; continue; }
-        const uint64_t s = jsum_find(table, log2_slots, mine);
-        if (s != ~(uint64_t)0) __hip_atomic_fetch_add((jsum_gu32)(table + 2 * s + 1) + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t s = jsum_find(table, JSUM_SLOT_WORDS, log2_slots, mine);
+        if (s != JSUM_NONE) __hip_atomic_fetch_add((jsum_gu32)(table + JSUM_SLOT_WORDS * s + 1) + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     jsum_count_empty(d.words, side, empty);
 }
@@ -204,15 +222,14 @@ __global__ __launch_bounds__(256) void k_jsum_sum(const JoinSumDesc *__restrict_
         if (base + (uint64_t)k * 256 >= n) continue;
         const uint64_t mine = key[k];
         if (mine == JSUM_EMPTY) { w[k] = w_empty; continue; }
-        const uint64_t s = jsum_find(table, log2_slots, mine);
-        if (s != ~(uint64_t)0) w[k] = ((jsum_gu32)(table + 2 * s + 1))[opposite];
+        const uint64_t s = jsum_find(table, JSUM_SLOT_WORDS, log2_slots, mine);
+        if (s != JSUM_NONE) w[k] = ((jsum_gu32)(table + JSUM_SLOT_WORDS * s + 1))[opposite];
     }
     if (side == 0) {
         unsigned long long m = 0;
 #pragma unroll
         for (int k = 0; k < JSUM_ROUNDS; ++k) m += w[k];
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) m += __shfl_xor(m, x, 64);
+        m = jsum_wave_sum(m);
         if (lane == 0) part[0][wv] = m;
     }
     for (int t = 0; t < nterms; ++t) {
@@ -233,8 +250,7 @@ __global__ __launch_bounds__(256) void k_jsum_sum(const JoinSumDesc *__restrict_
         unsigned long long s = 0;
 #pragma unroll
         for (int k = 0; k < JSUM_ROUNDS; ++k) s += w[k] * v[k];          // (w = 0 out of bounds)
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) s += __shfl_xor(s, x, 64);
+        s = jsum_wave_sum(s);
         if (lane == 0) part[1 + t][wv] = s;
     }
     __syncthreads();

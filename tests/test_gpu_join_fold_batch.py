@@ -359,3 +359,48 @@ def test_tables_of_half_the_arena_cut_after_two(rhj):
     outputs = Outputs(rhj, items)
     got, paths = rhj.join_fold_batch_device(outputs.args(dev, items), with_info=True)
     check(items, outputs, got, paths)
+
+
+def test_both_table_batches_share_one_arena(rhj):
+    """three calls in one process with nothing released between them: (a) 64 folds of 2049 x 4097 rows with nine values leave
+    the arena full of 80-byte slots whose words are not zero; (b) three join sums and then (c) two folds with one value place
+    16-byte slots over them.  A chunk clears exactly the tables it placed, so (b) and (c) must read none of what (a) left.
+    Keys are drawn from [0, 60), the empty key on every side of more than one row; the sizes sit on the 2048-row tile and on the tie
+    of the build side.  (c)'s one value is 0 in every row ("zero values": an item without a value can have no output), so a
+    single word of (a) read as an A_c shows in a d_out, all of whose words must be written zeros."""
+    rng = np.random.default_rng(64)
+    dev = Device(rhj)
+
+    def keys(n):
+        k = u64(rng.integers(0, 60, size=n))
+        if n > 1:
+            k[int(rng.integers(0, n))] = jm.EMPTY
+        return k
+    # (a)
+    weights = [u64(rng.integers(1, 1 << 63, size=4097)) * np.uint64(2) + np.uint64(1) for _ in range(3)]
+    src = u64(rng.permutation(4097))
+    nine = [ONES] + [(weights[c % 3], src if c % 2 else None, weights[(c + 1) % 3] if c >= 4 else None) for c in range(1, fm.MAX_VALUES)]
+    outs = [(0, ONES, True), (fm.MAX_VALUES - 1, (weights[0][:2049], None, None), True), (4, ONES, False)]
+    folds = [make("2049x4097 #%d" % k, keys(2049), None, keys(4097), None, nine, outs) for k in range(64)]
+    assert len(nine) == fm.MAX_VALUES and 64 * (80 << jm.table_log2(2049, 4097)) < jm.ARENA_BYTES      # one chunk
+    outputs = Outputs(rhj, folds)
+    got, paths = rhj.join_fold_batch_device(outputs.args(dev, folds), with_info=True)
+    check(folds, outputs, got, paths)
+    assert all(t != 0 for g in got for _, t in g)
+    # (b)
+    cols = [u64(rng.integers(0, 1 << 63, size=2048)) * np.uint64(2) + np.uint64(1) for _ in range(2)]
+    sums, want = [], []
+    for nR, nS in ((300, 900), (900, 300), (2048, 2048)):
+        kR, kS = keys(nR), keys(nS)
+        sums.append((dev(kR), None, dev(kS), None, [(0, None, dev(cols[0])), (1, None, dev(cols[1]))]))
+        want.append(jm.join_sum(kR, kS, [(0, cols[0][:nR]), (1, cols[1][:nS])]))
+    assert [(m, list(s)) for m, s in rhj.join_sum_batch_device(sums)] == [(m, list(s)) for m, s in want]
+    assert rhj.stats()["path"] == "join_sum_batch" and rhj.stats()["matches"] == sum(m for m, _ in want) & M64
+    # (c)
+    zeros = u64(np.zeros(2048))
+    last = [make("1x1", keys(1), None, keys(1), None, [(zeros[:1], None, None)], [(0, ONES, True)]),
+            make("2049x2048", keys(2049), None, keys(2048), None, [(zeros, None, None)], [(0, ONES, True)])]
+    outputs = Outputs(rhj, last)
+    got, paths = rhj.join_fold_batch_device(outputs.args(dev, last), with_info=True)
+    want = check(last, outputs, got, paths)
+    assert all(t == 0 and not vec.any() for w in want for vec, t in w)
