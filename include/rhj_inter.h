@@ -403,6 +403,51 @@ void rhj_set_query_fold(int on);
 typedef struct rhj_query_batch_fold_info { uint32_t fold_calls, fold_items, fold_queries; } rhj_query_batch_fold_info;
 const rhj_query_batch_fold_info *rhj_query_batch_last_fold_info(void);
 
+/* rhj_join_fold_batch_device on TUPLE keys (csrc/rhj_join_foldk_batch.hip.h): an item is rhj_join_fold_desc's with nkeys key
+ * columns a side, 1 .. RHJ_FOLD_MAX_KEYS, all of a side read through its one d_sel, and keyR(i) == keyS(j) is the equality of all
+ * nkeys words, word t of R against word t of S.  Values, outputs, totals and everything about chunks, tables (8 * (1 + nvalues)
+ * bytes a slot), alignment, overlap and empty sides are as there; the path is 14.  No key value is special.  A slot's first word
+ * holds the position of the build side's row that claimed it (and hash bits), not a key: whoever meets a taken slot compares its
+ * words with that row's, read from the build side's own columns.
+ *
+ * Validation as for the fold batch; in addition nkeys outside 1..RHJ_FOLD_MAX_KEYS, or a NULL column among the first nkeys of a
+ * side with rows, gives that item rc -3 before anything runs.  rhj_last_stats() afterwards as there, reserved 14. */
+#define RHJ_FOLD_MAX_KEYS 4
+typedef struct rhj_join_foldk_desc {
+    int             nkeys;                             /* 1 .. RHJ_FOLD_MAX_KEYS */
+    const uint64_t *d_colR[RHJ_FOLD_MAX_KEYS], *d_selR; uint64_t nR;     /* the parent side */
+    const uint64_t *d_colS[RHJ_FOLD_MAX_KEYS], *d_selS; uint64_t nS;     /* the child side */
+    int             nvalues, nouts;
+    rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
+    rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
+    int rc;                  /* out */
+    int path;                /* out: 14, or 0 when nothing was launched */
+} rhj_join_foldk_desc;
+int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n);
+
+/* The fold schedule of one query with its parallel predicates grouped, a pure function that needs no device.  The rule:
+ * rhj_query_levels must accept the query (else -3) and njoins >= 1; a predicate whose two sides are the same binding gives 0; a
+ * predicate that equals an earlier one, the same two (binding, column) terms written either way round, is dropped; the rest are
+ * grouped by unordered binding pair; a group of more than RHJ_FOLD_MAX_KEYS gives 0; the groups must be exactly nrels - 1 (they
+ * connect all bindings then: a spanning tree), else 0.  Schedule and root are rhj_query_fold_plan's over the groups.  A step's
+ * joins[0 .. nkeys) are the indices into q->joins of its kept predicates, ascending; key word t of the parent is predicate
+ * joins[t]'s column on the parent's binding, of the child its column on the child's, whichever way round it was written.  Returns
+ * nrels - 1, 0 or -3.  For every query rhj_query_fold_plan accepts the root and every step's child, parent and round are the same
+ * and nkeys is 1.  root and steps (room for RHJ_QUERY_MAX_RELS - 1) may be NULL. */
+typedef struct rhj_foldk_step { int child, parent, round, nkeys; int joins[RHJ_FOLD_MAX_KEYS]; } rhj_foldk_step;
+int rhj_query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps);
+
+/* rhj_query_batch_device with this switch on as well as rhj_set_query_fold (default off; environment RHJ_QUERY_FOLD_KEYS=1; no
+ * effect while the fold route is off): a query folds when rhj_query_foldk_plan > 0.  In a round the items with one key are ONE
+ * rhj_join_fold_batch_device call, exactly as with the switch off, and the items with two or more keys ONE
+ * rhj_join_foldk_batch_device call: at most two calls a round.  A binding's state, a fold's values and outputs, the round
+ * buffers, the zero-total exit and the 2^64 limit are the fold route's.  rhj_query_batch_last_foldk_info(): the tuple-key calls
+ * and their items, and the queries that fold only because of this switch and were alive after the filters (all zero with either
+ * switch off); rhj_query_batch_fold_info keeps counting the single-key calls and items, and all folding queries. */
+void rhj_set_query_fold_keys(int on);
+typedef struct rhj_query_batch_foldk_info { uint32_t foldk_calls, foldk_items, foldk_queries; } rhj_query_batch_foldk_info;
+const rhj_query_batch_foldk_info *rhj_query_batch_last_foldk_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

@@ -43,6 +43,7 @@ INTER_SYMBOLS = [
     "rhj_column_stats_batch_device", "rhj_column_stats_flags", "rhj_column_stats_batch_last_info",
     "rhj_join_sum_batch_device", "rhj_set_query_sum_last", "rhj_query_batch_last_sum_info",
     "rhj_join_fold_batch_device", "rhj_query_fold_plan", "rhj_set_query_fold", "rhj_query_batch_last_fold_info",
+    "rhj_join_foldk_batch_device", "rhj_query_foldk_plan", "rhj_set_query_fold_keys", "rhj_query_batch_last_foldk_info",
 ]
 
 
@@ -239,11 +240,39 @@ class QueryBatchFoldInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FOLD_MAX_KEYS = 4                        # RHJ_FOLD_MAX_KEYS
+
+
+class JoinFoldKDesc(C.Structure):
+    """rhj_join_foldk_desc (include/rhj_inter.h): one item of rhj_join_foldk_batch_device"""
+    _fields_ = [("nkeys", C.c_int),
+                ("d_colR", C.c_void_p * FOLD_MAX_KEYS), ("d_selR", C.c_void_p), ("nR", C.c_uint64),
+                ("d_colS", C.c_void_p * FOLD_MAX_KEYS), ("d_selS", C.c_void_p), ("nS", C.c_uint64),
+                ("nvalues", C.c_int), ("nouts", C.c_int),
+                ("values", FoldFactor * FOLD_MAX_VALUES), ("outs", FoldOut * FOLD_MAX_OUTS),
+                ("rc", C.c_int), ("path", C.c_int)]
+
+
+class FoldKStep(C.Structure):
+    """rhj_foldk_step (include/rhj_inter.h): one fold of rhj_query_foldk_plan's schedule"""
+    _fields_ = [("child", C.c_int), ("parent", C.c_int), ("round", C.c_int), ("nkeys", C.c_int), ("joins", C.c_int * FOLD_MAX_KEYS)]
+
+
+class QueryBatchFoldKInfo(C.Structure):
+    """rhj_query_batch_foldk_info (include/rhj_inter.h): the tuple-key fold calls the last rhj_query_batch_device issued, their
+    items and the queries that folded only because of rhj_set_query_fold_keys"""
+    _fields_ = [("foldk_calls", C.c_uint32), ("foldk_items", C.c_uint32), ("foldk_queries", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class QueryInfo(dict):
-    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info() and rhj_query_batch_last_fold_info() as the
-    dicts in its attributes sum_info and fold_info"""
+    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info(), rhj_query_batch_last_fold_info() and
+    rhj_query_batch_last_foldk_info() as the dicts in its attributes sum_info, fold_info and foldk_info"""
     sum_info = None
     fold_info = None
+    foldk_info = None
 
 
 def query_descs(queries):
@@ -271,7 +300,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -383,6 +412,12 @@ def load_library(path=None):
         L.rhj_set_query_fold.argtypes = [C.c_int]
         L.rhj_set_query_fold.restype = None
         L.rhj_query_batch_last_fold_info.restype = C.POINTER(QueryBatchFoldInfo)
+    if hasattr(L, "rhj_join_foldk_batch_device"):     # (A/B runs load earlier builds through this module too)
+        L.rhj_join_foldk_batch_device.argtypes = [C.POINTER(JoinFoldKDesc), C.c_uint64]
+        L.rhj_query_foldk_plan.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(C.c_int), C.POINTER(FoldKStep)]
+        L.rhj_set_query_fold_keys.argtypes = [C.c_int]
+        L.rhj_set_query_fold_keys.restype = None
+        L.rhj_query_batch_last_foldk_info.restype = C.POINTER(QueryBatchFoldKInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -708,6 +743,17 @@ class RHJ:
         """query_batch_device takes every query's last join as its row count and view sums, without its pairs (default off)"""
         self.lib.rhj_set_query_sum_last(1 if on else 0)
 
+    def join_foldk_batch_device(self, items, with_info=False):
+        """join_fold_batch_device on tuple keys (rhj_join_foldk_batch_device, include/rhj_inter.h): items as there, but colR and
+        colS are lists of 1..4 key columns, word t of R against word t of S, all of a side read through its one row-id vector.
+        Path id 14."""
+        return self._fold_batch(JoinFoldKDesc, "rhj_join_foldk_batch_device", items, with_info)
+
+    def set_query_fold_keys(self, on):
+        """with set_query_fold: the queries whose predicates are a tree once several predicates between two bindings are read as
+        one join on a tuple of columns fold too (default off)"""
+        self.lib.rhj_set_query_fold_keys(1 if on else 0)
+
     def join_fold_batch_device(self, items, with_info=False):
         """Many weighted join folds in one call (rhj_join_fold_batch_device, include/rhj_inter.h): items =
         [(colR, selR, colS, selS, values, outs), ...] as join_cols_batch_device takes the four (R the parent side, S the
@@ -717,16 +763,28 @@ class RHJ:
         Returns per item a list of (vector or None, total): d_out[i] = P(i) * A_value(keyR(i)) and its sum, Python ints below
         2^64.  The vectors this call makes are views of one allocation.  with_info: also the list of the items' path ids (13:
         the batched launches, 0: an item with an empty side, whose vectors are left as they were)."""
+        return self._fold_batch(JoinFoldDesc, "rhj_join_fold_batch_device", items, with_info)
+
+    def _fold_batch(self, Desc, entry, items, with_info):
+        """the two fold batches: their items differ in the key columns alone"""
         torch = self.torch
         ptr = lambda t: t.data_ptr() if t is not None else None
         n = len(items)
-        arr = (JoinFoldDesc * max(n, 1))()
+        arr = (Desc * max(n, 1))()
         places, at = [], 0
         for d, (cR, sR, cS, sS, values, outs) in zip(arr, items):
             if len(values) > FOLD_MAX_VALUES or len(outs) > FOLD_MAX_OUTS:
                 raise ValueError("an item has 0..%d values and 0..%d outputs, not %d and %d" % (FOLD_MAX_VALUES, FOLD_MAX_OUTS, len(values), len(outs)))
-            d.d_colR, d.d_selR, d.nR = self._cols_side(cR, sR)
-            d.d_colS, d.d_selS, d.nS = self._cols_side(cS, sS)
+            if Desc is JoinFoldKDesc:
+                if not 1 <= len(cR) <= FOLD_MAX_KEYS or len(cS) != len(cR):
+                    raise ValueError("an item has 1..%d key columns a side, as many on both, not %d and %d" % (FOLD_MAX_KEYS, len(cR), len(cS)))
+                d.nkeys = len(cR)
+                for t, (a, b) in enumerate(zip(cR, cS)):
+                    d.d_colR[t], d.d_selR, d.nR = self._cols_side(a, sR)
+                    d.d_colS[t], d.d_selS, d.nS = self._cols_side(b, sS)
+            else:
+                d.d_colR, d.d_selR, d.nR = self._cols_side(cR, sR)
+                d.d_colS, d.d_selS, d.nS = self._cols_side(cS, sS)
             d.nvalues, d.nouts = len(values), len(outs)
             for f, (w, src, col) in zip(d.values, values):
                 f.d_w, f.d_src, f.d_col = ptr(w), ptr(src), ptr(col)
@@ -745,9 +803,9 @@ class RHJ:
         for d, mine in zip(arr, places):
             for o, a in zip(d.outs, mine):
                 o.d_out = None if a is None else buf.data_ptr() + 8 * a if isinstance(a, int) else a.data_ptr()
-        rc = self.lib.rhj_join_fold_batch_device(arr, n)
+        rc = getattr(self.lib, entry)(arr, n)
         if rc < 0:
-            raise RuntimeError("rhj_join_fold_batch_device failed (%d)" % rc)
+            raise RuntimeError("%s failed (%d)" % (entry, rc))
         res = []
         for d, mine in zip(arr, places):
             res.append([(None if a is None else buf[a:a + d.nR] if isinstance(a, int) else a[:d.nR], d.outs[k].total) for k, a in enumerate(mine)])
@@ -801,6 +859,7 @@ class RHJ:
         info = QueryInfo(self.lib.rhj_query_batch_last_info().contents.as_dict())
         info.sum_info = self.lib.rhj_query_batch_last_sum_info().contents.as_dict()
         info.fold_info = self.lib.rhj_query_batch_last_fold_info().contents.as_dict()
+        info.foldk_info = self.lib.rhj_query_batch_last_foldk_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

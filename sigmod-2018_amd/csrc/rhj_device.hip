@@ -167,6 +167,7 @@ int g_ndev_env = 0;                  // RHJ_DEVICES as read at load time (applie
 int g_balance = 0;                   // rhj_join_devices: 1 cuts the bucket ranges by histR + histS instead of equal widths, 2 also cuts INSIDE hot buckets (rhj_set_devices_balance, env RHJ_DEVICES_BALANCE=hist / slice)
 int g_same_device = 0;               // RHJ_DEVICES_SAME=1 (tests): every context on the library's own device — n streams and workspaces on one GPU
 int g_query_fold = 0;                // 1: rhj_query_batch_device sums the queries whose predicates are a tree by rounds of rhj_join_fold_batch_device items (rhj_set_query_fold, env RHJ_QUERY_FOLD)
+int g_query_fold_keys = 0;           // 1: with g_query_fold, the queries whose predicates are a tree once parallel predicates are grouped fold too, the groups as rhj_join_foldk_batch_device items (rhj_set_query_fold_keys, env RHJ_QUERY_FOLD_KEYS)
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -198,6 +199,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_TIMING"))) g.timing = atoi(e);
         if ((e = getenv("RHJ_QUERY_SUM_LAST"))) g_query_sum_last = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD"))) g_query_fold = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_FOLD_KEYS"))) g_query_fold_keys = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1362,7 +1364,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2178,8 +2180,9 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
 }
 
 // ---- the table batches: batched final joins and weighted join folds (rhj_join_sum_batch.hip.h, rhj_join_fold_batch.hip.h) --------
-// rhj_join_sum_batch_device (path 12) and rhj_join_fold_batch_device (path 13) are ONE scheme over two descriptors (templates over
-// rhj_join_sum_desc / rhj_join_fold_desc, as filter_batch is over its two).  Every item with two non-empty sides runs in the
+// rhj_join_sum_batch_device (path 12), rhj_join_fold_batch_device (path 13) and rhj_join_foldk_batch_device (path 14, the folds on
+// tuple keys of rhj_join_foldk_batch.hip.h) are ONE scheme over three descriptors (templates over rhj_join_sum_desc /
+// rhj_join_fold_desc / rhj_join_foldk_desc, as filter_batch is over its two).  Every item with two non-empty sides runs in the
 // launches of its chunk; there is no run-alone class.  Every item has a hash table in the arena g.jsum_arena, which both share.
 // A chunk holds at most JSUM_MAX_ITEMS items and JSUM_MAX_TILES tiles of both sides together, so that no launch's grid passes the
 // limit (conditions, as the apply batch's), and JSUM_ARENA_BYTES of tables, and a batch beyond any of them is cut in call order:
@@ -2203,6 +2206,7 @@ template <class D> static inline bool tbatch_sides_valid(const D &q) { return !(
 template <class D> struct tbatch_dev;
 template <> struct tbatch_dev<rhj_join_sum_desc> { using type = JoinSumDesc; static constexpr size_t words = JSUM_WORDS; };
 template <> struct tbatch_dev<rhj_join_fold_desc> { using type = JoinFoldDesc; static constexpr size_t words = FOLD_WORDS; };
+template <> struct tbatch_dev<rhj_join_foldk_desc> { using type = JoinFoldKDesc; static constexpr size_t words = FOLDK_WORDS; };
 
 static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
@@ -2218,12 +2222,25 @@ static bool tbatch_valid(const rhj_join_fold_desc &q)
         if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
     return true;
 }
+// the fold batch's rule on tuple keys: 1..RHJ_FOLD_MAX_KEYS key columns, the first nkeys of a side with rows all given
+static bool tbatch_valid(const rhj_join_foldk_desc &q)
+{
+    if (q.nkeys < 1 || q.nkeys > RHJ_FOLD_MAX_KEYS || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
+    for (int t = 0; t < q.nkeys; ++t)
+        if ((q.nR && !q.d_colR[t]) || (q.nS && !q.d_colS[t])) return false;
+    if (q.nvalues < 0 || q.nvalues > RHJ_FOLD_MAX_VALUES || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS) return false;
+    for (int o = 0; o < q.nouts; ++o)
+        if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
+    return true;
+}
 
 static void tbatch_zero(rhj_join_sum_desc &q) { q.matches = 0; for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0; }
 static void tbatch_zero(rhj_join_fold_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
+static void tbatch_zero(rhj_join_foldk_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
 
 static inline uint64_t tbatch_table_bytes(const rhj_join_sum_desc &q) { return tbatch_slots(q) * JSUM_SLOT_BYTES; }
 static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_foldk_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 
 // the fields both device descriptors have
 template <class D, class Dev>
@@ -2246,10 +2263,11 @@ static void tbatch_fill(const rhj_join_sum_desc &q, unsigned long long *table, u
     for (int k = 0; k < q.nterms; ++k) { d.t[k].src = q.terms[k].d_src; d.t[k].col = q.terms[k].d_col; d.t[k].side = q.terms[k].side; }
     t[0] += (uint32_t)jsum_tiles(d.n[d.build]); t[1] += (uint32_t)jsum_tiles(d.n[d.build ^ 1]); t[2] += (uint32_t)(jsum_tiles(q.nR) + jsum_tiles(q.nS));
 }
-// the claim launch's (R's where R builds), the add launch's (S's), the apply launch's (R's)
-static void tbatch_fill(const rhj_join_fold_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldDesc &d, uint32_t (&t)[3])
+// the values, the outputs and the tiles of a fold, on one key or on a tuple: the claim launch's (R's where R builds), the add
+// launch's (S's), the apply launch's (R's)
+template <class D, class Dev>
+static void tbatch_fill_fold(const D &q, Dev &d, uint32_t (&t)[3])
 {
-    tbatch_common(q, table, words, d);
     d.slot_words = (uint32_t)(1 + q.nvalues);
     d.nvalues = q.nvalues; d.nouts = q.nouts;
     for (int c = 0; c < q.nvalues; ++c) d.v[c] = FoldFactor{q.values[c].d_w, q.values[c].d_src, q.values[c].d_col};
@@ -2259,6 +2277,23 @@ static void tbatch_fill(const rhj_join_fold_desc &q, unsigned long long *table, 
     }
     if (d.build == 0) t[0] += (uint32_t)jsum_tiles(q.nR);               // (an item whose S builds has no tile there: fbatch_find passes over it)
     t[1] += (uint32_t)jsum_tiles(q.nS); t[2] += (uint32_t)jsum_tiles(q.nR);
+}
+static void tbatch_fill(const rhj_join_fold_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldDesc &d, uint32_t (&t)[3])
+{
+    tbatch_common(q, table, words, d);
+    tbatch_fill_fold(q, d, t);
+}
+static void tbatch_fill(const rhj_join_foldk_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldKDesc &d, uint32_t (&t)[3])
+{
+    memset((void *)&d, 0, sizeof(d));
+    for (int k = 0; k < q.nkeys; ++k) { d.col[0][k] = q.d_colR[k]; d.col[1][k] = q.d_colS[k]; }
+    d.sel[0] = q.d_selR; d.n[0] = q.nR;
+    d.sel[1] = q.d_selS; d.n[1] = q.nS;
+    d.build = jsum_build_side(q.nR, q.nS);
+    d.log2_slots = jsum_log2_slots(d.n[d.build]);
+    d.table = table; d.words = words;
+    d.nkeys = q.nkeys;
+    tbatch_fill_fold(q, d, t);
 }
 
 static void tbatch_launch(const rhj_join_sum_desc &, const JoinSumDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
@@ -2273,6 +2308,12 @@ static void tbatch_launch(const rhj_join_fold_desc &, const JoinFoldDesc *dd, ui
     RHJ_LAUNCH(k_fold_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_fold_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
+static void tbatch_launch(const rhj_join_foldk_desc &, const JoinFoldKDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
+{
+    if (t[0]) RHJ_LAUNCH(k_foldk_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
+    RHJ_LAUNCH(k_foldk_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_foldk_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
+}
 
 static void tbatch_take(rhj_join_sum_desc &q, const unsigned long long *h)
 {
@@ -2280,13 +2321,17 @@ static void tbatch_take(rhj_join_sum_desc &q, const unsigned long long *h)
     for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = h[JSUM_W_SUM + t];
 }
 static void tbatch_take(rhj_join_fold_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[FOLD_W_TOTAL + o]; }
+static void tbatch_take(rhj_join_foldk_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[o]; }
 
 static inline int tbatch_path(const rhj_join_sum_desc &) { return PATH_BATCH_JOIN_SUM; }
 static inline int tbatch_path(const rhj_join_fold_desc &) { return PATH_BATCH_JOIN_FOLD; }
+static inline int tbatch_path(const rhj_join_foldk_desc &) { return PATH_BATCH_JOIN_FOLDK; }
 static inline const char *tbatch_noun(const rhj_join_sum_desc &) { return "join sums"; }
 static inline const char *tbatch_noun(const rhj_join_fold_desc &) { return "join folds"; }
+static inline const char *tbatch_noun(const rhj_join_foldk_desc &) { return "join folds on tuple keys"; }
 static inline uint64_t tbatch_matches(const rhj_join_sum_desc &q) { return q.matches; }
 static inline uint64_t tbatch_matches(const rhj_join_fold_desc &) { return 0; }           // (the folds' statistics have no matches)
+static inline uint64_t tbatch_matches(const rhj_join_foldk_desc &) { return 0; }
 
 // One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
 template <class D>
@@ -2454,13 +2499,14 @@ struct QueryTimingOff {                                   // the inner batches r
 rhj_query_batch_info g_query_info = {};
 rhj_query_batch_sum_info g_query_sum_info = {};
 rhj_query_batch_fold_info g_query_fold_info = {};
+rhj_query_batch_foldk_info g_query_foldk_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
     rhj_query_desc                 *queries;
     uint64_t                        n;
     std::vector<QueryState>         st;
-    std::vector<char>               folds;                // a query that takes the fold route (empty: none does)
+    std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, or 2 when only rhj_set_query_fold_keys lets it
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
     std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
     std::vector<size_t>             where;                // ... and its descriptor in ed / jd / sd
@@ -2718,15 +2764,72 @@ static int query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_r
     return lv;
 }
 
+// The plan with parallel predicates grouped (include/rhj_inter.h): a predicate on one binding does not fold, a
+// repeated predicate is dropped, the others are grouped by unordered binding pair, and the groups must be a spanning tree.  The
+// schedule is fold_schedule's over one predicate per group; for a query whose predicates are a tree already the groups are its
+// predicates and the plan is query_fold_plan's.
+static int query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps)
+{
+    if (!q) return -3;
+    const int lv = query_levels(q, nrel, rels, nullptr);
+    if (lv < 0) return -3;
+    if (lv == 0) return 0;
+    for (int l = 0; l < lv; ++l) if (q->joins[l].relA == q->joins[l].relB) return 0;       // a self-join
+    struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
+    std::vector<Group> groups;
+    std::vector<rhj_query_join> first;                    // a group's first predicate: the edge the schedule walks
+    for (int l = 0; l < lv; ++l) {
+        const rhj_query_join &p = q->joins[l];
+        bool repeated = false;
+        for (int m = 0; m < l && !repeated; ++m) {
+            const rhj_query_join &e = q->joins[m];
+            repeated = (e.relA == p.relA && e.colA == p.colA && e.relB == p.relB && e.colB == p.colB) ||
+                       (e.relA == p.relB && e.colA == p.colB && e.relB == p.relA && e.colB == p.colA);
+        }
+        if (repeated) continue;
+        const int a = p.relA < p.relB ? p.relA : p.relB, b = p.relA < p.relB ? p.relB : p.relA;
+        size_t k = 0;
+        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
+        if (k == groups.size()) { groups.push_back(Group{a, b, 0, {}}); first.push_back(p); }
+        if (groups[k].n == RHJ_FOLD_MAX_KEYS) return 0;   // more key words than a tuple has
+        groups[k].joins[groups[k].n++] = l;
+    }
+    if ((int)groups.size() != q->nrels - 1) return 0;     // (query_levels saw all bindings connected: nrels - 1 edges are a spanning tree)
+    rhj_query_desc tree = *q;
+    tree.njoins = (int)first.size(); tree.joins = first.data();
+    int best = -1, best_root = 0;
+    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
+    for (int r = 0; r < q->nrels; ++r) {
+        const int rounds = fold_schedule(tree, r, mine);
+        if (best >= 0 && rounds >= best) continue;
+        best = rounds; best_root = r;
+        memcpy(kept, mine, sizeof(kept));
+    }
+    if (root) *root = best_root;
+    for (int k = 0; steps && k < tree.njoins; ++k) {
+        const int a = kept[k].child < kept[k].parent ? kept[k].child : kept[k].parent, b = kept[k].child < kept[k].parent ? kept[k].parent : kept[k].child;
+        rhj_foldk_step &st = steps[k];
+        memset(&st, 0, sizeof(st));
+        st.child = kept[k].child; st.parent = kept[k].parent; st.round = kept[k].round;
+        for (const Group &gr : groups) {
+            if (gr.a != a || gr.b != b) continue;
+            st.nkeys = gr.n;
+            for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
+        }
+    }
+    return tree.njoins;
+}
+
 struct FoldQuery {                                        // a query on the fold route
     uint64_t        i;
     int             root, nsteps, next;                   // next: the first step not yet run
-    rhj_fold_step   steps[FOLD_MAX_STEPS];
+    rhj_foldk_step  steps[FOLD_MAX_STEPS];                // (nkeys 1 throughout unless rhj_set_query_fold_keys let the query in)
     const uint64_t *w[RHJ_QUERY_MAX_RELS];                // binding -> its weight vector; nullptr: ones
     const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // binding, view -> the view's partial sums per row, when the binding carries the view
 };
 
-// The folding queries still alive after the filters, round by round: every round is one table_batch call over all of them.
+// The folding queries still alive after the filters, round by round: every round is one table_batch call over all their items on
+// one key and, with rhj_set_query_fold_keys, one over all their items on tuple keys.
 static int query_folds(QueryRun &R)
 {
     std::vector<FoldQuery> fq;
@@ -2735,34 +2838,40 @@ static int query_folds(QueryRun &R)
         if (!R.folds[i] || !R.st[i].alive) continue;
         FoldQuery f = {};
         f.i = i;
-        f.nsteps = query_fold_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);      // (validated already)
+        f.nsteps = query_foldk_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);     // (validated already; query_fold_plan's where that has one)
         if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
+        if (R.folds[i] == 2) ++g_query_foldk_info.foldk_queries;
         if (f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
         fq.push_back(f);
     }
     g_query_fold_info.fold_queries = (uint32_t)fq.size();
     if (g_qb.fold.size() < (size_t)rounds) g_qb.fold.resize((size_t)rounds);
-    std::vector<rhj_join_fold_desc> fd;
+    std::vector<rhj_join_fold_desc> fd;                   // the round's items on one key ...
+    std::vector<rhj_join_foldk_desc> kd;                  // ... and on tuple keys
+    std::vector<std::pair<bool, size_t>> where;           // an item, in the order issued: whether it is in kd, and its place there or in fd
     std::vector<size_t> who;                              // an item's query in fq
     std::vector<int> par;                                 // an item's parent binding
     std::vector<std::array<int, RHJ_FOLD_MAX_OUTS>> view; // an item's outputs: the view each belongs to, -1 the weight
     for (int r = 0; r < rounds; ++r) {
         QueryBump ob;
-        fd.clear(); who.clear(); par.clear(); view.clear();
+        fd.clear(); kd.clear(); where.clear(); who.clear(); par.clear(); view.clear();
         for (size_t k = 0; k < fq.size(); ++k) {
             FoldQuery &f = fq[k];
             const rhj_query_desc &q = R.queries[f.i];
             const QueryState &s = R.st[f.i];
             for (; s.alive && f.next < f.nsteps && f.steps[f.next].round == r; ++f.next) {
-                const int S = f.steps[f.next].child, P = f.steps[f.next].parent;
+                const rhj_foldk_step &step = f.steps[f.next];
+                const int S = step.child, P = step.parent;
                 const bool last = f.next == f.nsteps - 1;  // the root's last fold: totals only
                 rhj_join_fold_desc d = {};
                 std::array<int, RHJ_FOLD_MAX_OUTS> ov;
-                for (int l = 0; l < q.njoins; ++l) {       // the predicate between the two
-                    const rhj_query_join &p = q.joins[l];
-                    if (p.relA == P && p.relB == S)      { d.d_colR = R.column(q, P, p.colA); d.d_colS = R.column(q, S, p.colB); }
-                    else if (p.relA == S && p.relB == P) { d.d_colR = R.column(q, P, p.colB); d.d_colS = R.column(q, S, p.colA); }
+                const uint64_t *keyR[RHJ_FOLD_MAX_KEYS] = {}, *keyS[RHJ_FOLD_MAX_KEYS] = {};
+                for (int t = 0; t < step.nkeys; ++t) {     // the predicates between the two: word t of both sides
+                    const rhj_query_join &p = q.joins[step.joins[t]];
+                    keyR[t] = p.relA == P ? R.column(q, P, p.colA) : R.column(q, P, p.colB);
+                    keyS[t] = p.relA == P ? R.column(q, S, p.colB) : R.column(q, S, p.colA);
                 }
+                d.d_colR = keyR[0]; d.d_colS = keyS[0];
                 d.d_selR = s.vec[P]; d.nR = s.rows[P];
                 d.d_selS = s.vec[S]; d.nS = s.rows[S];
                 int value_of[RHJ_QUERY_MAX_VIEWS];
@@ -2773,7 +2882,7 @@ static int query_folds(QueryRun &R)
                     else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
                 }
                 const auto out = [&](int value, rhj_fold_factor p, int v) {
-                    if (!last) ob.take(fd.size(), d.nouts, d.nR);
+                    if (!last) ob.take(where.size(), d.nouts, d.nR);
                     ov[(size_t)d.nouts] = v;
                     rhj_fold_out &o = d.outs[d.nouts++];
                     o.value = value; o.p = p;
@@ -2784,31 +2893,48 @@ static int query_folds(QueryRun &R)
                     else if (f.acc[P][v])                    out(0, rhj_fold_factor{f.acc[P][v], nullptr, nullptr}, v);           // a view the parent carried
                     else if (last && q.views[v].rel == P)    out(0, rhj_fold_factor{f.w[P], s.vec[P], R.column(q, P, q.views[v].col)}, v);   // a view on the root: lazy until now
                 }
-                who.push_back(k); par.push_back(P); view.push_back(ov); fd.push_back(d);
+                who.push_back(k); par.push_back(P); view.push_back(ov);
+                if (step.nkeys == 1) { where.emplace_back(false, fd.size()); fd.push_back(d); continue; }
+                rhj_join_foldk_desc t = {};                // the same item on its tuple of columns
+                t.nkeys = step.nkeys;
+                for (int w = 0; w < step.nkeys; ++w) { t.d_colR[w] = keyR[w]; t.d_colS[w] = keyS[w]; }
+                t.d_selR = d.d_selR; t.nR = d.nR; t.d_selS = d.d_selS; t.nS = d.nS;
+                t.nvalues = d.nvalues; t.nouts = d.nouts;
+                memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
+                where.emplace_back(true, kd.size()); kd.push_back(t);
             }
         }
-        if (fd.empty()) continue;
-        if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { fd[a].outs[o].d_out = (uint64_t *)p; })) return -1;
-        ++g_query_fold_info.fold_calls;
-        g_query_fold_info.fold_items += (uint32_t)fd.size();
-        if (const int rc = table_batch(fd.data(), fd.size())) return rc;      // (0 or an error: the items are valid)
-        for (size_t a = 0; a < fd.size(); ++a) {
+        if (where.empty()) continue;
+        const auto outs_of = [&](size_t a) { return where[a].first ? kd[where[a].second].outs : fd[where[a].second].outs; };
+        if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { outs_of(a)[o].d_out = (uint64_t *)p; })) return -1;
+        if (!fd.empty()) {
+            ++g_query_fold_info.fold_calls;
+            g_query_fold_info.fold_items += (uint32_t)fd.size();
+            if (const int rc = table_batch(fd.data(), fd.size())) return rc;      // (0 or an error: the items are valid)
+        }
+        if (!kd.empty()) {
+            ++g_query_foldk_info.foldk_calls;
+            g_query_foldk_info.foldk_items += (uint32_t)kd.size();
+            if (const int rc = table_batch(kd.data(), kd.size())) return rc;
+        }
+        for (size_t a = 0; a < where.size(); ++a) {
             FoldQuery &f = fq[who[a]];
             rhj_query_desc &q = R.queries[f.i];
             QueryState &s = R.st[f.i];
-            const rhj_join_fold_desc &d = fd[a];
+            const rhj_fold_out *outs = outs_of(a);
+            const int nouts = where[a].first ? kd[where[a].second].nouts : fd[where[a].second].nouts;
             if (!s.alive) continue;                       // (finished by another item of this round)
-            if (d.outs[0].total == 0) { s.alive = false; continue; }         // the subtree's join is empty: rows = 0, sums 0
-            const bool last = d.outs[0].d_out == nullptr;
+            if (outs[0].total == 0) { s.alive = false; continue; }           // the subtree's join is empty: rows = 0, sums 0
+            const bool last = outs[0].d_out == nullptr;
             if (last) {
-                q.rows = d.outs[0].total;
-                for (int o = 1; o < d.nouts; ++o) q.sums[view[a][(size_t)o]] = d.outs[o].total;
+                q.rows = outs[0].total;
+                for (int o = 1; o < nouts; ++o) q.sums[view[a][(size_t)o]] = outs[o].total;
                 s.alive = false;                          // finished
                 continue;
             }
             const int P = par[a];                         // the parent's new weight and what it carries now
-            f.w[P] = d.outs[0].d_out;
-            for (int o = 1; o < d.nouts; ++o) f.acc[P][view[a][(size_t)o]] = d.outs[o].d_out;
+            f.w[P] = outs[0].d_out;
+            for (int o = 1; o < nouts; ++o) f.acc[P][view[a][(size_t)o]] = outs[o].d_out;
         }
     }
     return 0;
@@ -2821,6 +2947,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     memset(&g_query_info, 0, sizeof(g_query_info));
     memset(&g_query_sum_info, 0, sizeof(g_query_sum_info));
     memset(&g_query_fold_info, 0, sizeof(g_query_fold_info));
+    memset(&g_query_foldk_info, 0, sizeof(g_query_foldk_info));
     bool invalid = false;                                 // the whole batch is validated before a device is touched
     int maxl = 0;
     std::vector<char> folds;
@@ -2829,10 +2956,12 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
         const int lv = query_levels(&queries[i], nrel, rels, nullptr);
         queries[i].rc = lv < 0 ? -3 : 0;
         invalid |= lv < 0;
-        if (g_query_fold && lv > 0 && query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0) {
+        const int how = !(g_query_fold && lv > 0) ? 0 : query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 1 :
+                        g_query_fold_keys && query_foldk_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 2 : 0;
+        if (how) {
             bool fits = true;                             // a fold's sides have fewer than 2^32 rows
             for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
-            folds[i] = fits;
+            folds[i] = fits ? (char)how : 0;
         }
         if (lv > maxl && !(g_query_fold && folds[i])) maxl = lv;       // (the levels of the queries that run by levels)
     }
@@ -3420,9 +3549,18 @@ const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void) { return &g_
 void rhj_set_query_sum_last(int on) { RhjApiLock api_lock; g_query_sum_last = on != 0; }
 const rhj_query_batch_fold_info *rhj_query_batch_last_fold_info(void) { return &g_query_fold_info; }
 void rhj_set_query_fold(int on) { RhjApiLock api_lock; g_query_fold = on != 0; }
+const rhj_query_batch_foldk_info *rhj_query_batch_last_foldk_info(void) { return &g_query_foldk_info; }
+void rhj_set_query_fold_keys(int on) { RhjApiLock api_lock; g_query_fold_keys = on != 0; }
+int rhj_query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps) { return query_foldk_plan(q, nrel, rels, root, steps); }
 int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps) { return query_fold_plan(q, nrel, rels, root, steps); }
 
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return table_batch(items, n);
+}
+
+int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
     return table_batch(items, n);

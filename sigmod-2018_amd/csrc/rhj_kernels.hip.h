@@ -47,6 +47,8 @@
 //                          item a table of {key, count of R, count of S}.
 //   rhj_join_fold_batch.hip.h many weighted join folds in three launches: a child side's values summed per key in the same
 //                          table, then multiplied into per-row u64 weights of the parent side.
+//   rhj_join_foldk_batch.hip.h the same folds on keys of up to four columns: a slot holds the build row that owns it, not a key,
+//                          and equality is decided on that row's words, gathered from the build side's own columns.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -69,4 +71,5 @@
 #include "rhj_stats_batch.hip.h"
 #include "rhj_join_sum_batch.hip.h"
 #include "rhj_join_fold_batch.hip.h"
+#include "rhj_join_foldk_batch.hip.h"
 #include "rhj_diag.hip.h"
