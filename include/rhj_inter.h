@@ -448,6 +448,85 @@ void rhj_set_query_fold_keys(int on);
 typedef struct rhj_query_batch_foldk_info { uint32_t foldk_calls, foldk_items, foldk_queries; } rhj_query_batch_foldk_info;
 const rhj_query_batch_foldk_info *rhj_query_batch_last_foldk_info(void);
 
+/* Many folds with NO child in one call (csrc/rhj_fold_self_batch.hip.h): what a predicate with both sides on one binding, and a
+ * query without a join, need on the fold route.  One item is ONE side of n rows, nterms equalities and nouts outputs, each a
+ * factor P (rhj_fold_factor) over the side's positions:
+ *     m(i)     = product over t of [ d_colA_t[d_selA_t ? d_selA_t[i] : i] == d_colB_t[d_selB_t ? d_selB_t[i] : i] ]   (no term: 1)
+ *     d_out[i] = m(i) * P(i)       for i < n, when d_out is given; a masked row stores 0 (written, not left)
+ *     total    = sum over i of m(i) * P(i)
+ * everything exact modulo 2^64.  A term carries a row-id vector PER COLUMN, as rhj_filter_eq2_batch_device does: the same vector
+ * twice is the predicate on one binding, two vectors the equality inside a materialised node.  A zero-term item with an output
+ * {NULL, d_src, d_col} gives rhj_apply_batch_device's view sum on the same pointers as its total.
+ *
+ * Every item with rows runs in the ONE launch of its chunk (path 15) over 2048-row tiles: one upload, one launch, one copy of the
+ * accumulator words and one stream synchronisation per chunk of at most 4096 items and 2^24 tiles, in call order.  There is no
+ * table and no memset.  Every pointer needs 8-byte alignment and no more; inputs may be shared between items, terms and factors;
+ * outputs must not overlap each other or any input of the call; nothing at or beyond d_out[n] is written; the caller guarantees
+ * that every index indexes its array.  An item with n == 0 has rc 0, every total 0 and path 0, its d_outs are untouched and it
+ * launches nothing; a batch of 0 items returns 0 without touching a device.
+ *
+ * The whole batch is validated before anything is launched: nterms outside 0..RHJ_FOLD_SELF_MAX_TERMS, nouts outside
+ * 0..RHJ_FOLD_MAX_OUTS, a NULL column in a term of an item with rows, or n of 2^32 or more give that item rc -3; then nothing
+ * runs, no total is written and the call returns -3.  Otherwise 0, or a negative value on a HIP error.  rhj_last_stats()
+ * afterwards: n_r the rows summed over the items, units the items launched, ms_total the whole call (timing level >= 1),
+ * reserved 15. */
+#define RHJ_FOLD_SELF_MAX_TERMS 4
+typedef struct rhj_fold_eq_term {
+    const uint64_t *d_colA, *d_selA;   /* sel NULL: q = p */
+    const uint64_t *d_colB, *d_selB;
+} rhj_fold_eq_term;
+typedef struct rhj_fold_self_out {
+    rhj_fold_factor p;       /* over the side's positions */
+    uint64_t       *d_out;   /* n words, or NULL: the total only */
+    uint64_t        total;   /* out */
+} rhj_fold_self_out;
+typedef struct rhj_fold_self_desc {
+    uint64_t          n;
+    int               nterms, nouts;   /* 0 .. RHJ_FOLD_SELF_MAX_TERMS, 0 .. RHJ_FOLD_MAX_OUTS */
+    rhj_fold_eq_term  terms[RHJ_FOLD_SELF_MAX_TERMS];
+    rhj_fold_self_out outs[RHJ_FOLD_MAX_OUTS];
+    int rc;                  /* out */
+    int path;                /* out: 15, or 0 when nothing was launched */
+} rhj_fold_self_desc;
+int rhj_fold_self_batch_device(rhj_fold_self_desc *items, uint64_t n);
+
+/* The fold schedule of one query with every predicate that forms no real cycle taken in, a pure function that needs no device.
+ * The rule: rhj_query_levels must accept the query (else -3).  The predicates are taken in the order given over a union-find of
+ * their (binding, column) terms: a predicate whose two terms are already in one class is DROPPED (the literal repeat, 0.1=0.1,
+ * and the predicate that earlier ones imply: 0.1=2.1 after 0.1=1.0 and 1.0=2.1); any other is kept and joins the two classes.  A
+ * kept predicate on one binding goes to self[0 .. nself), indices into q->joins, ascending; more than
+ * RHJ_FOLD_SELF_MAX_TERMS of them on one binding give 0.  The other kept predicates are grouped by unordered binding pair; a group
+ * of more than RHJ_FOLD_MAX_KEYS gives 0; the groups must number nrels - 1 (a spanning tree), else 0: a true cycle.  Schedule and
+ * root are rhj_query_fold_plan's over one predicate per group; steps[0 .. nsteps) are as rhj_query_foldk_plan's.  A query of one
+ * binding folds with nsteps 0 and root 0.  Returns 1 when the query folds, 0 when it does not, or -3.
+ *
+ * For every query rhj_query_foldk_plan accepts nself is 0 and the root and every step's child, parent and round are the same;
+ * nkeys and joins are the same too unless a dropped predicate was implied without being a repeat (that plan keeps it as a key
+ * word, this one does not).  plan may be NULL. */
+typedef struct rhj_folds_plan {
+    int root, nsteps, nself;
+    rhj_foldk_step steps[RHJ_QUERY_MAX_RELS - 1];
+    int self[RHJ_QUERY_MAX_RELS * RHJ_FOLD_SELF_MAX_TERMS];
+} rhj_folds_plan;
+int rhj_query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *plan);
+
+/* rhj_query_batch_device with this switch on as well as rhj_set_query_fold (default off; environment RHJ_QUERY_FOLD_SELF=1; no
+ * effect while the fold route is off): a query that neither rhj_query_fold_plan nor (with its switch) rhj_query_foldk_plan takes
+ * folds when rhj_query_folds_plan gives 1 and every step has one key or rhj_set_query_fold_keys is on.  After the filter batch
+ * ONE rhj_fold_self_batch_device call runs before round 0, over all such queries still alive.  A binding with kept one-binding
+ * predicates is an item of its rows, both row-id vectors of every term its hit list, and one output {ones, its first weight
+ * vector}; the total is the surviving rows (below 2^32, so 0 means empty exactly) and a total of 0 finishes the query with
+ * rows = 0 and sums 0.  A query of one binding is one item with every d_out NULL, output 0 {ones} its rows and one output
+ * {NULL, hit list, column} per view its sums, and finishes there, with or without terms.  Then the rounds run as always, a
+ * binding's weight starting at that vector instead of ones: at most two calls a round, and a binding's state, the round buffers,
+ * the zero-total exit and the 2^64 limit are the fold route's.  The first weight vectors have a workspace buffer of their own.
+ * rhj_query_batch_last_fold_self_info(): whether that call ran, its items, and the queries that fold only because of this switch
+ * and were alive after the filters (all zero with either switch off); rhj_query_batch_fold_info keeps counting all folding
+ * queries, rhj_query_batch_foldk_info the tuple-key calls and items. */
+void rhj_set_query_fold_self(int on);
+typedef struct rhj_query_batch_fold_self_info { uint32_t self_calls, self_items, self_queries; } rhj_query_batch_fold_self_info;
+const rhj_query_batch_fold_self_info *rhj_query_batch_last_fold_self_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

@@ -44,6 +44,7 @@ INTER_SYMBOLS = [
     "rhj_join_sum_batch_device", "rhj_set_query_sum_last", "rhj_query_batch_last_sum_info",
     "rhj_join_fold_batch_device", "rhj_query_fold_plan", "rhj_set_query_fold", "rhj_query_batch_last_fold_info",
     "rhj_join_foldk_batch_device", "rhj_query_foldk_plan", "rhj_set_query_fold_keys", "rhj_query_batch_last_foldk_info",
+    "rhj_fold_self_batch_device", "rhj_query_folds_plan", "rhj_set_query_fold_self", "rhj_query_batch_last_fold_self_info",
 ]
 
 
@@ -267,12 +268,65 @@ class QueryBatchFoldKInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FOLD_SELF_MAX_TERMS = 4                  # RHJ_FOLD_SELF_MAX_TERMS
+QUERY_MAX_RELS = 8                       # RHJ_QUERY_MAX_RELS
+
+
+class FoldEqTerm(C.Structure):
+    """rhj_fold_eq_term (include/rhj_inter.h): colA[selA ? selA[i] : i] == colB[selB ? selB[i] : i]"""
+    _fields_ = [("d_colA", C.c_void_p), ("d_selA", C.c_void_p), ("d_colB", C.c_void_p), ("d_selB", C.c_void_p)]
+
+
+class FoldSelfOut(C.Structure):
+    """rhj_fold_self_out (include/rhj_inter.h): one output of a batched fold item with no child"""
+    _fields_ = [("p", FoldFactor), ("d_out", C.c_void_p), ("total", C.c_uint64)]
+
+
+class FoldSelfDesc(C.Structure):
+    """rhj_fold_self_desc (include/rhj_inter.h): one item of rhj_fold_self_batch_device"""
+    _fields_ = [("n", C.c_uint64), ("nterms", C.c_int), ("nouts", C.c_int),
+                ("terms", FoldEqTerm * FOLD_SELF_MAX_TERMS), ("outs", FoldSelfOut * FOLD_MAX_OUTS),
+                ("rc", C.c_int), ("path", C.c_int)]
+
+
+class FoldsPlan(C.Structure):
+    """rhj_folds_plan (include/rhj_inter.h): what rhj_query_folds_plan returns of a query that folds"""
+    _fields_ = [("root", C.c_int), ("nsteps", C.c_int), ("nself", C.c_int), ("steps", FoldKStep * (QUERY_MAX_RELS - 1)),
+                ("self", C.c_int * (QUERY_MAX_RELS * FOLD_SELF_MAX_TERMS))]
+
+
+class QueryBatchFoldSelfInfo(C.Structure):
+    """rhj_query_batch_fold_self_info (include/rhj_inter.h): whether the last rhj_query_batch_device issued its
+    rhj_fold_self_batch_device call, that call's items and the queries that folded only because of rhj_set_query_fold_self"""
+    _fields_ = [("self_calls", C.c_uint32), ("self_items", C.c_uint32), ("self_queries", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def query_folds_plan(lib, query, nrel=None):
+    """rhj_query_folds_plan on one query (relations, joins, filters, views): None when it does not fold, else
+    (root, [(child, parent, round, [predicate indices])], [indices of the kept one-binding predicates]); ValueError on -3"""
+    arr, keep = query_descs([query])
+    plan = FoldsPlan()
+    rc = lib.rhj_query_folds_plan(C.byref(arr[0]), nrel if nrel is not None else max(query[0]) + 1, None, C.byref(plan))
+    del keep
+    if rc == -3:
+        raise ValueError("rhj_query_folds_plan refused the query")
+    if rc != 1:
+        return None
+    steps = [(s.child, s.parent, s.round, list(s.joins[:s.nkeys])) for s in plan.steps[:plan.nsteps]]
+    return plan.root, steps, list(plan.self[:plan.nself])
+
+
 class QueryInfo(dict):
-    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info(), rhj_query_batch_last_fold_info() and
-    rhj_query_batch_last_foldk_info() as the dicts in its attributes sum_info, fold_info and foldk_info"""
+    """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info(), rhj_query_batch_last_fold_info(),
+    rhj_query_batch_last_foldk_info() and rhj_query_batch_last_fold_self_info() as the dicts in its attributes sum_info,
+    fold_info, foldk_info and fold_self_info"""
     sum_info = None
     fold_info = None
     foldk_info = None
+    fold_self_info = None
 
 
 def query_descs(queries):
@@ -300,7 +354,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch", 15: "fold_self_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -418,6 +472,12 @@ def load_library(path=None):
         L.rhj_set_query_fold_keys.argtypes = [C.c_int]
         L.rhj_set_query_fold_keys.restype = None
         L.rhj_query_batch_last_foldk_info.restype = C.POINTER(QueryBatchFoldKInfo)
+    if hasattr(L, "rhj_fold_self_batch_device"):
+        L.rhj_fold_self_batch_device.argtypes = [C.POINTER(FoldSelfDesc), C.c_uint64]
+        L.rhj_query_folds_plan.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(FoldsPlan)]
+        L.rhj_set_query_fold_self.argtypes = [C.c_int]
+        L.rhj_set_query_fold_self.restype = None
+        L.rhj_query_batch_last_fold_self_info.restype = C.POINTER(QueryBatchFoldSelfInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -754,6 +814,53 @@ class RHJ:
         one join on a tuple of columns fold too (default off)"""
         self.lib.rhj_set_query_fold_keys(1 if on else 0)
 
+    def fold_self_batch_device(self, items, with_info=False):
+        """Many folds with no child in one call (rhj_fold_self_batch_device, include/rhj_inter.h): items =
+        [(n, terms, outs), ...] with terms = [(colA, selA, colB, selB), ...] (0..4 equalities, int64 tensors, a vector may be
+        None) and outs = [((w, src, col), out), ...] (0..9 of them: a factor over the side's positions, and out = None for the
+        total only, True for a vector of this call's, or an int64 tensor of at least n elements to write into).  Returns per
+        item a list of (vector or None, total): d_out[i] = m(i) * P(i) and its sum, Python ints below 2^64.  The vectors this
+        call makes are views of one allocation.  with_info: also the list of the items' path ids (15: the batched launch, 0:
+        an item without rows, whose vectors are left as they were)."""
+        torch = self.torch
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        n = len(items)
+        arr = (FoldSelfDesc * max(n, 1))()
+        places, at = [], 0
+        for d, (rows, terms, outs) in zip(arr, items):
+            if len(terms) > FOLD_SELF_MAX_TERMS or len(outs) > FOLD_MAX_OUTS:
+                raise ValueError("an item has 0..%d terms and 0..%d outputs, not %d and %d" % (FOLD_SELF_MAX_TERMS, FOLD_MAX_OUTS, len(terms), len(outs)))
+            d.n, d.nterms, d.nouts = int(rows), len(terms), len(outs)
+            for t, (colA, selA, colB, selB) in zip(d.terms, terms):
+                t.d_colA, t.d_selA, t.d_colB, t.d_selB = ptr(colA), ptr(selA), ptr(colB), ptr(selB)
+            mine = []
+            for o, ((w, src, col), out) in zip(d.outs, outs):
+                o.p.d_w, o.p.d_src, o.p.d_col = ptr(w), ptr(src), ptr(col)
+                if out is True:
+                    mine.append(at)
+                    at += (d.n + 1) // 2 * 2                     # 16-byte aligned pieces
+                else:
+                    if out is not None and out.numel() < d.n:
+                        raise ValueError("an output vector of %d words for %d rows" % (out.numel(), d.n))
+                    mine.append(out)
+            places.append(mine)
+        buf = torch.zeros(max(at, 1), dtype=torch.int64, device=self.dev)
+        for d, mine in zip(arr, places):
+            for o, a in zip(d.outs, mine):
+                o.d_out = None if a is None else buf.data_ptr() + 8 * a if isinstance(a, int) else a.data_ptr()
+        rc = self.lib.rhj_fold_self_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_fold_self_batch_device failed (%d)" % rc)
+        res = []
+        for d, mine in zip(arr, places):
+            res.append([(None if a is None else buf[a:a + d.n] if isinstance(a, int) else a[:d.n], d.outs[k].total) for k, a in enumerate(mine)])
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def set_query_fold_self(self, on):
+        """with set_query_fold: the queries that fold once their one-binding predicates are 0/1 factors on a binding's weight and
+        their implied predicates are dropped fold too, queries without a join among them (default off)"""
+        self.lib.rhj_set_query_fold_self(1 if on else 0)
+
     def join_fold_batch_device(self, items, with_info=False):
         """Many weighted join folds in one call (rhj_join_fold_batch_device, include/rhj_inter.h): items =
         [(colR, selR, colS, selS, values, outs), ...] as join_cols_batch_device takes the four (R the parent side, S the
@@ -860,6 +967,7 @@ class RHJ:
         info.sum_info = self.lib.rhj_query_batch_last_sum_info().contents.as_dict()
         info.fold_info = self.lib.rhj_query_batch_last_fold_info().contents.as_dict()
         info.foldk_info = self.lib.rhj_query_batch_last_foldk_info().contents.as_dict()
+        info.fold_self_info = self.lib.rhj_query_batch_last_fold_self_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

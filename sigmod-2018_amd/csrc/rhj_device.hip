@@ -168,6 +168,7 @@ int g_balance = 0;                   // rhj_join_devices: 1 cuts the bucket rang
 int g_same_device = 0;               // RHJ_DEVICES_SAME=1 (tests): every context on the library's own device — n streams and workspaces on one GPU
 int g_query_fold = 0;                // 1: rhj_query_batch_device sums the queries whose predicates are a tree by rounds of rhj_join_fold_batch_device items (rhj_set_query_fold, env RHJ_QUERY_FOLD)
 int g_query_fold_keys = 0;           // 1: with g_query_fold, the queries whose predicates are a tree once parallel predicates are grouped fold too, the groups as rhj_join_foldk_batch_device items (rhj_set_query_fold_keys, env RHJ_QUERY_FOLD_KEYS)
+int g_query_fold_self = 0;           // 1: with g_query_fold, the queries that fold once one-binding and implied predicates are taken care of fold too, after one rhj_fold_self_batch_device call (rhj_set_query_fold_self, env RHJ_QUERY_FOLD_SELF)
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -200,6 +201,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_SUM_LAST"))) g_query_sum_last = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD"))) g_query_fold = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_KEYS"))) g_query_fold_keys = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_FOLD_SELF"))) g_query_fold_self = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1364,7 +1366,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2405,6 +2407,87 @@ static int table_batch(D *items, uint64_t n)
     return batch_close(timed, st);
 }
 
+// ---- batched folds with no child (rhj_fold_self_batch.hip.h) ---------------------------------------------------------------------
+// rhj_fold_self_batch_device (path 15): every item with rows runs in the one launch of its chunk; there is no table, no arena and
+// no run-alone class.  A chunk holds at most FSELF_MAX_ITEMS items and FSELF_MAX_TILES tiles (conditions, as the apply batch's),
+// and a batch beyond either is cut in call order by batch_cut.  A chunk is one upload, one launch, one copy of its accumulator
+// words and one stream synchronisation; the uploaded block is
+//   [descriptors][items + 1 tile starts][the items' accumulator words, zero]
+constexpr size_t FSELF_MAX_ITEMS = 4096;
+constexpr uint64_t FSELF_MAX_TILES = 1ull << 24;
+
+static bool fself_valid(const rhj_fold_self_desc &q)
+{
+    if (q.nterms < 0 || q.nterms > RHJ_FOLD_SELF_MAX_TERMS || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS || q.n >= JSUM_MAX_ROWS) return false;
+    for (int t = 0; t < q.nterms; ++t)
+        if (q.n && (!q.terms[t].d_colA || !q.terms[t].d_colB)) return false;
+    return true;
+}
+
+// One chunk: items[which[lo, hi)], every one valid and of at least one row.
+static int fself_chunk(rhj_fold_self_desc *items, const std::vector<uint64_t> &which, size_t lo, size_t hi)
+{
+    constexpr size_t WORDS = FOLD_SELF_WORDS;
+    static_assert(sizeof(FoldSelfDesc) % 8 == 0, "the words' padding is that of the tile starts alone");
+    const size_t ni = hi - lo;
+    Block blk;
+    unsigned long long *back, *words, *d_words; FoldSelfDesc *hd, *dd; uint32_t *tile_start, *d_tile_start;
+    if (batch_block(blk, [&](Block &b) { b.back(back, ni * WORDS); b.up(hd, dd, ni); b.up(tile_start, d_tile_start, ni + 1); b.up(words, d_words, ni * WORDS); })) return -1;
+    memset(words, 0, ni * WORDS * 8);
+    uint32_t tiles = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const rhj_fold_self_desc &q = items[which[lo + k]];
+        FoldSelfDesc d;
+        memset((void *)&d, 0, sizeof(d));
+        d.n = q.n; d.words = d_words + k * WORDS; d.nterms = q.nterms; d.nouts = q.nouts;
+        for (int t = 0; t < q.nterms; ++t) {
+            d.t[t].col[0] = q.terms[t].d_colA; d.t[t].sel[0] = q.terms[t].d_selA;
+            d.t[t].col[1] = q.terms[t].d_colB; d.t[t].sel[1] = q.terms[t].d_selB;
+        }
+        for (int o = 0; o < q.nouts; ++o) {
+            d.o[o].p = FoldFactor{q.outs[o].p.d_w, q.outs[o].p.d_src, q.outs[o].p.d_col};
+            d.o[o].out = q.outs[o].d_out;
+        }
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        tile_start[k] = tiles;
+        tiles += (uint32_t)jsum_tiles(q.n);
+    }
+    tile_start[ni] = tiles;
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
+    RHJ_LAUNCH(k_fold_self, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)ni);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, d_words, ni * WORDS * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < ni; ++k) {
+        rhj_fold_self_desc &q = items[which[lo + k]];
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = back[k * WORDS + (size_t)o];
+        q.path = PATH_BATCH_FOLD_SELF;
+    }
+    return 0;
+}
+
+static int fold_self_batch(rhj_fold_self_desc *items, uint64_t n)
+{
+    if (n == 0) return 0;
+    bool timed = false;
+    const auto reset = [](rhj_fold_self_desc &q) { q.rc = 0; q.path = 0; return fself_valid(q); };      // (no total is written in a batch that is refused)
+    if (const int rc = batch_open(items, n, reset, timed)) return rc;
+    std::vector<uint64_t> which;
+    rhj_stats st = {};
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_fold_self_desc &q = items[i];
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0;
+        st.n_r += q.n;
+        if (q.n) which.push_back(i);                      // an empty item: nothing to launch, no d_out touched
+    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].n); };   // (one item never has more than the limit: fself_valid)
+    if (batch_cut(which.size(), FSELF_MAX_ITEMS, FSELF_MAX_TILES, tiles,
+                  [&](size_t lo, size_t hi, uint64_t) { return fself_chunk(items, which, lo, hi); })) return -1;
+    st.units = which.size();
+    st.reserved = PATH_BATCH_FOLD_SELF;
+    return batch_close(timed, st);
+}
+
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
 // rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
 // equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
@@ -2414,16 +2497,17 @@ static int table_batch(D *items, uint64_t n)
 //   g_qb.idx2       the pairs of the joins run a second time (the first call's lists of the others are still needed)
 //   g_qb.level[l]   the vectors level l rebuilds: read by any later level, so every level has its own
 //   g_qb.fold[r]    the weight and view vectors fold round r writes: read by any later round, so every round has its own
+//   g_qb.self       the first weight vectors, written by the fold route's one rhj_fold_self_batch_device call: read by any round
 // They belong to the library's own context (the entry point runs on no other), grow and stay, and go with rhj_release().
 struct QueryWorkspace {
-    Buf              filt, idx, idx2;
+    Buf              filt, idx, idx2, self;
     std::vector<Buf> level, fold;
     hipEvent_t       ev[2] = {};     // the whole call (its inner batches run untimed); created by the first timed call
 } g_qb;
 
 static void query_release()
 {
-    for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
+    for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2, &g_qb.self}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
     for (Buf &b : g_qb.level) if (b.p) (void)hipFree(b.p);
     g_qb.level.clear();
     for (Buf &b : g_qb.fold) if (b.p) (void)hipFree(b.p);
@@ -2500,13 +2584,14 @@ rhj_query_batch_info g_query_info = {};
 rhj_query_batch_sum_info g_query_sum_info = {};
 rhj_query_batch_fold_info g_query_fold_info = {};
 rhj_query_batch_foldk_info g_query_foldk_info = {};
+rhj_query_batch_fold_self_info g_query_fold_self_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
     rhj_query_desc                 *queries;
     uint64_t                        n;
     std::vector<QueryState>         st;
-    std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, or 2 when only rhj_set_query_fold_keys lets it
+    std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, 2 when only rhj_set_query_fold_keys lets it, 3 when only rhj_set_query_fold_self does
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
     std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
     std::vector<size_t>             where;                // ... and its descriptor in ed / jd / sd
@@ -2820,13 +2905,148 @@ static int query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_
     return tree.njoins;
 }
 
+// The plan with every predicate that forms no real cycle taken in (include/rhj_inter.h): the predicates go in
+// order through a union-find of their (binding, column) terms; one whose terms are in one class already is dropped (a repeat,
+// 0.1=0.1, an implied one); a kept one on one binding goes to self, the others are grouped as query_foldk_plan's and must be a
+// spanning tree.  1 folds, 0 does not, -3.
+static int query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *plan)
+{
+    if (!q) return -3;
+    const int lv = query_levels(q, nrel, rels, nullptr);
+    if (lv < 0) return -3;
+    std::vector<std::pair<int, int>> terms;               // a class member: (binding, column) ...
+    std::vector<size_t> up;                               // ... and the member above it (itself: the class's root)
+    const auto term = [&](int b, int c) {
+        size_t k = 0;
+        while (k < terms.size() && terms[k] != std::make_pair(b, c)) ++k;
+        if (k == terms.size()) { terms.emplace_back(b, c); up.push_back(k); }
+        while (up[k] != k) k = up[k];
+        return k;
+    };
+    struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
+    std::vector<Group> groups;
+    std::vector<rhj_query_join> first;                    // a group's first kept predicate: the edge the schedule walks
+    std::vector<int> self;
+    int on_binding[RHJ_QUERY_MAX_RELS] = {};
+    for (int l = 0; l < lv; ++l) {
+        const rhj_query_join &p = q->joins[l];
+        const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
+        if (ca == cb) continue;                           // said already by the predicates before it
+        up[cb] = ca;
+        if (p.relA == p.relB) {
+            if (++on_binding[p.relA] > RHJ_FOLD_SELF_MAX_TERMS) return 0;       // more terms than an item has
+            self.push_back(l);
+            continue;
+        }
+        const int a = p.relA < p.relB ? p.relA : p.relB, b = p.relA < p.relB ? p.relB : p.relA;
+        size_t k = 0;
+        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
+        if (k == groups.size()) { groups.push_back(Group{a, b, 0, {}}); first.push_back(p); }
+        if (groups[k].n == RHJ_FOLD_MAX_KEYS) return 0;   // more key words than a tuple has
+        groups[k].joins[groups[k].n++] = l;
+    }
+    // (query_levels saw all bindings connected, and a dropped predicate's bindings are connected by kept ones: nrels - 1 groups
+    // are a spanning tree, more are a true cycle)
+    if ((int)groups.size() != q->nrels - 1) return 0;
+    if (!plan) return 1;
+    memset(plan, 0, sizeof(*plan));
+    plan->nself = (int)self.size();
+    for (size_t k = 0; k < self.size(); ++k) plan->self[k] = self[k];
+    plan->nsteps = (int)groups.size();
+    if (groups.empty()) return 1;                         // one binding: nothing to schedule
+    rhj_query_desc tree = *q;
+    tree.njoins = (int)first.size(); tree.joins = first.data();
+    int best = -1;
+    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
+    for (int r = 0; r < q->nrels; ++r) {
+        const int rounds = fold_schedule(tree, r, mine);
+        if (best >= 0 && rounds >= best) continue;
+        best = rounds; plan->root = r;
+        memcpy(kept, mine, sizeof(kept));
+    }
+    for (int k = 0; k < plan->nsteps; ++k) {
+        const int a = kept[k].child < kept[k].parent ? kept[k].child : kept[k].parent, b = kept[k].child < kept[k].parent ? kept[k].parent : kept[k].child;
+        rhj_foldk_step &st = plan->steps[k];
+        st.child = kept[k].child; st.parent = kept[k].parent; st.round = kept[k].round;
+        for (const Group &gr : groups) {
+            if (gr.a != a || gr.b != b) continue;
+            st.nkeys = gr.n;
+            for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
+        }
+    }
+    return 1;
+}
+
+// whether the fold route takes a query because of rhj_set_query_fold_self: the plan above, its steps within the key switch
+static bool query_folds_self(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels)
+{
+    rhj_folds_plan plan;
+    if (query_folds_plan(q, nrel, rels, &plan) != 1) return false;
+    for (int k = 0; k < plan.nsteps; ++k) if (plan.steps[k].nkeys > 1 && !g_query_fold_keys) return false;
+    return true;
+}
+
 struct FoldQuery {                                        // a query on the fold route
     uint64_t        i;
     int             root, nsteps, next;                   // next: the first step not yet run
+    int             nself, self[RHJ_QUERY_MAX_RELS * RHJ_FOLD_SELF_MAX_TERMS];    // the one-binding predicates of a query rhj_set_query_fold_self let in
     rhj_foldk_step  steps[FOLD_MAX_STEPS];                // (nkeys 1 throughout unless rhj_set_query_fold_keys let the query in)
     const uint64_t *w[RHJ_QUERY_MAX_RELS];                // binding -> its weight vector; nullptr: ones
     const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // binding, view -> the view's partial sums per row, when the binding carries the view
 };
+
+// Before round 0, ONE fold_self_batch call over the queries rhj_set_query_fold_self let in: a binding with one-binding predicates
+// gets its first weight vector (0 / 1 per row of its hit list), and a query of one binding is finished.
+static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
+{
+    std::vector<rhj_fold_self_desc> sd;
+    std::vector<std::pair<size_t, int>> who;              // an item's query in fq and its binding
+    QueryBump wb;
+    for (size_t k = 0; k < fq.size(); ++k) {
+        const FoldQuery &f = fq[k];
+        const rhj_query_desc &q = R.queries[f.i];
+        const QueryState &s = R.st[f.i];
+        if (R.folds[f.i] != 3) continue;
+        for (int b = 0; b < q.nrels; ++b) {
+            rhj_fold_self_desc d = {};
+            for (int t = 0; t < f.nself; ++t) {
+                const rhj_query_join &p = q.joins[f.self[t]];
+                if (p.relA != b) continue;
+                d.terms[d.nterms++] = rhj_fold_eq_term{R.column(q, b, p.colA), s.vec[b], R.column(q, b, p.colB), s.vec[b]};
+            }
+            if (d.nterms == 0 && q.nrels > 1) continue;   // no predicate of its own: the binding's weight stays ones
+            d.n = s.rows[b];
+            d.nouts = 1;                                  // output 0: ones, so its total is the rows that pass
+            if (q.nrels == 1) {                           // the whole query: the views' sums, nothing written
+                for (int v = 0; v < q.nviews; ++v) d.outs[d.nouts++].p = rhj_fold_factor{nullptr, s.vec[0], R.column(q, 0, q.views[v].col)};
+            } else {
+                wb.take(sd.size(), 0, d.n);
+            }
+            who.emplace_back(k, b); sd.push_back(d);
+        }
+    }
+    if (sd.empty()) return 0;
+    if (wb.resolve(g_qb.self, [&](size_t a, int, char *p) { sd[a].outs[0].d_out = (uint64_t *)p; })) return -1;
+    ++g_query_fold_self_info.self_calls;
+    g_query_fold_self_info.self_items = (uint32_t)sd.size();
+    if (const int rc = fold_self_batch(sd.data(), sd.size())) return rc;       // (0 or an error: the items are valid)
+    for (size_t a = 0; a < sd.size(); ++a) {
+        FoldQuery &f = fq[who[a].first];
+        rhj_query_desc &q = R.queries[f.i];
+        QueryState &s = R.st[f.i];
+        const rhj_fold_self_desc &d = sd[a];
+        if (!s.alive) continue;                           // (finished by another item of this call)
+        if (d.outs[0].total == 0) { s.alive = false; continue; }               // no row passes: rows = 0, sums 0
+        if (q.nrels == 1) {
+            q.rows = d.outs[0].total;
+            for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.outs[1 + v].total;
+            s.alive = false;                              // finished
+            continue;
+        }
+        f.w[who[a].second] = d.outs[0].d_out;
+    }
+    return 0;
+}
 
 // The folding queries still alive after the filters, round by round: every round is one table_batch call over all their items on
 // one key and, with rhj_set_query_fold_keys, one over all their items on tuple keys.
@@ -2838,13 +3058,22 @@ static int query_folds(QueryRun &R)
         if (!R.folds[i] || !R.st[i].alive) continue;
         FoldQuery f = {};
         f.i = i;
-        f.nsteps = query_foldk_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);     // (validated already; query_fold_plan's where that has one)
-        if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
+        if (R.folds[i] == 3) {                            // rhj_set_query_fold_self's: possibly no step at all
+            rhj_folds_plan plan;
+            if (query_folds_plan(&R.queries[i], INT_MAX, nullptr, &plan) != 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
+            f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
+            memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
+            ++g_query_fold_self_info.self_queries;
+        } else {
+            f.nsteps = query_foldk_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);     // (validated already; query_fold_plan's where that has one)
+            if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
+        }
         if (R.folds[i] == 2) ++g_query_foldk_info.foldk_queries;
-        if (f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
+        if (f.nsteps && f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
         fq.push_back(f);
     }
     g_query_fold_info.fold_queries = (uint32_t)fq.size();
+    if (const int rc = query_fold_self(R, fq)) return rc;
     if (g_qb.fold.size() < (size_t)rounds) g_qb.fold.resize((size_t)rounds);
     std::vector<rhj_join_fold_desc> fd;                   // the round's items on one key ...
     std::vector<rhj_join_foldk_desc> kd;                  // ... and on tuple keys
@@ -2948,6 +3177,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     memset(&g_query_sum_info, 0, sizeof(g_query_sum_info));
     memset(&g_query_fold_info, 0, sizeof(g_query_fold_info));
     memset(&g_query_foldk_info, 0, sizeof(g_query_foldk_info));
+    memset(&g_query_fold_self_info, 0, sizeof(g_query_fold_self_info));
     bool invalid = false;                                 // the whole batch is validated before a device is touched
     int maxl = 0;
     std::vector<char> folds;
@@ -2956,8 +3186,9 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
         const int lv = query_levels(&queries[i], nrel, rels, nullptr);
         queries[i].rc = lv < 0 ? -3 : 0;
         invalid |= lv < 0;
-        const int how = !(g_query_fold && lv > 0) ? 0 : query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 1 :
-                        g_query_fold_keys && query_foldk_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 2 : 0;
+        const int how = !(g_query_fold && lv >= 0) ? 0 : lv > 0 && query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 1 :
+                        lv > 0 && g_query_fold_keys && query_foldk_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 2 :
+                        g_query_fold_self && query_folds_self(&queries[i], nrel, rels) ? 3 : 0;
         if (how) {
             bool fits = true;                             // a fold's sides have fewer than 2^32 rows
             for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
@@ -3550,6 +3781,9 @@ void rhj_set_query_sum_last(int on) { RhjApiLock api_lock; g_query_sum_last = on
 const rhj_query_batch_fold_info *rhj_query_batch_last_fold_info(void) { return &g_query_fold_info; }
 void rhj_set_query_fold(int on) { RhjApiLock api_lock; g_query_fold = on != 0; }
 const rhj_query_batch_foldk_info *rhj_query_batch_last_foldk_info(void) { return &g_query_foldk_info; }
+const rhj_query_batch_fold_self_info *rhj_query_batch_last_fold_self_info(void) { return &g_query_fold_self_info; }
+void rhj_set_query_fold_self(int on) { RhjApiLock api_lock; g_query_fold_self = on != 0; }
+int rhj_query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *plan) { return query_folds_plan(q, nrel, rels, plan); }
 void rhj_set_query_fold_keys(int on) { RhjApiLock api_lock; g_query_fold_keys = on != 0; }
 int rhj_query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps) { return query_foldk_plan(q, nrel, rels, root, steps); }
 int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps) { return query_fold_plan(q, nrel, rels, root, steps); }
@@ -3570,6 +3804,12 @@ int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
     return table_batch(items, n);
+}
+
+int rhj_fold_self_batch_device(rhj_fold_self_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return fold_self_batch(items, n);
 }
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */
