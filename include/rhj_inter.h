@@ -527,6 +527,69 @@ void rhj_set_query_fold_self(int on);
 typedef struct rhj_query_batch_fold_self_info { uint32_t self_calls, self_items, self_queries; } rhj_query_batch_fold_self_info;
 const rhj_query_batch_fold_self_info *rhj_query_batch_last_fold_self_info(void);
 
+/* rhj_join_foldk_batch_device with a row-id vector PER KEY WORD (csrc/rhj_join_foldn_batch.hip.h): what the key of a
+ * materialised node needs, whose words belong to different member bindings, each behind its own vector over the node's rows
+ * (DESIGN.md 4.18).  Word t of R's row at position p is d_colR[t][d_selR[t] ? d_selR[t][p] : p], of S's likewise, t < nkeys; nR
+ * and nS are the sides' positions.  Everything else is rhj_join_foldk_desc's: values, outputs and totals modulo 2^64, the slot
+ * {owner, A_0 ...}, equality decided on the owner's gathered words (each through its own vector), the hash, which side builds,
+ * chunks, tables, alignment, overlap, empty sides and validation (nkeys outside 1..RHJ_FOLD_MAX_KEYS or a NULL column among the
+ * first nkeys of a side with rows gives rc -3 before anything runs; a vector may always be NULL).  An item whose words all name
+ * one vector a side gives rhj_join_foldk_batch_device's outputs bit for bit.  The path is 16; rhj_last_stats() reserved 16. */
+typedef struct rhj_join_foldn_desc {
+    int             nkeys;                             /* 1 .. RHJ_FOLD_MAX_KEYS */
+    const uint64_t *d_colR[RHJ_FOLD_MAX_KEYS], *d_selR[RHJ_FOLD_MAX_KEYS]; uint64_t nR;     /* the parent side */
+    const uint64_t *d_colS[RHJ_FOLD_MAX_KEYS], *d_selS[RHJ_FOLD_MAX_KEYS]; uint64_t nS;     /* the child side */
+    int             nvalues, nouts;
+    rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
+    rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
+    int rc;                  /* out */
+    int path;                /* out: 16, or 0 when nothing was launched */
+} rhj_join_foldn_desc;
+int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n);
+
+/* Where a query can hand over from levels to folds over merged nodes, a pure function that needs no device.  -3 where
+ * rhj_query_levels gives it, 1 for every other query.  For a prefix L of the predicates the rule is: the first L predicates run as
+ * levels, so each merges its two bindings' nodes (B's node takes A's id, as rhj_query_levels names nodes) and joins its two
+ * (binding, column) terms in a union-find; the remaining predicates go through that same union-find in the order given; one whose
+ * terms are in one class already is dropped; a kept one with both bindings in one node is an inside predicate of that node, and
+ * more than RHJ_FOLD_SELF_MAX_TERMS of them on a node fail L; the other kept ones are grouped by unordered node pair, and a group
+ * of more than RHJ_FOLD_MAX_KEYS fails L; the groups must number (nodes - 1), else L fails.  levels is the smallest L that
+ * passes; it is at most max(njoins - 1, 0).  node[b] is binding b's node after those levels; root, steps[0 .. nsteps) and
+ * self[0 .. nself) are rhj_folds_plan's with node ids as child, parent and root: the schedule is rhj_query_fold_plan's over the
+ * nodes (fewest rounds, the lowest node id on a tie).  Key word t of a step is predicate joins[t]: the parent's word is the term
+ * whose binding lies in the parent node, the child's the other.  The predicates are not reordered: a first predicate off a cycle
+ * is merged like any other.  At levels 0 the plan is rhj_query_folds_plan's wherever that gives 1.  plan may be NULL. */
+typedef struct rhj_foldn_plan {
+    int levels, root, nsteps, nself;
+    int node[RHJ_QUERY_MAX_RELS];
+    rhj_foldk_step steps[RHJ_QUERY_MAX_RELS - 1];
+    int self[RHJ_QUERY_MAX_RELS * RHJ_FOLD_SELF_MAX_TERMS];
+} rhj_foldn_plan;
+int rhj_query_foldn_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_foldn_plan *plan);
+
+/* rhj_query_batch_device with this switch on as well as rhj_set_query_fold, rhj_set_query_fold_keys and rhj_set_query_fold_self
+ * (default off; environment RHJ_QUERY_FOLD_NODES=1; no effect unless all three are on): a query that none of the three plans
+ * takes, whose bindings each have fewer than 2^32 rows, runs rhj_query_foldn_plan's `levels` as levels and folds over its merged
+ * nodes from there.  The filter batch and the fold pass of the queries that fold from the start run as always;
+ * in the level loop such a query takes part in levels 0 .. levels - 1 only (it rebuilds there and never finishes, nor takes the
+ * rhj_set_query_sum_last form) and is parked; after the loop the nodes' pass runs over the parked queries still alive: ONE
+ * rhj_fold_self_batch_device call (a node with inside predicates is an item over the node's rows, each term's columns through the
+ * row-id vectors of the bindings it names; a query that is one node is one item with its views as outputs and finishes there),
+ * then the rounds, with weights and carried views per node; a key word, a child's view value and a root's lazy view read their
+ * column through the vector of the member binding named.  A round's items on one key are one rhj_join_fold_batch_device call,
+ * those on several words that name ONE binding a side one rhj_join_foldk_batch_device call, those whose words name several
+ * members of a side one rhj_join_foldn_batch_device call: at most three calls a round.  The zero-total exit, the 2^64 limit and
+ * the round buffers are the fold route's.  A query whose merged node has rhj_set_query_fold_node_rows's limit of rows or more at
+ * its hand-over (default and most 2^32; larger values clamp) stays on the levels to its end.
+ * rhj_query_batch_last_fold_nodes_info(): the rhj_join_foldn_batch_device calls and their items, the queries parked alive and
+ * the sum of their levels (all zero unless all four switches are on).  The fold, foldk and self infos count both passes'
+ * calls and items, and fold_queries the parked queries too; rhj_query_batch_info counts the levels and calls of the level queries
+ * and of the prefixes. */
+void rhj_set_query_fold_nodes(int on);
+void rhj_set_query_fold_node_rows(uint64_t limit);
+typedef struct rhj_query_batch_fold_nodes_info { uint32_t foldn_calls, foldn_items, node_queries, node_levels; } rhj_query_batch_fold_nodes_info;
+const rhj_query_batch_fold_nodes_info *rhj_query_batch_last_fold_nodes_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

@@ -45,6 +45,7 @@ INTER_SYMBOLS = [
     "rhj_join_fold_batch_device", "rhj_query_fold_plan", "rhj_set_query_fold", "rhj_query_batch_last_fold_info",
     "rhj_join_foldk_batch_device", "rhj_query_foldk_plan", "rhj_set_query_fold_keys", "rhj_query_batch_last_foldk_info",
     "rhj_fold_self_batch_device", "rhj_query_folds_plan", "rhj_set_query_fold_self", "rhj_query_batch_last_fold_self_info",
+    "rhj_join_foldn_batch_device", "rhj_query_foldn_plan", "rhj_set_query_fold_nodes", "rhj_set_query_fold_node_rows", "rhj_query_batch_last_fold_nodes_info",
 ]
 
 
@@ -304,6 +305,47 @@ class QueryBatchFoldSelfInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class JoinFoldNDesc(C.Structure):
+    """rhj_join_foldn_desc (include/rhj_inter.h): one item of rhj_join_foldn_batch_device"""
+    _fields_ = [("nkeys", C.c_int),
+                ("d_colR", C.c_void_p * FOLD_MAX_KEYS), ("d_selR", C.c_void_p * FOLD_MAX_KEYS), ("nR", C.c_uint64),
+                ("d_colS", C.c_void_p * FOLD_MAX_KEYS), ("d_selS", C.c_void_p * FOLD_MAX_KEYS), ("nS", C.c_uint64),
+                ("nvalues", C.c_int), ("nouts", C.c_int),
+                ("values", FoldFactor * FOLD_MAX_VALUES), ("outs", FoldOut * FOLD_MAX_OUTS),
+                ("rc", C.c_int), ("path", C.c_int)]
+
+
+class FoldNPlan(C.Structure):
+    """rhj_foldn_plan (include/rhj_inter.h): what rhj_query_foldn_plan returns"""
+    _fields_ = [("levels", C.c_int), ("root", C.c_int), ("nsteps", C.c_int), ("nself", C.c_int), ("node", C.c_int * QUERY_MAX_RELS),
+                ("steps", FoldKStep * (QUERY_MAX_RELS - 1)), ("self", C.c_int * (QUERY_MAX_RELS * FOLD_SELF_MAX_TERMS))]
+
+
+class QueryBatchFoldNodesInfo(C.Structure):
+    """rhj_query_batch_fold_nodes_info (include/rhj_inter.h): the rhj_join_foldn_batch_device calls the last
+    rhj_query_batch_device issued and their items, the queries that handed over from levels to folds over nodes, and the levels
+    they ran before"""
+    _fields_ = [("foldn_calls", C.c_uint32), ("foldn_items", C.c_uint32), ("node_queries", C.c_uint32), ("node_levels", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def query_foldn_plan(lib, query, nrel=None):
+    """rhj_query_foldn_plan on one query (relations, joins, filters, views): (levels, [node of every binding], root,
+    [(child, parent, round, [predicate indices])], [indices of the kept predicates inside a node]); ValueError on -3"""
+    arr, keep = query_descs([query])
+    plan = FoldNPlan()
+    rc = lib.rhj_query_foldn_plan(C.byref(arr[0]), nrel if nrel is not None else max(query[0]) + 1, None, C.byref(plan))
+    del keep
+    if rc == -3:
+        raise ValueError("rhj_query_foldn_plan refused the query")
+    if rc != 1:
+        raise RuntimeError("rhj_query_foldn_plan found no hand-over (%d)" % rc)
+    steps = [(s.child, s.parent, s.round, list(s.joins[:s.nkeys])) for s in plan.steps[:plan.nsteps]]
+    return plan.levels, list(plan.node[:len(query[0])]), plan.root, steps, list(plan.self[:plan.nself])
+
+
 def query_folds_plan(lib, query, nrel=None):
     """rhj_query_folds_plan on one query (relations, joins, filters, views): None when it does not fold, else
     (root, [(child, parent, round, [predicate indices])], [indices of the kept one-binding predicates]); ValueError on -3"""
@@ -322,11 +364,12 @@ def query_folds_plan(lib, query, nrel=None):
 class QueryInfo(dict):
     """rhj_query_batch_last_info() as a dict, with rhj_query_batch_last_sum_info(), rhj_query_batch_last_fold_info(),
     rhj_query_batch_last_foldk_info() and rhj_query_batch_last_fold_self_info() as the dicts in its attributes sum_info,
-    fold_info, foldk_info and fold_self_info"""
+    fold_info, foldk_info and fold_self_info, and rhj_query_batch_last_fold_nodes_info() in fold_nodes_info"""
     sum_info = None
     fold_info = None
     foldk_info = None
     fold_self_info = None
+    fold_nodes_info = None
 
 
 def query_descs(queries):
@@ -354,7 +397,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch", 15: "fold_self_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch", 15: "fold_self_batch", 16: "join_foldn_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -478,6 +521,14 @@ def load_library(path=None):
         L.rhj_set_query_fold_self.argtypes = [C.c_int]
         L.rhj_set_query_fold_self.restype = None
         L.rhj_query_batch_last_fold_self_info.restype = C.POINTER(QueryBatchFoldSelfInfo)
+    if hasattr(L, "rhj_join_foldn_batch_device"):     # (A/B runs load earlier builds through this module too)
+        L.rhj_join_foldn_batch_device.argtypes = [C.POINTER(JoinFoldNDesc), C.c_uint64]
+        L.rhj_query_foldn_plan.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(FoldNPlan)]
+        L.rhj_set_query_fold_nodes.argtypes = [C.c_int]
+        L.rhj_set_query_fold_nodes.restype = None
+        L.rhj_set_query_fold_node_rows.argtypes = [C.c_uint64]
+        L.rhj_set_query_fold_node_rows.restype = None
+        L.rhj_query_batch_last_fold_nodes_info.restype = C.POINTER(QueryBatchFoldNodesInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -809,6 +860,22 @@ class RHJ:
         Path id 14."""
         return self._fold_batch(JoinFoldKDesc, "rhj_join_foldk_batch_device", items, with_info)
 
+    def join_foldn_batch_device(self, items, with_info=False):
+        """join_foldk_batch_device with a row-id vector per key word (rhj_join_foldn_batch_device, include/rhj_inter.h): items as
+        there, but selR and selS are lists with one vector or None per key column; word t of a side's position p is
+        col[t][sel[t][p]] (col[t][p] without a vector).  A side's positions are the length of its first vector, or of its first
+        column when it has none.  Path id 16."""
+        return self._fold_batch(JoinFoldNDesc, "rhj_join_foldn_batch_device", items, with_info)
+
+    def set_query_fold_nodes(self, on):
+        """with set_query_fold, set_query_fold_keys and set_query_fold_self all on: a query none of them takes runs as levels only
+        until its merged nodes and remaining predicates form a tree, and folds over the nodes from there (default off)"""
+        self.lib.rhj_set_query_fold_nodes(1 if on else 0)
+
+    def set_query_fold_node_rows(self, limit):
+        """a query hands over to the folds over nodes only while its merged nodes have fewer rows than this (default and most 2^32)"""
+        self.lib.rhj_set_query_fold_node_rows(int(limit))
+
     def set_query_fold_keys(self, on):
         """with set_query_fold: the queries whose predicates are a tree once several predicates between two bindings are read as
         one join on a tuple of columns fold too (default off)"""
@@ -873,7 +940,7 @@ class RHJ:
         return self._fold_batch(JoinFoldDesc, "rhj_join_fold_batch_device", items, with_info)
 
     def _fold_batch(self, Desc, entry, items, with_info):
-        """the two fold batches: their items differ in the key columns alone"""
+        """the fold batches: their items differ in the key columns and row-id vectors alone"""
         torch = self.torch
         ptr = lambda t: t.data_ptr() if t is not None else None
         n = len(items)
@@ -882,7 +949,19 @@ class RHJ:
         for d, (cR, sR, cS, sS, values, outs) in zip(arr, items):
             if len(values) > FOLD_MAX_VALUES or len(outs) > FOLD_MAX_OUTS:
                 raise ValueError("an item has 0..%d values and 0..%d outputs, not %d and %d" % (FOLD_MAX_VALUES, FOLD_MAX_OUTS, len(values), len(outs)))
-            if Desc is JoinFoldKDesc:
+            if Desc is JoinFoldNDesc:
+                if not 1 <= len(cR) <= FOLD_MAX_KEYS or not len(cS) == len(cR) == len(sR) == len(sS):
+                    raise ValueError("an item has 1..%d key columns a side, as many on both, each with a vector or None, not %d and %d" % (FOLD_MAX_KEYS, len(cR), len(cS)))
+                d.nkeys = len(cR)
+                for cols, sels, d_col, d_sel, side in ((cR, sR, d.d_colR, d.d_selR, "nR"), (cS, sS, d.d_colS, d.d_selS, "nS")):
+                    given = [s for s in sels if s is not None]
+                    rows = given[0].shape[0] if given else cols[0].shape[0]
+                    if any(s.shape[0] != rows for s in given) or any(c.shape[0] < rows for c, s in zip(cols, sels) if s is None):
+                        raise ValueError("the vectors of a side have one length, and a column without a vector has as many rows at least")
+                    for t, (c, s) in enumerate(zip(cols, sels)):
+                        d_col[t], d_sel[t] = c.data_ptr(), ptr(s)
+                    setattr(d, side, rows)
+            elif Desc is JoinFoldKDesc:
                 if not 1 <= len(cR) <= FOLD_MAX_KEYS or len(cS) != len(cR):
                     raise ValueError("an item has 1..%d key columns a side, as many on both, not %d and %d" % (FOLD_MAX_KEYS, len(cR), len(cS)))
                 d.nkeys = len(cR)
@@ -968,6 +1047,7 @@ class RHJ:
         info.fold_info = self.lib.rhj_query_batch_last_fold_info().contents.as_dict()
         info.foldk_info = self.lib.rhj_query_batch_last_foldk_info().contents.as_dict()
         info.fold_self_info = self.lib.rhj_query_batch_last_fold_self_info().contents.as_dict()
+        info.fold_nodes_info = self.lib.rhj_query_batch_last_fold_nodes_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

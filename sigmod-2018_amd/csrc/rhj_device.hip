@@ -169,6 +169,8 @@ int g_same_device = 0;               // RHJ_DEVICES_SAME=1 (tests): every contex
 int g_query_fold = 0;                // 1: rhj_query_batch_device sums the queries whose predicates are a tree by rounds of rhj_join_fold_batch_device items (rhj_set_query_fold, env RHJ_QUERY_FOLD)
 int g_query_fold_keys = 0;           // 1: with g_query_fold, the queries whose predicates are a tree once parallel predicates are grouped fold too, the groups as rhj_join_foldk_batch_device items (rhj_set_query_fold_keys, env RHJ_QUERY_FOLD_KEYS)
 int g_query_fold_self = 0;           // 1: with g_query_fold, the queries that fold once one-binding and implied predicates are taken care of fold too, after one rhj_fold_self_batch_device call (rhj_set_query_fold_self, env RHJ_QUERY_FOLD_SELF)
+int g_query_fold_nodes = 0;          // 1: with the three fold switches above all on, a query none of them takes runs by levels only until its merged nodes and remaining predicates are a tree, and folds over the nodes from there (rhj_set_query_fold_nodes, env RHJ_QUERY_FOLD_NODES)
+uint64_t g_query_fold_node_rows = 1ull << 32;            // a query hands over only while every merged node has fewer rows than this (rhj_set_query_fold_node_rows; a fold's sides are below 2^32 rows)
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -202,6 +204,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_FOLD"))) g_query_fold = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_KEYS"))) g_query_fold_keys = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_SELF"))) g_query_fold_self = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_FOLD_NODES"))) g_query_fold_nodes = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1366,7 +1369,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2182,9 +2185,10 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
 }
 
 // ---- the table batches: batched final joins and weighted join folds (rhj_join_sum_batch.hip.h, rhj_join_fold_batch.hip.h) --------
-// rhj_join_sum_batch_device (path 12), rhj_join_fold_batch_device (path 13) and rhj_join_foldk_batch_device (path 14, the folds on
-// tuple keys of rhj_join_foldk_batch.hip.h) are ONE scheme over three descriptors (templates over rhj_join_sum_desc /
-// rhj_join_fold_desc / rhj_join_foldk_desc, as filter_batch is over its two).  Every item with two non-empty sides runs in the
+// rhj_join_sum_batch_device (path 12), rhj_join_fold_batch_device (path 13), rhj_join_foldk_batch_device (path 14, the folds on
+// tuple keys of rhj_join_foldk_batch.hip.h) and rhj_join_foldn_batch_device (path 16, those with a row-id vector per key word,
+// rhj_join_foldn_batch.hip.h) are ONE scheme over four descriptors (templates over rhj_join_sum_desc / rhj_join_fold_desc /
+// rhj_join_foldk_desc / rhj_join_foldn_desc, as filter_batch is over its two).  Every item with two non-empty sides runs in the
 // launches of its chunk; there is no run-alone class.  Every item has a hash table in the arena g.jsum_arena, which both share.
 // A chunk holds at most JSUM_MAX_ITEMS items and JSUM_MAX_TILES tiles of both sides together, so that no launch's grid passes the
 // limit (conditions, as the apply batch's), and JSUM_ARENA_BYTES of tables, and a batch beyond any of them is cut in call order:
@@ -2209,6 +2213,7 @@ template <class D> struct tbatch_dev;
 template <> struct tbatch_dev<rhj_join_sum_desc> { using type = JoinSumDesc; static constexpr size_t words = JSUM_WORDS; };
 template <> struct tbatch_dev<rhj_join_fold_desc> { using type = JoinFoldDesc; static constexpr size_t words = FOLD_WORDS; };
 template <> struct tbatch_dev<rhj_join_foldk_desc> { using type = JoinFoldKDesc; static constexpr size_t words = FOLDK_WORDS; };
+template <> struct tbatch_dev<rhj_join_foldn_desc> { using type = JoinFoldNDesc; static constexpr size_t words = FOLDK_WORDS; };
 
 static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
@@ -2224,8 +2229,10 @@ static bool tbatch_valid(const rhj_join_fold_desc &q)
         if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
     return true;
 }
-// the fold batch's rule on tuple keys: 1..RHJ_FOLD_MAX_KEYS key columns, the first nkeys of a side with rows all given
-static bool tbatch_valid(const rhj_join_foldk_desc &q)
+// the fold batch's rule on tuple keys: 1..RHJ_FOLD_MAX_KEYS key columns, the first nkeys of a side with rows all given (a word's
+// row-id vector may always be NULL, so the two tuple-key descriptors have one rule)
+template <class D>
+static bool tbatch_valid_tuple(const D &q)
 {
     if (q.nkeys < 1 || q.nkeys > RHJ_FOLD_MAX_KEYS || q.nR >= JSUM_MAX_ROWS || q.nS >= JSUM_MAX_ROWS) return false;
     for (int t = 0; t < q.nkeys; ++t)
@@ -2235,14 +2242,18 @@ static bool tbatch_valid(const rhj_join_foldk_desc &q)
         if (q.outs[o].value < 0 || q.outs[o].value >= q.nvalues) return false;
     return true;
 }
+static bool tbatch_valid(const rhj_join_foldk_desc &q) { return tbatch_valid_tuple(q); }
+static bool tbatch_valid(const rhj_join_foldn_desc &q) { return tbatch_valid_tuple(q); }
 
 static void tbatch_zero(rhj_join_sum_desc &q) { q.matches = 0; for (int t = 0; t < q.nterms; ++t) q.terms[t].sum = 0; }
 static void tbatch_zero(rhj_join_fold_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
 static void tbatch_zero(rhj_join_foldk_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
+static void tbatch_zero(rhj_join_foldn_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
 
 static inline uint64_t tbatch_table_bytes(const rhj_join_sum_desc &q) { return tbatch_slots(q) * JSUM_SLOT_BYTES; }
 static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 static inline uint64_t tbatch_table_bytes(const rhj_join_foldk_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_foldn_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 
 // the fields both device descriptors have
 template <class D, class Dev>
@@ -2297,6 +2308,20 @@ static void tbatch_fill(const rhj_join_foldk_desc &q, unsigned long long *table,
     d.nkeys = q.nkeys;
     tbatch_fill_fold(q, d, t);
 }
+static void tbatch_fill(const rhj_join_foldn_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldNDesc &d, uint32_t (&t)[3])
+{
+    memset((void *)&d, 0, sizeof(d));
+    for (int k = 0; k < q.nkeys; ++k) {                  // (a word beyond nkeys keeps no pointer: the kernels test nkeys first)
+        d.col[0][k] = q.d_colR[k]; d.sel[0][k] = q.d_selR[k];
+        d.col[1][k] = q.d_colS[k]; d.sel[1][k] = q.d_selS[k];
+    }
+    d.n[0] = q.nR; d.n[1] = q.nS;
+    d.build = jsum_build_side(q.nR, q.nS);
+    d.log2_slots = jsum_log2_slots(d.n[d.build]);
+    d.table = table; d.words = words;
+    d.nkeys = q.nkeys;
+    tbatch_fill_fold(q, d, t);
+}
 
 static void tbatch_launch(const rhj_join_sum_desc &, const JoinSumDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
 {
@@ -2316,6 +2341,12 @@ static void tbatch_launch(const rhj_join_foldk_desc &, const JoinFoldKDesc *dd, 
     RHJ_LAUNCH(k_foldk_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_foldk_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
+static void tbatch_launch(const rhj_join_foldn_desc &, const JoinFoldNDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
+{
+    if (t[0]) RHJ_LAUNCH(k_foldn_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
+    RHJ_LAUNCH(k_foldn_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_foldn_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
+}
 
 static void tbatch_take(rhj_join_sum_desc &q, const unsigned long long *h)
 {
@@ -2324,16 +2355,20 @@ static void tbatch_take(rhj_join_sum_desc &q, const unsigned long long *h)
 }
 static void tbatch_take(rhj_join_fold_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[FOLD_W_TOTAL + o]; }
 static void tbatch_take(rhj_join_foldk_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[o]; }
+static void tbatch_take(rhj_join_foldn_desc &q, const unsigned long long *h) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = h[o]; }
 
 static inline int tbatch_path(const rhj_join_sum_desc &) { return PATH_BATCH_JOIN_SUM; }
 static inline int tbatch_path(const rhj_join_fold_desc &) { return PATH_BATCH_JOIN_FOLD; }
 static inline int tbatch_path(const rhj_join_foldk_desc &) { return PATH_BATCH_JOIN_FOLDK; }
+static inline int tbatch_path(const rhj_join_foldn_desc &) { return PATH_BATCH_JOIN_FOLDN; }
 static inline const char *tbatch_noun(const rhj_join_sum_desc &) { return "join sums"; }
 static inline const char *tbatch_noun(const rhj_join_fold_desc &) { return "join folds"; }
 static inline const char *tbatch_noun(const rhj_join_foldk_desc &) { return "join folds on tuple keys"; }
+static inline const char *tbatch_noun(const rhj_join_foldn_desc &) { return "join folds on the keys of nodes"; }
 static inline uint64_t tbatch_matches(const rhj_join_sum_desc &q) { return q.matches; }
 static inline uint64_t tbatch_matches(const rhj_join_fold_desc &) { return 0; }           // (the folds' statistics have no matches)
 static inline uint64_t tbatch_matches(const rhj_join_foldk_desc &) { return 0; }
+static inline uint64_t tbatch_matches(const rhj_join_foldn_desc &) { return 0; }
 
 // One chunk: items[which[lo, hi)], every one valid and with two non-empty sides; their tables take `bytes` together.
 template <class D>
@@ -2585,13 +2620,15 @@ rhj_query_batch_sum_info g_query_sum_info = {};
 rhj_query_batch_fold_info g_query_fold_info = {};
 rhj_query_batch_foldk_info g_query_foldk_info = {};
 rhj_query_batch_fold_self_info g_query_fold_self_info = {};
+rhj_query_batch_fold_nodes_info g_query_fold_nodes_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
     rhj_query_desc                 *queries;
     uint64_t                        n;
     std::vector<QueryState>         st;
-    std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, 2 when only rhj_set_query_fold_keys lets it, 3 when only rhj_set_query_fold_self does
+    std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, 2 when only rhj_set_query_fold_keys lets it, 3 when only rhj_set_query_fold_self does, 4 when it hands over from levels to folds over its nodes (rhj_set_query_fold_nodes)
+    std::vector<int>                park;                 // of a query with folds 4: the levels it runs before it is parked for the nodes' pass (empty: no such query)
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
     std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
     std::vector<size_t>             where;                // ... and its descriptor in ed / jd / sd
@@ -2601,6 +2638,7 @@ struct QueryRun {                                         // what the stages of 
     std::vector<rhj_join_sum_desc>  sd;
     auto column(const rhj_query_desc &q, int b, int c) const { return rels[q.rels[b]].d_columns[c]; }
     bool finishes(uint64_t i, int l) const { return queries[i].njoins == 0 || l == queries[i].njoins - 1; }
+    bool parked(uint64_t i, int l) const { return !park.empty() && park[i] && l >= park[i]; }        // its level prefix is over
 };
 
 // The filters of all queries: all of one binding are one conjunction, all of them over all queries one call.
@@ -2675,7 +2713,7 @@ static int query_level_joins(QueryRun &R, int l)
     for (uint64_t i = 0; i < R.n; ++i) {
         const rhj_query_desc &q = R.queries[i];
         const QueryState &s = R.st[i];
-        if (!s.alive || (q.njoins <= l && (l || q.njoins))) continue;
+        if (!s.alive || (q.njoins <= l && (l || q.njoins)) || R.parked(i, l)) continue;
         R.active.push_back(i);
         if (q.njoins == 0) { R.kind.push_back(2); R.where.push_back(0); continue; }     // no predicate at all: level 0 sums its views
         const rhj_query_join &p = q.joins[l];
@@ -2977,6 +3015,108 @@ static int query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_
     return 1;
 }
 
+// The plan that hands over from levels to folds over merged nodes (include/rhj_inter.h): the shortest prefix L of
+// the predicates after which, run as levels, the rest is query_folds_plan's tree over the NODES.  One prefix: the first L
+// predicates merge their nodes as query_levels does and join their terms' classes; the others go through the same union-find in
+// order, a predicate inside one class dropped, a kept one inside one node counted on that node, the others grouped by node pair.
+static bool query_foldn_prefix(const rhj_query_desc *q, int L, rhj_foldn_plan *plan)
+{
+    std::vector<std::pair<int, int>> terms;               // a class member: (binding, column) ...
+    std::vector<size_t> up;                               // ... and the member above it (itself: the class's root)
+    const auto term = [&](int b, int c) {
+        size_t k = 0;
+        while (k < terms.size() && terms[k] != std::make_pair(b, c)) ++k;
+        if (k == terms.size()) { terms.emplace_back(b, c); up.push_back(k); }
+        while (up[k] != k) k = up[k];
+        return k;
+    };
+    int node[RHJ_QUERY_MAX_RELS];
+    for (int b = 0; b < q->nrels; ++b) node[b] = b;
+    for (int l = 0; l < L; ++l) {
+        const rhj_query_join &p = q->joins[l];
+        const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
+        if (ca != cb) up[cb] = ca;
+        const int na = node[p.relA], nb = node[p.relB];
+        for (int x = 0; x < q->nrels; ++x) if (node[x] == nb) node[x] = na;      // the two nodes merge into A's
+    }
+    struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
+    std::vector<Group> groups;
+    std::vector<int> self;
+    int on_node[RHJ_QUERY_MAX_RELS] = {};
+    for (int l = L; l < q->njoins; ++l) {
+        const rhj_query_join &p = q->joins[l];
+        const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
+        if (ca == cb) continue;                           // said already by the predicates before it
+        up[cb] = ca;
+        const int na = node[p.relA], nb = node[p.relB];
+        if (na == nb) {
+            if (++on_node[na] > RHJ_FOLD_SELF_MAX_TERMS) return false;          // more terms than an item has
+            self.push_back(l);
+            continue;
+        }
+        const int a = na < nb ? na : nb, b = na < nb ? nb : na;
+        size_t k = 0;
+        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
+        if (k == groups.size()) groups.push_back(Group{a, b, 0, {}});
+        if (groups[k].n == RHJ_FOLD_MAX_KEYS) return false;                     // more key words than a tuple has
+        groups[k].joins[groups[k].n++] = l;
+    }
+    int id[RHJ_QUERY_MAX_RELS], of[RHJ_QUERY_MAX_RELS], nodes = 0;              // node -> its rank among the nodes, ascending, and back
+    for (int b = 0; b < q->nrels; ++b) {
+        bool is_node = false;
+        for (int x = 0; x < q->nrels; ++x) is_node |= node[x] == b;
+        id[b] = is_node ? nodes : -1;
+        if (is_node) of[nodes++] = b;
+    }
+    if ((int)groups.size() != nodes - 1) return false;    // a true cycle over the nodes
+    if (!plan) return true;
+    memset(plan, 0, sizeof(*plan));
+    plan->levels = L;
+    for (int b = 0; b < q->nrels; ++b) plan->node[b] = node[b];
+    plan->nself = (int)self.size();
+    for (size_t k = 0; k < self.size(); ++k) plan->self[k] = self[k];
+    plan->nsteps = (int)groups.size();
+    plan->root = of[0];
+    if (groups.empty()) return true;                      // one node: nothing to schedule
+    // fold_schedule over the nodes by rank (the ranks ascend with the ids, so "the lowest first" means the same): one edge a group
+    std::vector<rhj_query_join> first;
+    for (const Group &gr : groups) {
+        const rhj_query_join &p = q->joins[gr.joins[0]];
+        first.push_back(rhj_query_join{id[node[p.relA]], p.colA, id[node[p.relB]], p.colB});
+    }
+    rhj_query_desc tree = *q;
+    tree.nrels = nodes; tree.njoins = (int)first.size(); tree.joins = first.data();
+    int best = -1;
+    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
+    for (int r = 0; r < nodes; ++r) {
+        const int rounds = fold_schedule(tree, r, mine);
+        if (best >= 0 && rounds >= best) continue;
+        best = rounds; plan->root = of[r];
+        memcpy(kept, mine, sizeof(kept));
+    }
+    for (int k = 0; k < plan->nsteps; ++k) {
+        const int c = of[kept[k].child], p = of[kept[k].parent];
+        rhj_foldk_step &st = plan->steps[k];
+        st.child = c; st.parent = p; st.round = kept[k].round;
+        for (const Group &gr : groups) {
+            if (gr.a != (c < p ? c : p) || gr.b != (c < p ? p : c)) continue;
+            st.nkeys = gr.n;
+            for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
+        }
+    }
+    return true;
+}
+
+static int query_foldn_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_foldn_plan *plan)
+{
+    if (!q) return -3;
+    const int lv = query_levels(q, nrel, rels, nullptr);
+    if (lv < 0) return -3;
+    for (int L = 0; L <= (lv > 0 ? lv - 1 : 0); ++L)
+        if (query_foldn_prefix(q, L, plan)) return 1;
+    return 0;                                             // (not reached: with one predicate left the rest is one step, one term or nothing)
+}
+
 // whether the fold route takes a query because of rhj_set_query_fold_self: the plan above, its steps within the key switch
 static bool query_folds_self(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels)
 {
@@ -2991,12 +3131,13 @@ struct FoldQuery {                                        // a query on the fold
     int             root, nsteps, next;                   // next: the first step not yet run
     int             nself, self[RHJ_QUERY_MAX_RELS * RHJ_FOLD_SELF_MAX_TERMS];    // the one-binding predicates of a query rhj_set_query_fold_self let in
     rhj_foldk_step  steps[FOLD_MAX_STEPS];                // (nkeys 1 throughout unless rhj_set_query_fold_keys let the query in)
-    const uint64_t *w[RHJ_QUERY_MAX_RELS];                // binding -> its weight vector; nullptr: ones
-    const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // binding, view -> the view's partial sums per row, when the binding carries the view
+    const uint64_t *w[RHJ_QUERY_MAX_RELS];                // node -> its weight vector; nullptr: ones.  (A node is a binding until levels have merged some: QueryState::node)
+    const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // node, view -> the view's partial sums per row, when the node carries the view
 };
 
-// Before round 0, ONE fold_self_batch call over the queries rhj_set_query_fold_self let in: a binding with one-binding predicates
-// gets its first weight vector (0 / 1 per row of its hit list), and a query of one binding is finished.
+// Before round 0, ONE fold_self_batch call over the queries with predicates inside a node (rhj_set_query_fold_self's, whose nodes
+// are their bindings, and rhj_set_query_fold_nodes's): a node with such predicates gets its first weight vector (0 / 1 per row),
+// each column of a term read through the vector of the member binding it names, and a query of one node is finished.
 static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
 {
     std::vector<rhj_fold_self_desc> sd;
@@ -3006,19 +3147,20 @@ static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
         const FoldQuery &f = fq[k];
         const rhj_query_desc &q = R.queries[f.i];
         const QueryState &s = R.st[f.i];
-        if (R.folds[f.i] != 3) continue;
+        if (R.folds[f.i] < 3) continue;
         for (int b = 0; b < q.nrels; ++b) {
+            if (s.node[b] != b) continue;                 // (a node carries the id of one of its members)
             rhj_fold_self_desc d = {};
             for (int t = 0; t < f.nself; ++t) {
                 const rhj_query_join &p = q.joins[f.self[t]];
-                if (p.relA != b) continue;
-                d.terms[d.nterms++] = rhj_fold_eq_term{R.column(q, b, p.colA), s.vec[b], R.column(q, b, p.colB), s.vec[b]};
+                if (s.node[p.relA] != b) continue;
+                d.terms[d.nterms++] = rhj_fold_eq_term{R.column(q, p.relA, p.colA), s.vec[p.relA], R.column(q, p.relB, p.colB), s.vec[p.relB]};
             }
-            if (d.nterms == 0 && q.nrels > 1) continue;   // no predicate of its own: the binding's weight stays ones
+            if (d.nterms == 0 && f.nsteps > 0) continue;  // no predicate of its own: the node's weight stays ones
             d.n = s.rows[b];
             d.nouts = 1;                                  // output 0: ones, so its total is the rows that pass
-            if (q.nrels == 1) {                           // the whole query: the views' sums, nothing written
-                for (int v = 0; v < q.nviews; ++v) d.outs[d.nouts++].p = rhj_fold_factor{nullptr, s.vec[0], R.column(q, 0, q.views[v].col)};
+            if (f.nsteps == 0) {                          // the whole query is this node: the views' sums, nothing written
+                for (int v = 0; v < q.nviews; ++v) d.outs[d.nouts++].p = rhj_fold_factor{nullptr, s.vec[q.views[v].rel], R.column(q, q.views[v].rel, q.views[v].col)};
             } else {
                 wb.take(sd.size(), 0, d.n);
             }
@@ -3028,7 +3170,7 @@ static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
     if (sd.empty()) return 0;
     if (wb.resolve(g_qb.self, [&](size_t a, int, char *p) { sd[a].outs[0].d_out = (uint64_t *)p; })) return -1;
     ++g_query_fold_self_info.self_calls;
-    g_query_fold_self_info.self_items = (uint32_t)sd.size();
+    g_query_fold_self_info.self_items += (uint32_t)sd.size();
     if (const int rc = fold_self_batch(sd.data(), sd.size())) return rc;       // (0 or an error: the items are valid)
     for (size_t a = 0; a < sd.size(); ++a) {
         FoldQuery &f = fq[who[a].first];
@@ -3037,7 +3179,7 @@ static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
         const rhj_fold_self_desc &d = sd[a];
         if (!s.alive) continue;                           // (finished by another item of this call)
         if (d.outs[0].total == 0) { s.alive = false; continue; }               // no row passes: rows = 0, sums 0
-        if (q.nrels == 1) {
+        if (f.nsteps == 0) {
             q.rows = d.outs[0].total;
             for (int v = 0; v < q.nviews; ++v) q.sums[v] = d.outs[1 + v].total;
             s.alive = false;                              // finished
@@ -3049,16 +3191,27 @@ static int query_fold_self(QueryRun &R, std::vector<FoldQuery> &fq)
 }
 
 // The folding queries still alive after the filters, round by round: every round is one table_batch call over all their items on
-// one key and, with rhj_set_query_fold_keys, one over all their items on tuple keys.
-static int query_folds(QueryRun &R)
+// one key and, with rhj_set_query_fold_keys, one over all their items on tuple keys.  The same over NODES (nodes_pass, after the
+// level loop) for the queries that were parked after their level prefix: a step folds a node into a node, a key word, a child's
+// view value and a root's lazy view read their column through the vector of the member binding that the predicate or view names
+// (QueryState::vec, left by the levels), and a tuple whose words name several members of a side is an item of a third call,
+// rhj_join_foldn_batch_device's.  Before the levels every node is its binding, so the first pass issues what it always did.
+static int query_folds(QueryRun &R, bool nodes_pass)
 {
     std::vector<FoldQuery> fq;
     int rounds = 0;
     for (uint64_t i = 0; i < R.n && !R.folds.empty(); ++i) {
-        if (!R.folds[i] || !R.st[i].alive) continue;
+        if (!R.folds[i] || !R.st[i].alive || (R.folds[i] == 4) != nodes_pass) continue;
         FoldQuery f = {};
         f.i = i;
-        if (R.folds[i] == 3) {                            // rhj_set_query_fold_self's: possibly no step at all
+        if (R.folds[i] == 4) {                            // parked alive after its level prefix
+            rhj_foldn_plan plan;
+            if (query_foldn_plan(&R.queries[i], INT_MAX, nullptr, &plan) != 1 || plan.levels != R.park[i]) { fprintf(stderr, "rhj: a parked query has no plan over its nodes\n"); return -1; }
+            f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
+            memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
+            ++g_query_fold_nodes_info.node_queries;
+            g_query_fold_nodes_info.node_levels += (uint32_t)plan.levels;
+        } else if (R.folds[i] == 3) {                            // rhj_set_query_fold_self's: possibly no step at all
             rhj_folds_plan plan;
             if (query_folds_plan(&R.queries[i], INT_MAX, nullptr, &plan) != 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
             f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
@@ -3072,18 +3225,19 @@ static int query_folds(QueryRun &R)
         if (f.nsteps && f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
         fq.push_back(f);
     }
-    g_query_fold_info.fold_queries = (uint32_t)fq.size();
+    g_query_fold_info.fold_queries += (uint32_t)fq.size();
     if (const int rc = query_fold_self(R, fq)) return rc;
     if (g_qb.fold.size() < (size_t)rounds) g_qb.fold.resize((size_t)rounds);
     std::vector<rhj_join_fold_desc> fd;                   // the round's items on one key ...
-    std::vector<rhj_join_foldk_desc> kd;                  // ... and on tuple keys
-    std::vector<std::pair<bool, size_t>> where;           // an item, in the order issued: whether it is in kd, and its place there or in fd
+    std::vector<rhj_join_foldk_desc> kd;                  // ... on tuple keys ...
+    std::vector<rhj_join_foldn_desc> nd;                  // ... and on tuple keys whose words name several members of a node
+    std::vector<std::pair<int, size_t>> where;            // an item, in the order issued: 0 in fd, 1 in kd, 2 in nd, and its place there
     std::vector<size_t> who;                              // an item's query in fq
     std::vector<int> par;                                 // an item's parent binding
     std::vector<std::array<int, RHJ_FOLD_MAX_OUTS>> view; // an item's outputs: the view each belongs to, -1 the weight
     for (int r = 0; r < rounds; ++r) {
         QueryBump ob;
-        fd.clear(); kd.clear(); where.clear(); who.clear(); par.clear(); view.clear();
+        fd.clear(); kd.clear(); nd.clear(); where.clear(); who.clear(); par.clear(); view.clear();
         for (size_t k = 0; k < fq.size(); ++k) {
             FoldQuery &f = fq[k];
             const rhj_query_desc &q = R.queries[f.i];
@@ -3095,19 +3249,25 @@ static int query_folds(QueryRun &R)
                 rhj_join_fold_desc d = {};
                 std::array<int, RHJ_FOLD_MAX_OUTS> ov;
                 const uint64_t *keyR[RHJ_FOLD_MAX_KEYS] = {}, *keyS[RHJ_FOLD_MAX_KEYS] = {};
+                int memR[RHJ_FOLD_MAX_KEYS] = {}, memS[RHJ_FOLD_MAX_KEYS] = {};     // the member binding a word is read through
+                bool one_member = true;                    // every word of a side names the member its word 0 names
                 for (int t = 0; t < step.nkeys; ++t) {     // the predicates between the two: word t of both sides
                     const rhj_query_join &p = q.joins[step.joins[t]];
-                    keyR[t] = p.relA == P ? R.column(q, P, p.colA) : R.column(q, P, p.colB);
-                    keyS[t] = p.relA == P ? R.column(q, S, p.colB) : R.column(q, S, p.colA);
+                    const bool a_is_parent = s.node[p.relA] == P;
+                    memR[t] = a_is_parent ? p.relA : p.relB; memS[t] = a_is_parent ? p.relB : p.relA;
+                    keyR[t] = R.column(q, memR[t], a_is_parent ? p.colA : p.colB);
+                    keyS[t] = R.column(q, memS[t], a_is_parent ? p.colB : p.colA);
+                    one_member &= memR[t] == memR[0] && memS[t] == memS[0];
                 }
                 d.d_colR = keyR[0]; d.d_colS = keyS[0];
-                d.d_selR = s.vec[P]; d.nR = s.rows[P];
-                d.d_selS = s.vec[S]; d.nS = s.rows[S];
+                d.d_selR = s.vec[memR[0]]; d.nR = s.rows[P];
+                d.d_selS = s.vec[memS[0]]; d.nS = s.rows[S];
                 int value_of[RHJ_QUERY_MAX_VIEWS];
                 d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
                 for (int v = 0; v < q.nviews; ++v) {
+                    const int x = q.views[v].rel;
                     value_of[v] = -1;
-                    if (q.views[v].rel == S) d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], s.vec[S], R.column(q, S, q.views[v].col)};
+                    if (s.node[x] == S)      d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], s.vec[x], R.column(q, x, q.views[v].col)};
                     else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
                 }
                 const auto out = [&](int value, rhj_fold_factor p, int v) {
@@ -3120,21 +3280,34 @@ static int query_folds(QueryRun &R)
                 for (int v = 0; v < q.nviews; ++v) {
                     if (value_of[v] >= 0)                    out(value_of[v], rhj_fold_factor{f.w[P], nullptr, nullptr}, v);      // a view coming from the child
                     else if (f.acc[P][v])                    out(0, rhj_fold_factor{f.acc[P][v], nullptr, nullptr}, v);           // a view the parent carried
-                    else if (last && q.views[v].rel == P)    out(0, rhj_fold_factor{f.w[P], s.vec[P], R.column(q, P, q.views[v].col)}, v);   // a view on the root: lazy until now
+                    else if (last && s.node[q.views[v].rel] == P)    out(0, rhj_fold_factor{f.w[P], s.vec[q.views[v].rel], R.column(q, q.views[v].rel, q.views[v].col)}, v);   // a view on the root: lazy until now
                 }
                 who.push_back(k); par.push_back(P); view.push_back(ov);
-                if (step.nkeys == 1) { where.emplace_back(false, fd.size()); fd.push_back(d); continue; }
+                if (step.nkeys == 1) { where.emplace_back(0, fd.size()); fd.push_back(d); continue; }
+                if (!one_member) {                         // the same item, every word through its member's vector
+                    rhj_join_foldn_desc t = {};
+                    t.nkeys = step.nkeys;
+                    for (int w = 0; w < step.nkeys; ++w) {
+                        t.d_colR[w] = keyR[w]; t.d_selR[w] = s.vec[memR[w]];
+                        t.d_colS[w] = keyS[w]; t.d_selS[w] = s.vec[memS[w]];
+                    }
+                    t.nR = d.nR; t.nS = d.nS;
+                    t.nvalues = d.nvalues; t.nouts = d.nouts;
+                    memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
+                    where.emplace_back(2, nd.size()); nd.push_back(t);
+                    continue;
+                }
                 rhj_join_foldk_desc t = {};                // the same item on its tuple of columns
                 t.nkeys = step.nkeys;
                 for (int w = 0; w < step.nkeys; ++w) { t.d_colR[w] = keyR[w]; t.d_colS[w] = keyS[w]; }
                 t.d_selR = d.d_selR; t.nR = d.nR; t.d_selS = d.d_selS; t.nS = d.nS;
                 t.nvalues = d.nvalues; t.nouts = d.nouts;
                 memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
-                where.emplace_back(true, kd.size()); kd.push_back(t);
+                where.emplace_back(1, kd.size()); kd.push_back(t);
             }
         }
         if (where.empty()) continue;
-        const auto outs_of = [&](size_t a) { return where[a].first ? kd[where[a].second].outs : fd[where[a].second].outs; };
+        const auto outs_of = [&](size_t a) { return where[a].first == 2 ? nd[where[a].second].outs : where[a].first ? kd[where[a].second].outs : fd[where[a].second].outs; };
         if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { outs_of(a)[o].d_out = (uint64_t *)p; })) return -1;
         if (!fd.empty()) {
             ++g_query_fold_info.fold_calls;
@@ -3146,12 +3319,17 @@ static int query_folds(QueryRun &R)
             g_query_foldk_info.foldk_items += (uint32_t)kd.size();
             if (const int rc = table_batch(kd.data(), kd.size())) return rc;
         }
+        if (!nd.empty()) {
+            ++g_query_fold_nodes_info.foldn_calls;
+            g_query_fold_nodes_info.foldn_items += (uint32_t)nd.size();
+            if (const int rc = table_batch(nd.data(), nd.size())) return rc;
+        }
         for (size_t a = 0; a < where.size(); ++a) {
             FoldQuery &f = fq[who[a]];
             rhj_query_desc &q = R.queries[f.i];
             QueryState &s = R.st[f.i];
             const rhj_fold_out *outs = outs_of(a);
-            const int nouts = where[a].first ? kd[where[a].second].nouts : fd[where[a].second].nouts;
+            const int nouts = where[a].first == 2 ? nd[where[a].second].nouts : where[a].first ? kd[where[a].second].nouts : fd[where[a].second].nouts;
             if (!s.alive) continue;                       // (finished by another item of this round)
             if (outs[0].total == 0) { s.alive = false; continue; }           // the subtree's join is empty: rows = 0, sums 0
             const bool last = outs[0].d_out == nullptr;
@@ -3178,6 +3356,9 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     memset(&g_query_fold_info, 0, sizeof(g_query_fold_info));
     memset(&g_query_foldk_info, 0, sizeof(g_query_foldk_info));
     memset(&g_query_fold_self_info, 0, sizeof(g_query_fold_self_info));
+    memset(&g_query_fold_nodes_info, 0, sizeof(g_query_fold_nodes_info));
+    const bool hand_over = g_query_fold && g_query_fold_keys && g_query_fold_self && g_query_fold_nodes;
+    std::vector<int> park;
     bool invalid = false;                                 // the whole batch is validated before a device is touched
     int maxl = 0;
     std::vector<char> folds;
@@ -3189,10 +3370,20 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
         const int how = !(g_query_fold && lv >= 0) ? 0 : lv > 0 && query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 1 :
                         lv > 0 && g_query_fold_keys && query_foldk_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 2 :
                         g_query_fold_self && query_folds_self(&queries[i], nrel, rels) ? 3 : 0;
-        if (how) {
+        int prefix = 0;                                   // of a query none of the three plans takes: the levels before its nodes fold
+        if (!how && hand_over && lv >= 0) {
+            rhj_foldn_plan plan;
+            if (query_foldn_plan(&queries[i], nrel, rels, &plan) == 1) prefix = plan.levels;         // (>= 1: at 0 levels query_folds_plan took it)
+        }
+        if (how || prefix) {
             bool fits = true;                             // a fold's sides have fewer than 2^32 rows
             for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
-            folds[i] = fits ? (char)how : 0;
+            folds[i] = !fits ? 0 : how ? (char)how : 4;
+            if (fits && prefix) {
+                if (park.empty()) park.assign(n, 0);
+                park[i] = prefix;
+                if (prefix > maxl) maxl = prefix;         // (the prefix runs in the level loop)
+            }
         }
         if (lv > maxl && !(g_query_fold && folds[i])) maxl = lv;       // (the levels of the queries that run by levels)
     }
@@ -3206,16 +3397,32 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     {
         QueryTimingOff inner_untimed;
         QueryRun R = {rels, queries, n, std::vector<QueryState>(n)};
-        R.folds.swap(folds);
+        R.folds.swap(folds); R.park.swap(park);
         if (const int rc = query_filters(R)) return rc;
-        if (const int rc = query_folds(R)) return rc;     // the fold route's queries: all finished before the levels
+        if (const int rc = query_folds(R, false)) return rc;       // the fold route's queries: all finished before the levels
         // the levels.  (Level 0 also runs when no query has a join: the queries without one sum their views in its apply call.)
         if (g_qb.level.size() < (size_t)(maxl > 1 ? maxl : 1)) g_qb.level.resize((size_t)(maxl > 1 ? maxl : 1));
         for (int l = 0; l < maxl || l == 0; ++l) {
             if (const int rc = query_level_joins(R, l)) return rc;
             if (const int rc = query_level_apply(R, l)) return rc;
             query_take_back(R, l);
+            // the queries whose prefix ends here are parked from the next level on, unless a merged node has too many rows for a
+            // fold's side: such a query stays on the levels to its end
+            for (uint64_t i = 0; i < n && !R.park.empty(); ++i) {
+                if (R.park[i] != l + 1 || !R.st[i].alive) continue;
+                const QueryState &s = R.st[i];
+                bool fits = true;
+                for (int b = 0; b < queries[i].nrels; ++b) fits &= s.node[b] == b || s.rows[s.node[b]] < g_query_fold_node_rows;     // (a binding not its node's name: a merged node)
+                if (fits) continue;
+                R.park[i] = 0; R.folds[i] = 0;
+                if (queries[i].njoins > maxl) {
+                    maxl = queries[i].njoins;
+                    g_query_info.levels = (uint32_t)maxl;
+                    if (g_qb.level.size() < (size_t)maxl) g_qb.level.resize((size_t)maxl);
+                }
+            }
         }
+        if (const int rc = query_folds(R, true)) return rc;        // the nodes' pass over the parked queries still alive
     }
     uint64_t rows = 0;
     for (uint64_t i = 0; i < n; ++i) rows += queries[i].rows;
@@ -3784,7 +3991,11 @@ const rhj_query_batch_foldk_info *rhj_query_batch_last_foldk_info(void) { return
 const rhj_query_batch_fold_self_info *rhj_query_batch_last_fold_self_info(void) { return &g_query_fold_self_info; }
 void rhj_set_query_fold_self(int on) { RhjApiLock api_lock; g_query_fold_self = on != 0; }
 int rhj_query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *plan) { return query_folds_plan(q, nrel, rels, plan); }
+int rhj_query_foldn_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_foldn_plan *plan) { return query_foldn_plan(q, nrel, rels, plan); }
 void rhj_set_query_fold_keys(int on) { RhjApiLock api_lock; g_query_fold_keys = on != 0; }
+void rhj_set_query_fold_nodes(int on) { RhjApiLock api_lock; g_query_fold_nodes = on != 0; }
+void rhj_set_query_fold_node_rows(uint64_t limit) { RhjApiLock api_lock; g_query_fold_node_rows = limit < JSUM_MAX_ROWS ? limit : JSUM_MAX_ROWS; }
+const rhj_query_batch_fold_nodes_info *rhj_query_batch_last_fold_nodes_info(void) { return &g_query_fold_nodes_info; }
 int rhj_query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps) { return query_foldk_plan(q, nrel, rels, root, steps); }
 int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps) { return query_fold_plan(q, nrel, rels, root, steps); }
 
@@ -3795,6 +4006,12 @@ int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 }
 
 int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return table_batch(items, n);
+}
+
+int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
     return table_batch(items, n);

@@ -123,8 +123,10 @@ __device__ __forceinline__ bool foldk_owner_is(const FoldKSide &build, int nkeys
     return same;
 }
 
-// foldk_find: the slot whose owner carries `mine`, or JSUM_NONE when the table has none: at most `slots` steps
-__device__ __forceinline__ uint64_t foldk_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, const FoldKSide &build, int nkeys,
+// foldk_find: the slot whose owner carries `mine`, or JSUM_NONE when the table has none: at most `slots` steps.  (Side: FoldKSide,
+// or rhj_join_foldn_batch.hip.h's side with a row-id vector per word; the table protocol is stated here once for both.)
+template <class Side>
+__device__ __forceinline__ uint64_t foldk_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
                                                const uint64_t (&mine)[RHJ_FOLD_MAX_KEYS])
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
@@ -141,7 +143,8 @@ __device__ __forceinline__ uint64_t foldk_find(jsum_gull table, uint32_t sw, uin
 
 // foldk_claim: the slot of the tuple `mine` of the build side's row at position `pos`, found or claimed, at most `slots` steps (a
 // free slot is always met: at most half are taken); JSUM_NONE only if the table were full
-__device__ __forceinline__ uint64_t foldk_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, const FoldKSide &build, int nkeys,
+template <class Side>
+__device__ __forceinline__ uint64_t foldk_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
                                                 const uint64_t (&mine)[RHJ_FOLD_MAX_KEYS], uint64_t pos)
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
@@ -160,17 +163,18 @@ __device__ __forceinline__ uint64_t foldk_claim(jsum_gull table, uint32_t sw, ui
     return JSUM_NONE;
 }
 
-__global__ __launch_bounds__(256) void k_foldk_claim(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+template <class Desc>
+__device__ __forceinline__ void foldk_claim_tile(const Desc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
-    const JoinFoldKDesc &d = descs[j];
+    const Desc &d = descs[j];
     const uint32_t tile = blockIdx.x - tile_start[j];
     const uint64_t n = d.n[0];
     const uint64_t base = (uint64_t)tile * JSUM_TILE + threadIdx.x;
     const uint32_t log2_slots = d.log2_slots, sw = d.slot_words;
     const jsum_gull table = (jsum_gull)d.table;
     const int nkeys = d.nkeys;
-    const FoldKSide R = foldk_side(d, 0);
+    const auto R = foldk_side(d, 0);
     uint64_t key[RHJ_FOLD_MAX_KEYS][JSUM_ROUNDS];
     foldk_keys(R, nkeys, n, base, key);
 #pragma unroll
@@ -182,10 +186,11 @@ __global__ __launch_bounds__(256) void k_foldk_claim(const JoinFoldKDesc *__rest
     }
 }
 
-__global__ __launch_bounds__(256) void k_foldk_add(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+template <class Desc>
+__device__ __forceinline__ void foldk_add_tile(const Desc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
-    const JoinFoldKDesc &d = descs[j];
+    const Desc &d = descs[j];
     const uint32_t tile = blockIdx.x - tile_start[j];
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t n = d.n[1];
@@ -197,7 +202,7 @@ __global__ __launch_bounds__(256) void k_foldk_add(const JoinFoldKDesc *__restri
     uint64_t slot[JSUM_ROUNDS], pos[JSUM_ROUNDS];
     uint32_t lead[JSUM_ROUNDS];                          // the lane that adds for the wave when the round's slots are one, else 64
     {
-        const FoldKSide S = foldk_side(d, 1), B = foldk_side(d, d.build);
+        const auto S = foldk_side(d, 1), B = foldk_side(d, d.build);
         uint64_t key[RHJ_FOLD_MAX_KEYS][JSUM_ROUNDS];
         foldk_keys(S, nkeys, n, base, key);
 #pragma unroll
@@ -232,11 +237,12 @@ __global__ __launch_bounds__(256) void k_foldk_add(const JoinFoldKDesc *__restri
     }
 }
 
-__global__ __launch_bounds__(256) void k_foldk_apply(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+template <class Desc>
+__device__ __forceinline__ void foldk_apply_tile(const Desc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     __shared__ unsigned long long part[RHJ_FOLD_MAX_OUTS][4];
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
-    const JoinFoldKDesc &d = descs[j];
+    const Desc &d = descs[j];
     const uint32_t tile = blockIdx.x - tile_start[j];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t n = d.n[0];
@@ -246,7 +252,7 @@ __global__ __launch_bounds__(256) void k_foldk_apply(const JoinFoldKDesc *__rest
     const int nouts = d.nouts, nkeys = d.nkeys;
     uint64_t slot[JSUM_ROUNDS], pos[JSUM_ROUNDS];
     {
-        const FoldKSide R = foldk_side(d, 0), B = foldk_side(d, d.build);
+        const auto R = foldk_side(d, 0), B = foldk_side(d, d.build);
         uint64_t key[RHJ_FOLD_MAX_KEYS][JSUM_ROUNDS];
         foldk_keys(R, nkeys, n, base, key);
 #pragma unroll
@@ -286,6 +292,22 @@ __global__ __launch_bounds__(256) void k_foldk_apply(const JoinFoldKDesc *__rest
         const unsigned long long mine = part[o][0] + part[o][1] + part[o][2] + part[o][3];
         if (mine) __hip_atomic_fetch_add(&d.words[o], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// the three launches of a chunk (the bodies above are shared with rhj_join_foldn_batch.hip.h's kernels)
+__global__ __launch_bounds__(256) void k_foldk_claim(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+{
+    foldk_claim_tile(descs, tile_start, ni);
+}
+
+__global__ __launch_bounds__(256) void k_foldk_add(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+{
+    foldk_add_tile(descs, tile_start, ni);
+}
+
+__global__ __launch_bounds__(256) void k_foldk_apply(const JoinFoldKDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
+{
+    foldk_apply_tile(descs, tile_start, ni);
 }
 
 }  // namespace rhj

@@ -49,6 +49,8 @@
 //                          table, then multiplied into per-row u64 weights of the parent side.
 //   rhj_join_foldk_batch.hip.h the same folds on keys of up to four columns: a slot holds the build row that owns it, not a key,
 //                          and equality is decided on that row's words, gathered from the build side's own columns.
+//   rhj_join_foldn_batch.hip.h the tuple-key folds with a row-id vector per key word: the keys of a materialised node, whose
+//                          words belong to different member bindings.
 //   rhj_fold_self_batch.hip.h many folds with no child in one launch: the equalities between two columns of one side as a 0/1
 //                          factor on its weights, and the sums of a query without a join.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
@@ -74,5 +76,6 @@
 #include "rhj_join_sum_batch.hip.h"
 #include "rhj_join_fold_batch.hip.h"
 #include "rhj_join_foldk_batch.hip.h"
+#include "rhj_join_foldn_batch.hip.h"
 #include "rhj_fold_self_batch.hip.h"
 #include "rhj_diag.hip.h"
