@@ -590,6 +590,68 @@ void rhj_set_query_fold_node_rows(uint64_t limit);
 typedef struct rhj_query_batch_fold_nodes_info { uint32_t foldn_calls, foldn_items, node_queries, node_levels; } rhj_query_batch_fold_nodes_info;
 const rhj_query_batch_fold_nodes_info *rhj_query_batch_last_fold_nodes_info(void);
 
+/* rhj_fold_self_batch_device with CONSTANT predicates in the mask (csrc/rhj_fold_pred_batch.hip.h): a filter as a 0/1 factor on a
+ * side's weights, with no hit list.  One item is ONE side of n rows, nconst comparisons, neq equalities and nouts
+ * outputs, each a factor P (rhj_fold_factor) over the side's positions:
+ *     m(i)     = AND over c of [ d_col_c[d_sel_c ? d_sel_c[i] : i]  op_c  value_c ]  AND  over t of [ A_t == B_t ]     (no term: 1)
+ *     d_out[i] = m(i) * P(i)       for i < n, when d_out is given; a masked row stores 0 (written, not left)
+ *     total    = sum over i of m(i) * P(i)
+ * everything exact modulo 2^64.  op is '<', '>' or '=' and the comparison is UNSIGNED, value already converted, as
+ * rhj_filter_device's; the equalities are rhj_fold_self_desc's terms.  With nconst 0 an item gives rhj_fold_self_batch_device's
+ * outputs bit for bit; with one output {ones} its total is rhj_filter_batch_device's hits on the same terms.
+ *
+ * Every item with rows runs in the ONE launch of its chunk (path 17) over 2048-row tiles: one upload, one launch, one copy of the
+ * accumulator words and one stream synchronisation per chunk of at most 4096 items and 2^24 tiles, in call order.  There is no
+ * table and no memset.  Pointers, sharing, overlap, d_out[n] and empty items are as there: an item with n == 0 has rc 0, every
+ * total 0 and path 0, its d_outs are untouched and it launches nothing; a batch of 0 items returns 0 without touching a device.
+ *
+ * The whole batch is validated before anything is launched: an op outside '<', '>', '=', nconst outside
+ * 0..RHJ_FILTER_MAX_TERMS, neq outside 0..RHJ_FOLD_SELF_MAX_TERMS, nouts outside 0..RHJ_FOLD_MAX_OUTS, a NULL column in a term of
+ * an item with rows, or n of 2^32 or more give that item rc -3; then nothing runs, no total is written and the call returns -3.
+ * Otherwise 0, or a negative value on a HIP error.  rhj_last_stats() afterwards: n_r the rows summed over the items, units the
+ * items launched, ms_total the whole call (timing level >= 1), reserved 17. */
+typedef struct rhj_fold_const_term {
+    const uint64_t *d_col, *d_sel;     /* sel NULL: q = p */
+    char            op;                /* '<', '>' or '=' */
+    uint64_t        value;
+} rhj_fold_const_term;
+typedef struct rhj_fold_pred_desc {
+    uint64_t            n;
+    int                 nconst, neq, nouts;   /* 0 .. RHJ_FILTER_MAX_TERMS, 0 .. RHJ_FOLD_SELF_MAX_TERMS, 0 .. RHJ_FOLD_MAX_OUTS */
+    rhj_fold_const_term consts[RHJ_FILTER_MAX_TERMS];
+    rhj_fold_eq_term    eqs[RHJ_FOLD_SELF_MAX_TERMS];
+    rhj_fold_self_out   outs[RHJ_FOLD_MAX_OUTS];
+    int rc;                  /* out */
+    int path;                /* out: 17, or 0 when nothing was launched */
+} rhj_fold_pred_desc;
+int rhj_fold_pred_batch_device(rhj_fold_pred_desc *items, uint64_t n);
+
+/* rhj_query_batch_device with this switch on as well as rhj_set_query_fold (default off; environment RHJ_QUERY_FOLD_ONE_WAIT=1; no
+ * effect while the fold route is off): a FOLD PROGRAM with one wait.  A query takes this route when, under the
+ * fold, keys and self switches as they stand, rhj_query_fold_plan, rhj_query_foldk_plan or rhj_query_folds_plan lets it fold (a
+ * query that hands over from levels, rhj_set_query_fold_nodes's, does not) and every binding's relation has between 1 row and
+ * rhj_set_query_fold_one_wait_rows's limit (default 4096: the largest size at which the route measured no slower on filtered chains; `small` needs 65 536 and gains with it).  rhj_query_one_wait_plan says so of one query: 1 it takes the route,
+ * 0 it is valid and does not, -3 as rhj_query_levels; a pure function that needs no device (rels may not be NULL for a 1: the
+ * rule reads the rows; with rels NULL it gives 0 or -3).
+ *
+ * For such a query no filter item is issued: a binding's side is its WHOLE relation (no row-id vector), and its filters and kept
+ * one-binding predicates are ONE rhj_fold_pred_desc item whose output {ones} is the binding's first weight vector; a query with
+ * no join is one such item with its views as outputs.  Every size of every round is then known before the device is touched, so
+ * the route's queries, in call order, are one program: one upload of every descriptor, tile start and zeroed accumulator word,
+ * one k_fold_pred launch, per round one memset of that round's tables and the fold batches' unchanged launches on one key and on
+ * tuple keys, one copy of all words back and ONE stream synchronisation.  A program is cut only where a batch's chunk would be:
+ * 4096 items a round and kind (and pred items), 2^24 tiles a launch, 1 GiB of tables a round.  The answers follow the fold
+ * route's rule, so the two agree bit for bit, the 2^64 limit included: a query is empty (rows 0, sums 0) when a pred item's
+ * weight total or a step's first total is 0; else rows and sums are the last step's totals, or the join-less item's.  There is
+ * no early exit: zero weights propagate.  The other queries run exactly as with the switch off, after the programs, and every
+ * other info struct counts them alone.  rhj_query_batch_last_one_wait_info(): the route's queries, the programs, their items by
+ * kind, the rounds, kernel launches, memsets and stream synchronisations summed over the programs (all zero with the switch off). */
+void rhj_set_query_fold_one_wait(int on);
+void rhj_set_query_fold_one_wait_rows(uint64_t limit);
+int rhj_query_one_wait_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels);
+typedef struct rhj_query_batch_one_wait_info { uint32_t queries, programs, pred_items, fold_items, foldk_items, rounds, launches, memsets, waits; } rhj_query_batch_one_wait_info;
+const rhj_query_batch_one_wait_info *rhj_query_batch_last_one_wait_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

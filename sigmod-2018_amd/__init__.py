@@ -46,6 +46,7 @@ INTER_SYMBOLS = [
     "rhj_join_foldk_batch_device", "rhj_query_foldk_plan", "rhj_set_query_fold_keys", "rhj_query_batch_last_foldk_info",
     "rhj_fold_self_batch_device", "rhj_query_folds_plan", "rhj_set_query_fold_self", "rhj_query_batch_last_fold_self_info",
     "rhj_join_foldn_batch_device", "rhj_query_foldn_plan", "rhj_set_query_fold_nodes", "rhj_set_query_fold_node_rows", "rhj_query_batch_last_fold_nodes_info",
+    "rhj_fold_pred_batch_device", "rhj_query_one_wait_plan", "rhj_set_query_fold_one_wait", "rhj_set_query_fold_one_wait_rows", "rhj_query_batch_last_one_wait_info",
 ]
 
 
@@ -331,6 +332,42 @@ class QueryBatchFoldNodesInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FILTER_MAX_TERMS = 4                     # RHJ_FILTER_MAX_TERMS
+
+
+class FoldConstTerm(C.Structure):
+    """rhj_fold_const_term (include/rhj_inter.h): col[sel ? sel[i] : i] op value, compared unsigned"""
+    _fields_ = [("d_col", C.c_void_p), ("d_sel", C.c_void_p), ("op", C.c_char), ("value", C.c_uint64)]
+
+
+class FoldPredDesc(C.Structure):
+    """rhj_fold_pred_desc (include/rhj_inter.h): one item of rhj_fold_pred_batch_device"""
+    _fields_ = [("n", C.c_uint64), ("nconst", C.c_int), ("neq", C.c_int), ("nouts", C.c_int),
+                ("consts", FoldConstTerm * FILTER_MAX_TERMS), ("eqs", FoldEqTerm * FOLD_SELF_MAX_TERMS),
+                ("outs", FoldSelfOut * FOLD_MAX_OUTS), ("rc", C.c_int), ("path", C.c_int)]
+
+
+class QueryBatchOneWaitInfo(C.Structure):
+    """rhj_query_batch_one_wait_info (include/rhj_inter.h): the queries the last rhj_query_batch_device ran as fold programs with
+    one wait each, the programs, their items by kind, their rounds, launches, memsets and waits"""
+    _fields_ = [(n, C.c_uint32) for n in ("queries", "programs", "pred_items", "fold_items", "foldk_items", "rounds", "launches", "memsets", "waits")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def query_one_wait_plan(lib, query, rels=None, nrel=None):
+    """rhj_query_one_wait_plan on one query (relations, joins, filters, views): 1 when it takes the one-wait route under the
+    switches and the row limit as they stand, 0 when it does not; ValueError on -3.  rels: a DeviceRelation array (the rule reads
+    the relations' rows), or None."""
+    arr, keep = query_descs([query])
+    rc = lib.rhj_query_one_wait_plan(C.byref(arr[0]), nrel if nrel is not None else max(query[0]) + 1, rels)
+    del keep
+    if rc == -3:
+        raise ValueError("rhj_query_one_wait_plan refused the query")
+    return rc
+
+
 def query_foldn_plan(lib, query, nrel=None):
     """rhj_query_foldn_plan on one query (relations, joins, filters, views): (levels, [node of every binding], root,
     [(child, parent, round, [predicate indices])], [indices of the kept predicates inside a node]); ValueError on -3"""
@@ -370,6 +407,7 @@ class QueryInfo(dict):
     foldk_info = None
     fold_self_info = None
     fold_nodes_info = None
+    one_wait_info = None
 
 
 def query_descs(queries):
@@ -397,7 +435,7 @@ class Stats(C.Structure):
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         r = self.reserved                  # path of the last join (include/rhj.h)
-        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch", 15: "fold_self_batch", 16: "join_foldn_batch"}.get(r & 0xff, "?")
+        d["path"] = {0: "tiled", 1: "fused", 3: "small", 4: "lowradix", 5: "subbucket", 6: "batch", 7: "filter_batch", 8: "apply_batch", 9: "eq2_batch", 10: "query_batch", 11: "stats_batch", 12: "join_sum_batch", 13: "join_fold_batch", 14: "join_foldk_batch", 15: "fold_self_batch", 16: "join_foldn_batch", 17: "fold_pred_batch"}.get(r & 0xff, "?")
         d["sub_bits"], d["pass1_bits"] = (r >> 8) & 0xff, (r >> 16) & 0xff
         return d
 
@@ -529,6 +567,14 @@ def load_library(path=None):
         L.rhj_set_query_fold_node_rows.argtypes = [C.c_uint64]
         L.rhj_set_query_fold_node_rows.restype = None
         L.rhj_query_batch_last_fold_nodes_info.restype = C.POINTER(QueryBatchFoldNodesInfo)
+    if hasattr(L, "rhj_fold_pred_batch_device"):      # (A/B runs load earlier builds through this module too)
+        L.rhj_fold_pred_batch_device.argtypes = [C.POINTER(FoldPredDesc), C.c_uint64]
+        L.rhj_query_one_wait_plan.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation)]
+        L.rhj_set_query_fold_one_wait.argtypes = [C.c_int]
+        L.rhj_set_query_fold_one_wait.restype = None
+        L.rhj_set_query_fold_one_wait_rows.argtypes = [C.c_uint64]
+        L.rhj_set_query_fold_one_wait_rows.restype = None
+        L.rhj_query_batch_last_one_wait_info.restype = C.POINTER(QueryBatchOneWaitInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -923,6 +969,59 @@ class RHJ:
             res.append([(None if a is None else buf[a:a + d.n] if isinstance(a, int) else a[:d.n], d.outs[k].total) for k, a in enumerate(mine)])
         return (res, [arr[i].path for i in range(n)]) if with_info else res
 
+    def fold_pred_batch_device(self, items, with_info=False):
+        """fold_self_batch_device with constant predicates (rhj_fold_pred_batch_device, include/rhj_inter.h): items =
+        [(n, consts, eqs, outs), ...] with consts = [(col, sel, op, value), ...] (0..4 comparisons col[sel[i]] op value, op one of
+        "<", ">", "=", compared unsigned, sel a vector or None), eqs and outs as fold_self_batch_device's terms and outs.  Returns
+        per item a list of (vector or None, total).  with_info: also the list of the items' path ids (17: the batched launch, 0:
+        an item without rows, whose vectors are left as they were)."""
+        torch = self.torch
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        n = len(items)
+        arr = (FoldPredDesc * max(n, 1))()
+        places, at = [], 0
+        for d, (rows, consts, eqs, outs) in zip(arr, items):
+            if len(consts) > FILTER_MAX_TERMS or len(eqs) > FOLD_SELF_MAX_TERMS or len(outs) > FOLD_MAX_OUTS:
+                raise ValueError("an item has 0..%d constant terms, 0..%d equalities and 0..%d outputs, not %d, %d and %d"
+                                 % (FILTER_MAX_TERMS, FOLD_SELF_MAX_TERMS, FOLD_MAX_OUTS, len(consts), len(eqs), len(outs)))
+            d.n, d.nconst, d.neq, d.nouts = int(rows), len(consts), len(eqs), len(outs)
+            for t, (col, sel, op, value) in zip(d.consts, consts):
+                t.d_col, t.d_sel, t.op, t.value = ptr(col), ptr(sel), op.encode(), int(value) & ((1 << 64) - 1)
+            for t, (colA, selA, colB, selB) in zip(d.eqs, eqs):
+                t.d_colA, t.d_selA, t.d_colB, t.d_selB = ptr(colA), ptr(selA), ptr(colB), ptr(selB)
+            mine = []
+            for o, ((w, src, col), out) in zip(d.outs, outs):
+                o.p.d_w, o.p.d_src, o.p.d_col = ptr(w), ptr(src), ptr(col)
+                if out is True:
+                    mine.append(at)
+                    at += (d.n + 1) // 2 * 2                     # 16-byte aligned pieces
+                else:
+                    if out is not None and out.numel() < d.n:
+                        raise ValueError("an output vector of %d words for %d rows" % (out.numel(), d.n))
+                    mine.append(out)
+            places.append(mine)
+        buf = torch.zeros(max(at, 1), dtype=torch.int64, device=self.dev)
+        for d, mine in zip(arr, places):
+            for o, a in zip(d.outs, mine):
+                o.d_out = None if a is None else buf.data_ptr() + 8 * a if isinstance(a, int) else a.data_ptr()
+        rc = self.lib.rhj_fold_pred_batch_device(arr, n)
+        if rc < 0:
+            raise RuntimeError("rhj_fold_pred_batch_device failed (%d)" % rc)
+        res = []
+        for d, mine in zip(arr, places):
+            res.append([(None if a is None else buf[a:a + d.n] if isinstance(a, int) else a[:d.n], d.outs[k].total) for k, a in enumerate(mine)])
+        return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def set_query_fold_one_wait(self, on):
+        """with set_query_fold: the folding queries whose relations all have 1..set_query_fold_one_wait_rows' limit of rows run
+        as fold programs: filters as 0/1 weights over whole relations, every round's launches queued behind one upload, and one
+        wait a program (default off)"""
+        self.lib.rhj_set_query_fold_one_wait(1 if on else 0)
+
+    def set_query_fold_one_wait_rows(self, limit):
+        """a query takes the one-wait route only while every binding's relation has at most this many rows (default 4096)"""
+        self.lib.rhj_set_query_fold_one_wait_rows(int(limit))
+
     def set_query_fold_self(self, on):
         """with set_query_fold: the queries that fold once their one-binding predicates are 0/1 factors on a binding's weight and
         their implied predicates are dropped fold too, queries without a join among them (default off)"""
@@ -1048,6 +1147,8 @@ class RHJ:
         info.foldk_info = self.lib.rhj_query_batch_last_foldk_info().contents.as_dict()
         info.fold_self_info = self.lib.rhj_query_batch_last_fold_self_info().contents.as_dict()
         info.fold_nodes_info = self.lib.rhj_query_batch_last_fold_nodes_info().contents.as_dict()
+        if hasattr(self.lib, "rhj_query_batch_last_one_wait_info"):
+            info.one_wait_info = self.lib.rhj_query_batch_last_one_wait_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

@@ -171,6 +171,8 @@ int g_query_fold_keys = 0;           // 1: with g_query_fold, the queries whose 
 int g_query_fold_self = 0;           // 1: with g_query_fold, the queries that fold once one-binding and implied predicates are taken care of fold too, after one rhj_fold_self_batch_device call (rhj_set_query_fold_self, env RHJ_QUERY_FOLD_SELF)
 int g_query_fold_nodes = 0;          // 1: with the three fold switches above all on, a query none of them takes runs by levels only until its merged nodes and remaining predicates are a tree, and folds over the nodes from there (rhj_set_query_fold_nodes, env RHJ_QUERY_FOLD_NODES)
 uint64_t g_query_fold_node_rows = 1ull << 32;            // a query hands over only while every merged node has fewer rows than this (rhj_set_query_fold_node_rows; a fold's sides are below 2^32 rows)
+int g_query_fold_one_wait = 0;       // 1: with g_query_fold, the folding queries over relations of 1..g_query_fold_one_wait_rows rows run as fold programs with one wait each, their filters 0/1 weights (rhj_set_query_fold_one_wait, env RHJ_QUERY_FOLD_ONE_WAIT)
+uint64_t g_query_fold_one_wait_rows = 4096;              // the most rows of a relation on that route (rhj_set_query_fold_one_wait_rows): the largest size at which whole relations under weights measured no slower than hit lists
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -205,6 +207,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_FOLD_KEYS"))) g_query_fold_keys = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_SELF"))) g_query_fold_self = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_NODES"))) g_query_fold_nodes = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_FOLD_ONE_WAIT"))) g_query_fold_one_wait = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -1369,7 +1372,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16, PATH_BATCH_FOLD_PRED = 17 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2523,6 +2526,92 @@ static int fold_self_batch(rhj_fold_self_desc *items, uint64_t n)
     return batch_close(timed, st);
 }
 
+// ---- batched folds with no child and constant predicates (rhj_fold_pred_batch.hip.h) ---------------------------------------------
+// rhj_fold_pred_batch_device (path 17): fold_self_batch's frame, limits and block over rhj_fold_pred_desc.  fpred_fill is also
+// what a fold program (query_one_wait below) fills its pred descriptors with.
+static bool fpred_valid(const rhj_fold_pred_desc &q)
+{
+    if (q.nconst < 0 || q.nconst > RHJ_FILTER_MAX_TERMS || q.neq < 0 || q.neq > RHJ_FOLD_SELF_MAX_TERMS || q.nouts < 0 || q.nouts > RHJ_FOLD_MAX_OUTS || q.n >= JSUM_MAX_ROWS) return false;
+    for (int c = 0; c < q.nconst; ++c)
+        if (op_code(q.consts[c].op) < 0 || (q.n && !q.consts[c].d_col)) return false;
+    for (int t = 0; t < q.neq; ++t)
+        if (q.n && (!q.eqs[t].d_colA || !q.eqs[t].d_colB)) return false;
+    return true;
+}
+
+static void fpred_fill(const rhj_fold_pred_desc &q, unsigned long long *words, FoldPredDesc &d)
+{
+    memset((void *)&d, 0, sizeof(d));
+    d.n = q.n; d.words = words; d.nconst = q.nconst; d.neq = q.neq; d.nouts = q.nouts;
+    for (int c = 0; c < q.nconst; ++c) {
+        d.c[c].col = q.consts[c].d_col; d.c[c].sel = q.consts[c].d_sel;
+        d.c[c].value = q.consts[c].value; d.c[c].op = op_code(q.consts[c].op);
+    }
+    for (int t = 0; t < q.neq; ++t) {
+        d.t[t].col[0] = q.eqs[t].d_colA; d.t[t].sel[0] = q.eqs[t].d_selA;
+        d.t[t].col[1] = q.eqs[t].d_colB; d.t[t].sel[1] = q.eqs[t].d_selB;
+    }
+    for (int o = 0; o < q.nouts; ++o) {
+        d.o[o].p = FoldFactor{q.outs[o].p.d_w, q.outs[o].p.d_src, q.outs[o].p.d_col};
+        d.o[o].out = q.outs[o].d_out;
+    }
+}
+
+// One chunk: items[which[lo, hi)], every one valid and of at least one row.
+static int fpred_chunk(rhj_fold_pred_desc *items, const std::vector<uint64_t> &which, size_t lo, size_t hi)
+{
+    constexpr size_t WORDS = FOLD_PRED_WORDS;
+    static_assert(sizeof(FoldPredDesc) % 8 == 0, "the words' padding is that of the tile starts alone");
+    const size_t ni = hi - lo;
+    Block blk;
+    unsigned long long *back, *words, *d_words; FoldPredDesc *hd, *dd; uint32_t *tile_start, *d_tile_start;
+    if (batch_block(blk, [&](Block &b) { b.back(back, ni * WORDS); b.up(hd, dd, ni); b.up(tile_start, d_tile_start, ni + 1); b.up(words, d_words, ni * WORDS); })) return -1;
+    memset(words, 0, ni * WORDS * 8);
+    uint32_t tiles = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        const rhj_fold_pred_desc &q = items[which[lo + k]];
+        FoldPredDesc d;
+        fpred_fill(q, d_words + k * WORDS, d);
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        tile_start[k] = tiles;
+        tiles += (uint32_t)jsum_tiles(q.n);
+    }
+    tile_start[ni] = tiles;
+    if (batch_upload(blk, hd, blk.host_end())) return -1;
+    RHJ_LAUNCH(k_fold_pred, dim3(tiles), dim3(256), 0, g.stream, dd, d_tile_start, (uint32_t)ni);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, d_words, ni * WORDS * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < ni; ++k) {
+        rhj_fold_pred_desc &q = items[which[lo + k]];
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = back[k * WORDS + (size_t)o];
+        q.path = PATH_BATCH_FOLD_PRED;
+    }
+    return 0;
+}
+
+static int fold_pred_batch(rhj_fold_pred_desc *items, uint64_t n)
+{
+    if (n == 0) return 0;
+    bool timed = false;
+    const auto reset = [](rhj_fold_pred_desc &q) { q.rc = 0; q.path = 0; return fpred_valid(q); };      // (no total is written in a batch that is refused)
+    if (const int rc = batch_open(items, n, reset, timed)) return rc;
+    std::vector<uint64_t> which;
+    rhj_stats st = {};
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_fold_pred_desc &q = items[i];
+        for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0;
+        st.n_r += q.n;
+        if (q.n) which.push_back(i);                      // an empty item: nothing to launch, no d_out touched
+    }
+    const auto tiles = [&](size_t k, uint64_t t) { return t + jsum_tiles(items[which[k]].n); };   // (one item never has more than the limit: fpred_valid)
+    if (batch_cut(which.size(), FSELF_MAX_ITEMS, FSELF_MAX_TILES, tiles,
+                  [&](size_t lo, size_t hi, uint64_t) { return fpred_chunk(items, which, lo, hi); })) return -1;
+    st.units = which.size();
+    st.reserved = PATH_BATCH_FOLD_PRED;
+    return batch_close(timed, st);
+}
+
 // ---- a batch of queries, level by level (include/rhj_inter.h) ------------------------------------------------------------------
 // rhj_query_batch_device drives the four batches above: one filter batch, then per join level at most one batch of two-column
 // equalities, at most two batches of joins on columns (the second for the joins whose fan-out passed max(nR, nS)) and one
@@ -2533,16 +2622,17 @@ static int fold_self_batch(rhj_fold_self_desc *items, uint64_t n)
 //   g_qb.level[l]   the vectors level l rebuilds: read by any later level, so every level has its own
 //   g_qb.fold[r]    the weight and view vectors fold round r writes: read by any later round, so every round has its own
 //   g_qb.self       the first weight vectors, written by the fold route's one rhj_fold_self_batch_device call: read by any round
+//   g_qb.prog       every weight and view vector of one fold program (the one-wait route): a piece each, none reused inside it
 // They belong to the library's own context (the entry point runs on no other), grow and stay, and go with rhj_release().
 struct QueryWorkspace {
-    Buf              filt, idx, idx2, self;
+    Buf              filt, idx, idx2, self, prog;
     std::vector<Buf> level, fold;
     hipEvent_t       ev[2] = {};     // the whole call (its inner batches run untimed); created by the first timed call
 } g_qb;
 
 static void query_release()
 {
-    for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2, &g_qb.self}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
+    for (Buf *b : {&g_qb.filt, &g_qb.idx, &g_qb.idx2, &g_qb.self, &g_qb.prog}) { if (b->p) (void)hipFree(b->p); *b = Buf{}; }
     for (Buf &b : g_qb.level) if (b.p) (void)hipFree(b.p);
     g_qb.level.clear();
     for (Buf &b : g_qb.fold) if (b.p) (void)hipFree(b.p);
@@ -2621,6 +2711,7 @@ rhj_query_batch_fold_info g_query_fold_info = {};
 rhj_query_batch_foldk_info g_query_foldk_info = {};
 rhj_query_batch_fold_self_info g_query_fold_self_info = {};
 rhj_query_batch_fold_nodes_info g_query_fold_nodes_info = {};
+rhj_query_batch_one_wait_info g_query_one_wait_info = {};
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
@@ -2628,6 +2719,7 @@ struct QueryRun {                                         // what the stages of 
     uint64_t                        n;
     std::vector<QueryState>         st;
     std::vector<char>               folds;                // a query that takes the fold route (empty: none does): 1, 2 when only rhj_set_query_fold_keys lets it, 3 when only rhj_set_query_fold_self does, 4 when it hands over from levels to folds over its nodes (rhj_set_query_fold_nodes)
+    std::vector<char>               one_wait;             // a query that ran in a fold program with one wait (empty: none did): it is finished before the filters, and no stage below sees it
     std::vector<int>                park;                 // of a query with folds 4: the levels it runs before it is parked for the nodes' pass (empty: no such query)
     std::vector<uint64_t>           active, awho;         // of the level at hand: the queries that take part; an apply item's query
     std::vector<int>                kind;                 // of an active query's predicate: 0 a join, 1 an equality, 2 none (level 0 of a query without joins), 3 a last join taken as its sums ...
@@ -2650,7 +2742,7 @@ static int query_filters(QueryRun &R)
     for (uint64_t i = 0; i < R.n; ++i) {
         const rhj_query_desc &q = R.queries[i];
         QueryState &s = R.st[i];
-        s.alive = true;
+        s.alive = R.one_wait.empty() || !R.one_wait[i];   // (a query of a fold program has its answer already)
         for (int b = 0; b < q.nrels; ++b) {
             s.vec[b] = nullptr; s.node[b] = b; s.rows[b] = R.rels[q.rels[b]].num_tuples;
             if (s.rows[b] == 0) s.alive = false;          // an empty relation: every result it takes part in is empty
@@ -3347,6 +3439,361 @@ static int query_folds(QueryRun &R, bool nodes_pass)
     return 0;
 }
 
+// ---- the fold program with one wait (include/rhj_inter.h) ----------------------------------------------------------
+// A query whose bindings stay whole relations, their filters 0/1 weights (rhj_fold_pred_batch.hip.h), has every size of every round
+// known on the host.  The route's queries, in call order, are laid out as programs: ow_build states one query's pred items and
+// steps, ow_fits says whether a program still takes them within the batches' chunk limits, ow_run issues a program: one upload,
+// k_fold_pred, per round a memset and the fold batches' own launches, one copy back and one wait.  A weight or view vector is a
+// piece of ONE buffer a program (g_qb.prog), never reused inside it; until the buffer has its size a descriptor names such a vector
+// by its offset (ow_ref), and ow_run turns the offsets into addresses.
+// which plan lets a valid query of lv levels fold under the switches as they stand: 1 rhj_query_fold_plan, 2 rhj_query_foldk_plan,
+// 3 rhj_query_folds_plan, 0 none
+static int query_fold_how(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int lv)
+{
+    return !(g_query_fold && lv >= 0) ? 0 : lv > 0 && query_fold_plan(q, nrel, rels, nullptr, nullptr) > 0 ? 1 :
+           lv > 0 && g_query_fold_keys && query_foldk_plan(q, nrel, rels, nullptr, nullptr) > 0 ? 2 :
+           g_query_fold_self && query_folds_self(q, nrel, rels) ? 3 : 0;
+}
+
+static int query_one_wait_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels)
+{
+    if (!q) return -3;
+    const int lv = query_levels(q, nrel, rels, nullptr);
+    if (lv < 0) return -3;
+    if (!rels || !query_fold_how(q, nrel, rels, lv)) return 0;
+    for (int b = 0; b < q->nrels; ++b) {
+        const uint64_t rows = rels[q->rels[b]].num_tuples;
+        if (rows < 1 || rows > g_query_fold_one_wait_rows) return 0;
+    }
+    return 1;
+}
+
+constexpr uintptr_t OW_REF = 16;                          // an offset's bias: no vector is the null pointer
+static inline uint64_t *ow_ref(size_t off) { return (uint64_t *)(uintptr_t)(off + OW_REF); }
+static inline void ow_fix(const uint64_t *&p, uintptr_t base) { if (p) p = (const uint64_t *)(base + ((uintptr_t)p - OW_REF)); }
+static inline void ow_fix(uint64_t *&p, uintptr_t base) { if (p) p = (uint64_t *)(base + ((uintptr_t)p - OW_REF)); }
+
+struct OwStep {                                           // one fold of a program, in the order built
+    size_t who;                                           // its query, by its place in the program
+    int    round, kind;                                   // kind 0: rounds[round].fd[at], 1: .kd[at]
+    size_t at;
+    bool   last;                                          // the root's last fold: its totals are rows and sums
+    std::array<int, RHJ_FOLD_MAX_OUTS> view;              // the view an output belongs to, -1 the weight
+};
+struct OwRound {
+    std::vector<rhj_join_fold_desc>  fd;
+    std::vector<rhj_join_foldk_desc> kd;
+    uint64_t tiles[2] = {0, 0}, bytes = 0;                // both sides' tiles by kind; the round's tables
+};
+struct OwProgram {
+    std::vector<uint64_t>           who;                  // the queries
+    std::vector<rhj_fold_pred_desc> pd;
+    std::vector<size_t>             pwho;                 // a pred item's query, by its place in who
+    std::vector<char>               pfinal;               // a pred item that is its whole query: totals are rows and sums
+    uint64_t                        ptiles = 0;
+    std::vector<OwRound>            rounds;
+    std::vector<OwStep>             steps;
+    size_t                          vec_at = 0;           // bytes of vectors handed out
+};
+
+// Query i alone as a program whose vectors begin at offset vec_at.
+static int ow_build(const QueryRun &R, uint64_t i, size_t vec_at, OwProgram &P)
+{
+    const rhj_query_desc &q = R.queries[i];
+    P = OwProgram();
+    P.who.push_back(i);
+    P.vec_at = vec_at;
+    FoldQuery f = {};
+    f.i = i;
+    if (R.folds[i] == 3) {
+        rhj_folds_plan plan;
+        if (query_folds_plan(&q, INT_MAX, nullptr, &plan) != 1) { fprintf(stderr, "rhj: a query on the one-wait route has no fold plan\n"); return -1; }
+        f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
+        memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
+    } else {
+        f.nsteps = query_foldk_plan(&q, INT_MAX, nullptr, &f.root, f.steps);
+        if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the one-wait route has no fold plan\n"); return -1; }
+    }
+    const auto rows = [&](int b) { return R.rels[q.rels[b]].num_tuples; };
+    const auto take = [&](uint64_t n) { uint64_t *p = ow_ref(P.vec_at); P.vec_at += (size_t)((n + 1) / 2 * 2) * 8; return p; };
+    // the pred items: a binding's filters and kept one-binding predicates as its first weight vector
+    for (int b = 0; b < q.nrels; ++b) {
+        rhj_fold_pred_desc d = {};
+        for (int k = 0; k < q.nfilters; ++k) {
+            const rhj_query_filter &p = q.filters[k];
+            if (p.rel != b) continue;
+            rhj_fold_const_term &t = d.consts[d.nconst++];
+            t.d_col = R.column(q, b, p.col); t.op = p.op; t.value = p.value;
+        }
+        for (int t = 0; t < f.nself; ++t) {
+            const rhj_query_join &p = q.joins[f.self[t]];
+            if (p.relA != b) continue;
+            d.eqs[d.neq++] = rhj_fold_eq_term{R.column(q, b, p.colA), nullptr, R.column(q, b, p.colB), nullptr};
+        }
+        if (d.nconst + d.neq == 0 && f.nsteps > 0) continue;       // no predicate of its own: the weight stays ones
+        d.n = rows(b);
+        d.nouts = 1;                                      // output 0: ones, so its total is the rows that pass
+        if (f.nsteps == 0) {                              // the whole query is this binding: the views' sums, nothing written
+            for (int v = 0; v < q.nviews; ++v) d.outs[d.nouts++].p = rhj_fold_factor{nullptr, nullptr, R.column(q, q.views[v].rel, q.views[v].col)};
+        } else {
+            d.outs[0].d_out = take(d.n);
+            f.w[b] = d.outs[0].d_out;
+        }
+        P.pd.push_back(d); P.pwho.push_back(0); P.pfinal.push_back(f.nsteps == 0);
+        P.ptiles += jsum_tiles(d.n);
+    }
+    // the steps: query_folds's items, every side a whole relation
+    for (int k = 0; k < f.nsteps; ++k) {
+        const rhj_foldk_step &step = f.steps[k];
+        const int S = step.child, Pn = step.parent;
+        const bool last = k == f.nsteps - 1;
+        if (P.rounds.size() <= (size_t)step.round) P.rounds.resize((size_t)step.round + 1);
+        OwRound &rd = P.rounds[(size_t)step.round];
+        rhj_join_fold_desc d = {};
+        OwStep os = {};
+        os.who = 0; os.round = step.round; os.last = last;
+        const uint64_t *keyR[RHJ_FOLD_MAX_KEYS] = {}, *keyS[RHJ_FOLD_MAX_KEYS] = {};
+        for (int t = 0; t < step.nkeys; ++t) {
+            const rhj_query_join &p = q.joins[step.joins[t]];
+            const bool a_is_parent = p.relA == Pn;
+            keyR[t] = R.column(q, Pn, a_is_parent ? p.colA : p.colB);
+            keyS[t] = R.column(q, S, a_is_parent ? p.colB : p.colA);
+        }
+        d.d_colR = keyR[0]; d.d_colS = keyS[0];
+        d.nR = rows(Pn); d.nS = rows(S);
+        int value_of[RHJ_QUERY_MAX_VIEWS];
+        d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
+        for (int v = 0; v < q.nviews; ++v) {
+            value_of[v] = -1;
+            if (q.views[v].rel == S) d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, R.column(q, S, q.views[v].col)};
+            else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
+        }
+        const auto out = [&](int value, rhj_fold_factor p, int v) {
+            os.view[(size_t)d.nouts] = v;
+            rhj_fold_out &o = d.outs[d.nouts++];
+            o.value = value; o.p = p;
+            if (!last) o.d_out = take(d.nR);
+        };
+        out(0, rhj_fold_factor{f.w[Pn], nullptr, nullptr}, -1);                        // the parent's new weight
+        for (int v = 0; v < q.nviews; ++v) {
+            if (value_of[v] >= 0)                    out(value_of[v], rhj_fold_factor{f.w[Pn], nullptr, nullptr}, v);     // a view coming from the child
+            else if (f.acc[Pn][v])                   out(0, rhj_fold_factor{f.acc[Pn][v], nullptr, nullptr}, v);          // a view the parent carried
+            else if (last && q.views[v].rel == Pn)   out(0, rhj_fold_factor{f.w[Pn], nullptr, R.column(q, Pn, q.views[v].col)}, v);   // a view on the root: lazy until now
+        }
+        if (!last) {                                      // (a round's steps of one query share no node: what a step leaves is read by later rounds only)
+            f.w[Pn] = d.outs[0].d_out;
+            for (int o = 1; o < d.nouts; ++o) f.acc[Pn][os.view[(size_t)o]] = d.outs[o].d_out;
+        }
+        rd.tiles[step.nkeys > 1] += jsum_tiles(d.nR) + jsum_tiles(d.nS);
+        if (step.nkeys == 1) {
+            os.kind = 0; os.at = rd.fd.size();
+            rd.bytes += tbatch_table_bytes(d);
+            rd.fd.push_back(d);
+        } else {
+            rhj_join_foldk_desc t = {};
+            t.nkeys = step.nkeys;
+            for (int w = 0; w < step.nkeys; ++w) { t.d_colR[w] = keyR[w]; t.d_colS[w] = keyS[w]; }
+            t.nR = d.nR; t.nS = d.nS;
+            t.nvalues = d.nvalues; t.nouts = d.nouts;
+            memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
+            os.kind = 1; os.at = rd.kd.size();
+            rd.bytes += tbatch_table_bytes(t);
+            rd.kd.push_back(t);
+        }
+        P.steps.push_back(os);
+    }
+    return 0;
+}
+
+// whether program P stays within a chunk's limits once `one` has joined it: items a round and kind, tiles a launch, tables a round
+static bool ow_fits(const OwProgram &P, const OwProgram &one)
+{
+    if (P.pd.size() + one.pd.size() > FSELF_MAX_ITEMS || P.ptiles + one.ptiles > FSELF_MAX_TILES) return false;
+    for (size_t r = 0; r < one.rounds.size() && r < P.rounds.size(); ++r) {
+        const OwRound &a = P.rounds[r], &b = one.rounds[r];
+        if (a.fd.size() + b.fd.size() > JSUM_MAX_ITEMS || a.kd.size() + b.kd.size() > JSUM_MAX_ITEMS) return false;
+        if (a.tiles[0] + b.tiles[0] > JSUM_MAX_TILES || a.tiles[1] + b.tiles[1] > JSUM_MAX_TILES || a.bytes + b.bytes > JSUM_ARENA_BYTES) return false;
+    }
+    return true;
+}
+
+static void ow_merge(OwProgram &P, const OwProgram &one)
+{
+    const size_t me = P.who.size();
+    P.who.push_back(one.who[0]);
+    P.pd.insert(P.pd.end(), one.pd.begin(), one.pd.end());
+    P.pwho.insert(P.pwho.end(), one.pd.size(), me);
+    P.pfinal.insert(P.pfinal.end(), one.pfinal.begin(), one.pfinal.end());
+    P.ptiles += one.ptiles;
+    if (P.rounds.size() < one.rounds.size()) P.rounds.resize(one.rounds.size());
+    for (OwStep s : one.steps) {
+        s.who = me;
+        s.at += s.kind ? P.rounds[(size_t)s.round].kd.size() : P.rounds[(size_t)s.round].fd.size();
+        P.steps.push_back(s);
+    }
+    for (size_t r = 0; r < one.rounds.size(); ++r) {
+        OwRound &a = P.rounds[r];
+        const OwRound &b = one.rounds[r];
+        a.fd.insert(a.fd.end(), b.fd.begin(), b.fd.end());
+        a.kd.insert(a.kd.end(), b.kd.begin(), b.kd.end());
+        a.tiles[0] += b.tiles[0]; a.tiles[1] += b.tiles[1]; a.bytes += b.bytes;
+    }
+    P.vec_at = one.vec_at;
+}
+
+template <class D>
+static void ow_fix_fold(D &d, uintptr_t base)
+{
+    for (int c = 0; c < d.nvalues; ++c) ow_fix(d.values[c].d_w, base);
+    for (int o = 0; o < d.nouts; ++o) { ow_fix(d.outs[o].p.d_w, base); ow_fix(d.outs[o].d_out, base); }
+}
+
+// a round's items of one kind into the block: descriptors, tile starts, tables from byte `at` of the arena on, words from `wat` on
+template <class D, class Dev>
+static void ow_fill(const std::vector<D> &items, Dev *hd, uint32_t *const (&ts)[3], uint32_t (&t)[3], size_t &at, unsigned long long *d_words, size_t &wat)
+{
+    constexpr size_t WORDS = tbatch_dev<D>::words;
+    t[0] = t[1] = t[2] = 0;
+    for (size_t k = 0; k < items.size(); ++k) {
+        ts[0][k] = t[0]; ts[1][k] = t[1]; ts[2][k] = t[2];
+        Dev d;
+        tbatch_fill(items[k], (unsigned long long *)((char *)g.jsum_arena.p + at), d_words + wat, d, t);
+        memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
+        at += (size_t)tbatch_table_bytes(items[k]);
+        wat += WORDS;
+    }
+    ts[0][items.size()] = t[0]; ts[1][items.size()] = t[1]; ts[2][items.size()] = t[2];
+}
+
+// One program: one upload, the launches of the pred items and of every round, one copy back, one wait; then the answers.
+static int ow_run(QueryRun &R, OwProgram &P)
+{
+    const size_t np = P.pd.size(), nr = P.rounds.size();
+    uint64_t arena = 0;
+    size_t nwords = np * FOLD_PRED_WORDS;
+    for (const OwRound &rd : P.rounds) {
+        if (rd.bytes > arena) arena = rd.bytes;
+        nwords += rd.fd.size() * FOLD_WORDS + rd.kd.size() * FOLDK_WORDS;
+    }
+    if (arena && batch_arena(g.jsum_arena, (size_t)arena, JSUM_ARENA_BYTES)) return -1;
+    if (ensure(g_qb.prog, P.vec_at)) return -1;
+    const uintptr_t base = (uintptr_t)g_qb.prog.p;
+    for (rhj_fold_pred_desc &d : P.pd) ow_fix(d.outs[0].d_out, base);
+    for (OwRound &rd : P.rounds) {
+        for (rhj_join_fold_desc &d : rd.fd) ow_fix_fold(d, base);
+        for (rhj_join_foldk_desc &d : rd.kd) ow_fix_fold(d, base);
+    }
+    struct RoundPieces { JoinFoldDesc *hf, *df; JoinFoldKDesc *hk, *dk; uint32_t *ts[2][3], *d_ts[2][3]; uint32_t t[2][3]; };
+    std::vector<RoundPieces> rp(nr);
+    Block blk;
+    unsigned long long *back, *words, *d_words; FoldPredDesc *hp, *dp; uint32_t *ptile, *d_ptile;
+    const auto pieces = [&](Block &b) {
+        b.back(back, nwords);
+        b.up(hp, dp, np); b.up(ptile, d_ptile, np + 1);
+        for (size_t r = 0; r < nr; ++r) {
+            const size_t nf = P.rounds[r].fd.size(), nk = P.rounds[r].kd.size();
+            b.up(rp[r].hf, rp[r].df, nf);
+            for (int j = 0; j < 3; ++j) b.up(rp[r].ts[0][j], rp[r].d_ts[0][j], nf + 1);
+            b.up(rp[r].hk, rp[r].dk, nk);
+            for (int j = 0; j < 3; ++j) b.up(rp[r].ts[1][j], rp[r].d_ts[1][j], nk + 1);
+        }
+        b.up(words, d_words, nwords);
+    };
+    if (batch_block(blk, pieces)) return -1;
+    memset(words, 0, nwords * 8);
+    size_t wat = 0;
+    uint32_t ptiles = 0;
+    for (size_t k = 0; k < np; ++k) {
+        FoldPredDesc d;
+        fpred_fill(P.pd[k], d_words + wat, d);
+        memcpy((void *)&hp[k], (const void *)&d, sizeof(d));
+        ptile[k] = ptiles;
+        ptiles += (uint32_t)jsum_tiles(P.pd[k].n);
+        wat += FOLD_PRED_WORDS;
+    }
+    ptile[np] = ptiles;
+    std::vector<size_t> wfold(nr), wfoldk(nr);           // where a round's words begin, by kind
+    for (size_t r = 0; r < nr; ++r) {
+        size_t at = 0;
+        wfold[r] = wat;
+        ow_fill(P.rounds[r].fd, rp[r].hf, rp[r].ts[0], rp[r].t[0], at, d_words, wat);
+        wfoldk[r] = wat;
+        ow_fill(P.rounds[r].kd, rp[r].hk, rp[r].ts[1], rp[r].t[1], at, d_words, wat);
+        if (at != (size_t)P.rounds[r].bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a round of a fold program were placed beyond its arena\n"); return -1; }
+    }
+    if (wat != nwords) { fprintf(stderr, "rhj: a fold program's words were miscounted\n"); return -1; }
+    rhj_query_batch_one_wait_info &info = g_query_one_wait_info;
+    if (batch_upload(blk, hp, blk.host_end())) return -1;
+    if (ptiles) {
+        RHJ_LAUNCH(k_fold_pred, dim3(ptiles), dim3(256), 0, g.stream, dp, d_ptile, (uint32_t)np);
+        ++info.launches;
+    }
+    for (size_t r = 0; r < nr; ++r) {
+        const OwRound &rd = P.rounds[r];
+        if (rd.fd.empty() && rd.kd.empty()) continue;
+        // the arena's tables of the round before are dead: stream order puts this memset behind their last reader
+        HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, (size_t)rd.bytes, g.stream));
+        ++info.memsets; ++info.rounds;
+        if (!rd.fd.empty()) {
+            tbatch_launch(rd.fd[0], rp[r].df, (uint32_t)rd.fd.size(), rp[r].d_ts[0], rp[r].t[0]);
+            info.launches += 2 + (rp[r].t[0][0] != 0);
+        }
+        if (!rd.kd.empty()) {
+            tbatch_launch(rd.kd[0], rp[r].dk, (uint32_t)rd.kd.size(), rp[r].d_ts[1], rp[r].t[1]);
+            info.launches += 2 + (rp[r].t[1][0] != 0);
+        }
+        info.fold_items += (uint32_t)rd.fd.size(); info.foldk_items += (uint32_t)rd.kd.size();
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, d_words, nwords * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    ++info.programs; ++info.waits;
+    info.queries += (uint32_t)P.who.size(); info.pred_items += (uint32_t)np;
+    // the answers, by the fold route's rule: a weight total of 0 anywhere is the empty result; else the last totals
+    std::vector<char> dead(P.who.size(), 0);
+    for (size_t k = 0; k < np; ++k)
+        if (back[k * FOLD_PRED_WORDS] == 0) dead[P.pwho[k]] = 1;
+    for (size_t r = 0; r < nr; ++r) {
+        for (size_t k = 0; k < P.rounds[r].fd.size(); ++k) tbatch_take(P.rounds[r].fd[k], back + wfold[r] + k * FOLD_WORDS);
+        for (size_t k = 0; k < P.rounds[r].kd.size(); ++k) tbatch_take(P.rounds[r].kd[k], back + wfoldk[r] + k * FOLDK_WORDS);
+    }
+    const auto outs_of = [&](const OwStep &s) { return s.kind ? P.rounds[(size_t)s.round].kd[s.at].outs : P.rounds[(size_t)s.round].fd[s.at].outs; };
+    for (const OwStep &s : P.steps)
+        if (outs_of(s)[0].total == 0) dead[s.who] = 1;
+    for (size_t k = 0; k < np; ++k) {
+        if (!P.pfinal[k] || dead[P.pwho[k]]) continue;
+        rhj_query_desc &q = R.queries[P.who[P.pwho[k]]];
+        q.rows = back[k * FOLD_PRED_WORDS];
+        for (int v = 0; v < q.nviews; ++v) q.sums[v] = back[k * FOLD_PRED_WORDS + 1 + (size_t)v];
+    }
+    for (const OwStep &s : P.steps) {
+        if (!s.last || dead[s.who]) continue;
+        rhj_query_desc &q = R.queries[P.who[s.who]];
+        const rhj_fold_out *outs = outs_of(s);
+        const int nouts = s.kind ? P.rounds[(size_t)s.round].kd[s.at].nouts : P.rounds[(size_t)s.round].fd[s.at].nouts;
+        q.rows = outs[0].total;
+        for (int o = 1; o < nouts; ++o) q.sums[s.view[(size_t)o]] = outs[o].total;
+    }
+    return 0;
+}
+
+// The one-wait route's queries (R.one_wait), in call order, as programs cut only at the chunk limits.
+static int query_one_wait(QueryRun &R)
+{
+    OwProgram P, one;
+    for (uint64_t i = 0; i < R.n; ++i) {
+        if (!R.one_wait[i]) continue;
+        if (ow_build(R, i, P.vec_at, one)) return -1;
+        if (!P.who.empty() && !ow_fits(P, one)) {
+            if (const int rc = ow_run(R, P)) return rc;
+            P = OwProgram();
+            if (ow_build(R, i, 0, one)) return -1;
+        }
+        if (P.who.empty()) P = one; else ow_merge(P, one);
+    }
+    return P.who.empty() ? 0 : ow_run(R, P);
+}
+
 static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     if (n == 0) return 0;
@@ -3357,6 +3804,8 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     memset(&g_query_foldk_info, 0, sizeof(g_query_foldk_info));
     memset(&g_query_fold_self_info, 0, sizeof(g_query_fold_self_info));
     memset(&g_query_fold_nodes_info, 0, sizeof(g_query_fold_nodes_info));
+    memset(&g_query_one_wait_info, 0, sizeof(g_query_one_wait_info));
+    std::vector<char> one_wait;
     const bool hand_over = g_query_fold && g_query_fold_keys && g_query_fold_self && g_query_fold_nodes;
     std::vector<int> park;
     bool invalid = false;                                 // the whole batch is validated before a device is touched
@@ -3367,9 +3816,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
         const int lv = query_levels(&queries[i], nrel, rels, nullptr);
         queries[i].rc = lv < 0 ? -3 : 0;
         invalid |= lv < 0;
-        const int how = !(g_query_fold && lv >= 0) ? 0 : lv > 0 && query_fold_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 1 :
-                        lv > 0 && g_query_fold_keys && query_foldk_plan(&queries[i], nrel, rels, nullptr, nullptr) > 0 ? 2 :
-                        g_query_fold_self && query_folds_self(&queries[i], nrel, rels) ? 3 : 0;
+        const int how = query_fold_how(&queries[i], nrel, rels, lv);
         int prefix = 0;                                   // of a query none of the three plans takes: the levels before its nodes fold
         if (!how && hand_over && lv >= 0) {
             rhj_foldn_plan plan;
@@ -3379,6 +3826,10 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
             bool fits = true;                             // a fold's sides have fewer than 2^32 rows
             for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
             folds[i] = !fits ? 0 : how ? (char)how : 4;
+            if (how && g_query_fold_one_wait && query_one_wait_plan(&queries[i], nrel, rels) == 1) {
+                if (one_wait.empty()) one_wait.assign(n, 0);
+                one_wait[i] = 1;
+            }
             if (fits && prefix) {
                 if (park.empty()) park.assign(n, 0);
                 park[i] = prefix;
@@ -3397,7 +3848,9 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     {
         QueryTimingOff inner_untimed;
         QueryRun R = {rels, queries, n, std::vector<QueryState>(n)};
-        R.folds.swap(folds); R.park.swap(park);
+        R.folds.swap(folds); R.park.swap(park); R.one_wait.swap(one_wait);
+        if (!R.one_wait.empty())
+            if (const int rc = query_one_wait(R)) return rc;       // the fold programs: their queries are finished before the others begin
         if (const int rc = query_filters(R)) return rc;
         if (const int rc = query_folds(R, false)) return rc;       // the fold route's queries: all finished before the levels
         // the levels.  (Level 0 also runs when no query has a join: the queries without one sum their views in its apply call.)
@@ -3996,6 +4449,10 @@ void rhj_set_query_fold_keys(int on) { RhjApiLock api_lock; g_query_fold_keys = 
 void rhj_set_query_fold_nodes(int on) { RhjApiLock api_lock; g_query_fold_nodes = on != 0; }
 void rhj_set_query_fold_node_rows(uint64_t limit) { RhjApiLock api_lock; g_query_fold_node_rows = limit < JSUM_MAX_ROWS ? limit : JSUM_MAX_ROWS; }
 const rhj_query_batch_fold_nodes_info *rhj_query_batch_last_fold_nodes_info(void) { return &g_query_fold_nodes_info; }
+void rhj_set_query_fold_one_wait(int on) { RhjApiLock api_lock; g_query_fold_one_wait = on != 0; }
+void rhj_set_query_fold_one_wait_rows(uint64_t limit) { RhjApiLock api_lock; g_query_fold_one_wait_rows = limit < JSUM_MAX_ROWS ? limit : JSUM_MAX_ROWS - 1; }
+int rhj_query_one_wait_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels) { return query_one_wait_plan(q, nrel, rels); }
+const rhj_query_batch_one_wait_info *rhj_query_batch_last_one_wait_info(void) { return &g_query_one_wait_info; }
 int rhj_query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps) { return query_foldk_plan(q, nrel, rels, root, steps); }
 int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps) { return query_fold_plan(q, nrel, rels, root, steps); }
 
@@ -4027,6 +4484,12 @@ int rhj_fold_self_batch_device(rhj_fold_self_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
     return fold_self_batch(items, n);
+}
+
+int rhj_fold_pred_batch_device(rhj_fold_pred_desc *items, uint64_t n)
+{
+    RhjApiLock api_lock;
+    return fold_pred_batch(items, n);
 }
 
 /* ---- bucket-range sharding of one join across GPUs (host side: sigmod-2018_amd/shard.py) ---- */

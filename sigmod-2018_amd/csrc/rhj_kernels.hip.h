@@ -53,6 +53,8 @@
 //                          words belong to different member bindings.
 //   rhj_fold_self_batch.hip.h many folds with no child in one launch: the equalities between two columns of one side as a 0/1
 //                          factor on its weights, and the sums of a query without a join.
+//   rhj_fold_pred_batch.hip.h the same with comparisons against constants in the mask: a filter as a 0/1 factor on a side's
+//                          weights, with no hit list.
 // Tags only pre-filter everywhere: every candidate is verified against the build tuple's full 64-bit key, so results are exact
 // for any hash and any tag collision.
 #pragma once
@@ -78,4 +80,5 @@
 #include "rhj_join_foldk_batch.hip.h"
 #include "rhj_join_foldn_batch.hip.h"
 #include "rhj_fold_self_batch.hip.h"
+#include "rhj_fold_pred_batch.hip.h"
 #include "rhj_diag.hip.h"
