@@ -2712,6 +2712,11 @@ rhj_query_batch_foldk_info g_query_foldk_info = {};
 rhj_query_batch_fold_self_info g_query_fold_self_info = {};
 rhj_query_batch_fold_nodes_info g_query_fold_nodes_info = {};
 rhj_query_batch_one_wait_info g_query_one_wait_info = {};
+static void query_infos_clear()
+{
+    g_query_info = {}; g_query_sum_info = {}; g_query_fold_info = {}; g_query_foldk_info = {};
+    g_query_fold_self_info = {}; g_query_fold_nodes_info = {}; g_query_one_wait_info = {};
+}
 
 struct QueryRun {                                         // what the stages of one call share
     const rhj_device_relation      *rels;
@@ -2958,198 +2963,76 @@ static int fold_schedule(const rhj_query_desc &q, int root, rhj_fold_step *steps
     return round;
 }
 
-static int query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps)
-{
-    if (!q) return -3;
-    std::vector<int> kinds((size_t)(q->njoins > 0 ? q->njoins : 0));
-    const int lv = query_levels(q, nrel, rels, kinds.data());
-    if (lv < 0) return -3;
-    if (lv == 0) return 0;
-    for (int l = 0; l < lv; ++l) if (kinds[l]) return 0;  // an equality inside a node: the predicates are no tree
-    int best = -1, best_root = 0;                         // (every step merged two nodes into one: nrels - 1 predicates, a spanning tree)
-    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
-    for (int r = 0; r < q->nrels; ++r) {
-        const int rounds = fold_schedule(*q, r, mine);
-        if (best >= 0 && rounds >= best) continue;
-        best = rounds; best_root = r;
-        memcpy(kept, mine, sizeof(kept));
-    }
-    if (root) *root = best_root;
-    if (steps) memcpy(steps, kept, (size_t)lv * sizeof(rhj_fold_step));
-    return lv;
-}
+// ---- the one planner (include/rhj_inter.h) ----------------------------------------------------------------
+// The four plan functions are one rule at four strengths, so one function plans and each of the four decides what it accepts.
+// fold_plan_at is the general rule, rhj_query_foldn_plan's for one prefix L of a VALID query (one query_levels accepts): the first
+// L predicates merge their nodes as query_levels does and join their (binding, column) terms' classes in a union-find; the others
+// go through the same union-find in order.  One that `drop` names is dropped; a kept one inside one node goes to self, counted on
+// that node; the others are grouped by unordered node pair, and the groups must be a spanning tree of the nodes.  The schedule is
+// fold_schedule's over one edge per group, the root the node that gives the fewest rounds, the lowest on a tie.
+enum FoldDrop {
+    DROP_REPEATS,                                         // rhj_query_foldk_plan's: the predicate written before, either way round
+    DROP_IMPLIED                                          // the others': every predicate whose terms are in one class already (a repeat, 0.1=0.1, an implied one)
+};
+struct FoldPlan : rhj_foldn_plan {                        // the general plan, and what the weaker rules ask about the predicates from L on:
+    bool twice;                                           // one names a binding on both sides
+    bool dropped;                                         // one was dropped
+};
 
-// The plan with parallel predicates grouped (include/rhj_inter.h): a predicate on one binding does not fold, a
-// repeated predicate is dropped, the others are grouped by unordered binding pair, and the groups must be a spanning tree.  The
-// schedule is fold_schedule's over one predicate per group; for a query whose predicates are a tree already the groups are its
-// predicates and the plan is query_fold_plan's.
-static int query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps)
+static bool fold_plan_at(const rhj_query_desc *q, int L, FoldDrop drop, FoldPlan &plan)
 {
-    if (!q) return -3;
-    const int lv = query_levels(q, nrel, rels, nullptr);
-    if (lv < 0) return -3;
-    if (lv == 0) return 0;
-    for (int l = 0; l < lv; ++l) if (q->joins[l].relA == q->joins[l].relB) return 0;       // a self-join
-    struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
-    std::vector<Group> groups;
-    std::vector<rhj_query_join> first;                    // a group's first predicate: the edge the schedule walks
-    for (int l = 0; l < lv; ++l) {
+    struct Term { int b, c; size_t up; };                 // a class member, and the member above it (itself: the class's root)
+    std::vector<Term> terms;
+    terms.reserve(2 * (size_t)q->njoins);
+    const auto term = [&](int b, int c) {
+        size_t k = 0;
+        while (k < terms.size() && !(terms[k].b == b && terms[k].c == c)) ++k;
+        if (k == terms.size()) terms.push_back(Term{b, c, k});
+        while (terms[k].up != k) k = terms[k].up;
+        return k;
+    };
+    const auto repeat = [&](int l) {
         const rhj_query_join &p = q->joins[l];
-        bool repeated = false;
-        for (int m = 0; m < l && !repeated; ++m) {
+        for (int m = 0; m < l; ++m) {
             const rhj_query_join &e = q->joins[m];
-            repeated = (e.relA == p.relA && e.colA == p.colA && e.relB == p.relB && e.colB == p.colB) ||
-                       (e.relA == p.relB && e.colA == p.colB && e.relB == p.relA && e.colB == p.colA);
+            if ((e.relA == p.relA && e.colA == p.colA && e.relB == p.relB && e.colB == p.colB) ||
+                (e.relA == p.relB && e.colA == p.colB && e.relB == p.relA && e.colB == p.colA)) return true;
         }
-        if (repeated) continue;
-        const int a = p.relA < p.relB ? p.relA : p.relB, b = p.relA < p.relB ? p.relB : p.relA;
-        size_t k = 0;
-        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
-        if (k == groups.size()) { groups.push_back(Group{a, b, 0, {}}); first.push_back(p); }
-        if (groups[k].n == RHJ_FOLD_MAX_KEYS) return 0;   // more key words than a tuple has
-        groups[k].joins[groups[k].n++] = l;
-    }
-    if ((int)groups.size() != q->nrels - 1) return 0;     // (query_levels saw all bindings connected: nrels - 1 edges are a spanning tree)
-    rhj_query_desc tree = *q;
-    tree.njoins = (int)first.size(); tree.joins = first.data();
-    int best = -1, best_root = 0;
-    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
-    for (int r = 0; r < q->nrels; ++r) {
-        const int rounds = fold_schedule(tree, r, mine);
-        if (best >= 0 && rounds >= best) continue;
-        best = rounds; best_root = r;
-        memcpy(kept, mine, sizeof(kept));
-    }
-    if (root) *root = best_root;
-    for (int k = 0; steps && k < tree.njoins; ++k) {
-        const int a = kept[k].child < kept[k].parent ? kept[k].child : kept[k].parent, b = kept[k].child < kept[k].parent ? kept[k].parent : kept[k].child;
-        rhj_foldk_step &st = steps[k];
-        memset(&st, 0, sizeof(st));
-        st.child = kept[k].child; st.parent = kept[k].parent; st.round = kept[k].round;
-        for (const Group &gr : groups) {
-            if (gr.a != a || gr.b != b) continue;
-            st.nkeys = gr.n;
-            for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
-        }
-    }
-    return tree.njoins;
-}
-
-// The plan with every predicate that forms no real cycle taken in (include/rhj_inter.h): the predicates go in
-// order through a union-find of their (binding, column) terms; one whose terms are in one class already is dropped (a repeat,
-// 0.1=0.1, an implied one); a kept one on one binding goes to self, the others are grouped as query_foldk_plan's and must be a
-// spanning tree.  1 folds, 0 does not, -3.
-static int query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *plan)
-{
-    if (!q) return -3;
-    const int lv = query_levels(q, nrel, rels, nullptr);
-    if (lv < 0) return -3;
-    std::vector<std::pair<int, int>> terms;               // a class member: (binding, column) ...
-    std::vector<size_t> up;                               // ... and the member above it (itself: the class's root)
-    const auto term = [&](int b, int c) {
-        size_t k = 0;
-        while (k < terms.size() && terms[k] != std::make_pair(b, c)) ++k;
-        if (k == terms.size()) { terms.emplace_back(b, c); up.push_back(k); }
-        while (up[k] != k) k = up[k];
-        return k;
+        return false;
     };
-    struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
-    std::vector<Group> groups;
-    std::vector<rhj_query_join> first;                    // a group's first kept predicate: the edge the schedule walks
-    std::vector<int> self;
-    int on_binding[RHJ_QUERY_MAX_RELS] = {};
-    for (int l = 0; l < lv; ++l) {
-        const rhj_query_join &p = q->joins[l];
-        const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
-        if (ca == cb) continue;                           // said already by the predicates before it
-        up[cb] = ca;
-        if (p.relA == p.relB) {
-            if (++on_binding[p.relA] > RHJ_FOLD_SELF_MAX_TERMS) return 0;       // more terms than an item has
-            self.push_back(l);
-            continue;
-        }
-        const int a = p.relA < p.relB ? p.relA : p.relB, b = p.relA < p.relB ? p.relB : p.relA;
-        size_t k = 0;
-        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
-        if (k == groups.size()) { groups.push_back(Group{a, b, 0, {}}); first.push_back(p); }
-        if (groups[k].n == RHJ_FOLD_MAX_KEYS) return 0;   // more key words than a tuple has
-        groups[k].joins[groups[k].n++] = l;
-    }
-    // (query_levels saw all bindings connected, and a dropped predicate's bindings are connected by kept ones: nrels - 1 groups
-    // are a spanning tree, more are a true cycle)
-    if ((int)groups.size() != q->nrels - 1) return 0;
-    if (!plan) return 1;
-    memset(plan, 0, sizeof(*plan));
-    plan->nself = (int)self.size();
-    for (size_t k = 0; k < self.size(); ++k) plan->self[k] = self[k];
-    plan->nsteps = (int)groups.size();
-    if (groups.empty()) return 1;                         // one binding: nothing to schedule
-    rhj_query_desc tree = *q;
-    tree.njoins = (int)first.size(); tree.joins = first.data();
-    int best = -1;
-    rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
-    for (int r = 0; r < q->nrels; ++r) {
-        const int rounds = fold_schedule(tree, r, mine);
-        if (best >= 0 && rounds >= best) continue;
-        best = rounds; plan->root = r;
-        memcpy(kept, mine, sizeof(kept));
-    }
-    for (int k = 0; k < plan->nsteps; ++k) {
-        const int a = kept[k].child < kept[k].parent ? kept[k].child : kept[k].parent, b = kept[k].child < kept[k].parent ? kept[k].parent : kept[k].child;
-        rhj_foldk_step &st = plan->steps[k];
-        st.child = kept[k].child; st.parent = kept[k].parent; st.round = kept[k].round;
-        for (const Group &gr : groups) {
-            if (gr.a != a || gr.b != b) continue;
-            st.nkeys = gr.n;
-            for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
-        }
-    }
-    return 1;
-}
-
-// The plan that hands over from levels to folds over merged nodes (include/rhj_inter.h): the shortest prefix L of
-// the predicates after which, run as levels, the rest is query_folds_plan's tree over the NODES.  One prefix: the first L
-// predicates merge their nodes as query_levels does and join their terms' classes; the others go through the same union-find in
-// order, a predicate inside one class dropped, a kept one inside one node counted on that node, the others grouped by node pair.
-static bool query_foldn_prefix(const rhj_query_desc *q, int L, rhj_foldn_plan *plan)
-{
-    std::vector<std::pair<int, int>> terms;               // a class member: (binding, column) ...
-    std::vector<size_t> up;                               // ... and the member above it (itself: the class's root)
-    const auto term = [&](int b, int c) {
-        size_t k = 0;
-        while (k < terms.size() && terms[k] != std::make_pair(b, c)) ++k;
-        if (k == terms.size()) { terms.emplace_back(b, c); up.push_back(k); }
-        while (up[k] != k) k = up[k];
-        return k;
-    };
-    int node[RHJ_QUERY_MAX_RELS];
+    memset(&plan, 0, sizeof(plan));
+    plan.levels = L;
+    int *const node = plan.node;
     for (int b = 0; b < q->nrels; ++b) node[b] = b;
     for (int l = 0; l < L; ++l) {
         const rhj_query_join &p = q->joins[l];
         const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
-        if (ca != cb) up[cb] = ca;
+        if (ca != cb) terms[cb].up = ca;
         const int na = node[p.relA], nb = node[p.relB];
         for (int x = 0; x < q->nrels; ++x) if (node[x] == nb) node[x] = na;      // the two nodes merge into A's
     }
     struct Group { int a, b, n; int joins[RHJ_FOLD_MAX_KEYS]; };
-    std::vector<Group> groups;
-    std::vector<int> self;
-    int on_node[RHJ_QUERY_MAX_RELS] = {};
+    Group groups[RHJ_QUERY_MAX_RELS * (RHJ_QUERY_MAX_RELS - 1) / 2];            // (room for every pair of nodes)
+    int ngroups = 0, on_node[RHJ_QUERY_MAX_RELS] = {};
     for (int l = L; l < q->njoins; ++l) {
         const rhj_query_join &p = q->joins[l];
         const size_t ca = term(p.relA, p.colA), cb = term(p.relB, p.colB);
-        if (ca == cb) continue;                           // said already by the predicates before it
-        up[cb] = ca;
+        plan.twice |= p.relA == p.relB;
+        if (drop == DROP_IMPLIED ? ca == cb : repeat(l)) {                      // said already by the predicates before it
+            plan.dropped = true;
+            continue;
+        }
+        if (ca != cb) terms[cb].up = ca;
         const int na = node[p.relA], nb = node[p.relB];
         if (na == nb) {
             if (++on_node[na] > RHJ_FOLD_SELF_MAX_TERMS) return false;          // more terms than an item has
-            self.push_back(l);
+            plan.self[plan.nself++] = l;
             continue;
         }
         const int a = na < nb ? na : nb, b = na < nb ? nb : na;
-        size_t k = 0;
-        while (k < groups.size() && !(groups[k].a == a && groups[k].b == b)) ++k;
-        if (k == groups.size()) groups.push_back(Group{a, b, 0, {}});
+        int k = 0;
+        while (k < ngroups && !(groups[k].a == a && groups[k].b == b)) ++k;
+        if (k == ngroups) groups[ngroups++] = Group{a, b, 0, {}};
         if (groups[k].n == RHJ_FOLD_MAX_KEYS) return false;                     // more key words than a tuple has
         groups[k].joins[groups[k].n++] = l;
     }
@@ -3160,37 +3043,34 @@ static bool query_foldn_prefix(const rhj_query_desc *q, int L, rhj_foldn_plan *p
         id[b] = is_node ? nodes : -1;
         if (is_node) of[nodes++] = b;
     }
-    if ((int)groups.size() != nodes - 1) return false;    // a true cycle over the nodes
-    if (!plan) return true;
-    memset(plan, 0, sizeof(*plan));
-    plan->levels = L;
-    for (int b = 0; b < q->nrels; ++b) plan->node[b] = node[b];
-    plan->nself = (int)self.size();
-    for (size_t k = 0; k < self.size(); ++k) plan->self[k] = self[k];
-    plan->nsteps = (int)groups.size();
-    plan->root = of[0];
-    if (groups.empty()) return true;                      // one node: nothing to schedule
+    // (query_levels saw all bindings connected, and a dropped predicate's are connected by kept ones: nodes - 1 groups are a
+    // spanning tree, more are a true cycle)
+    if (ngroups != nodes - 1) return false;
+    plan.nsteps = ngroups;
+    plan.root = of[0];
+    if (ngroups == 0) return true;                        // one node: nothing to schedule
     // fold_schedule over the nodes by rank (the ranks ascend with the ids, so "the lowest first" means the same): one edge a group
-    std::vector<rhj_query_join> first;
-    for (const Group &gr : groups) {
-        const rhj_query_join &p = q->joins[gr.joins[0]];
-        first.push_back(rhj_query_join{id[node[p.relA]], p.colA, id[node[p.relB]], p.colB});
+    rhj_query_join first[FOLD_MAX_STEPS];
+    for (int k = 0; k < ngroups; ++k) {
+        const rhj_query_join &p = q->joins[groups[k].joins[0]];
+        first[k] = rhj_query_join{id[node[p.relA]], p.colA, id[node[p.relB]], p.colB};
     }
     rhj_query_desc tree = *q;
-    tree.nrels = nodes; tree.njoins = (int)first.size(); tree.joins = first.data();
+    tree.nrels = nodes; tree.njoins = ngroups; tree.joins = first;
     int best = -1;
     rhj_fold_step mine[FOLD_MAX_STEPS], kept[FOLD_MAX_STEPS];
     for (int r = 0; r < nodes; ++r) {
         const int rounds = fold_schedule(tree, r, mine);
         if (best >= 0 && rounds >= best) continue;
-        best = rounds; plan->root = of[r];
+        best = rounds; plan.root = of[r];
         memcpy(kept, mine, sizeof(kept));
     }
-    for (int k = 0; k < plan->nsteps; ++k) {
+    for (int k = 0; k < plan.nsteps; ++k) {
         const int c = of[kept[k].child], p = of[kept[k].parent];
-        rhj_foldk_step &st = plan->steps[k];
+        rhj_foldk_step &st = plan.steps[k];
         st.child = c; st.parent = p; st.round = kept[k].round;
-        for (const Group &gr : groups) {
+        for (int m = 0; m < ngroups; ++m) {
+            const Group &gr = groups[m];
             if (gr.a != (c < p ? c : p) || gr.b != (c < p ? p : c)) continue;
             st.nkeys = gr.n;
             for (int t = 0; t < gr.n; ++t) st.joins[t] = gr.joins[t];
@@ -3199,23 +3079,81 @@ static bool query_foldn_prefix(const rhj_query_desc *q, int L, rhj_foldn_plan *p
     return true;
 }
 
-static int query_foldn_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_foldn_plan *plan)
+// The four rules over a valid query; each leaves the plan it accepts in `plan`.
+// rhj_query_folds_plan's: the general rule with no level before it.
+static bool folds_rule(const rhj_query_desc *q, FoldPlan &plan) { return fold_plan_at(q, 0, DROP_IMPLIED, plan); }
+// rhj_query_foldn_plan's: the shortest prefix of levels after which the general rule holds over the nodes.
+static bool foldn_rule(const rhj_query_desc *q, FoldPlan &plan)
 {
-    if (!q) return -3;
-    const int lv = query_levels(q, nrel, rels, nullptr);
-    if (lv < 0) return -3;
-    for (int L = 0; L <= (lv > 0 ? lv - 1 : 0); ++L)
-        if (query_foldn_prefix(q, L, plan)) return 1;
-    return 0;                                             // (not reached: with one predicate left the rest is one step, one term or nothing)
+    for (int L = 0; L <= (q->njoins > 0 ? q->njoins - 1 : 0); ++L)
+        if (fold_plan_at(q, L, DROP_IMPLIED, plan)) return true;
+    return false;                                         // (not reached: with one predicate left the rest is one step, one term or nothing)
+}
+// rhj_query_foldk_plan's: at least one predicate, none on one binding, and only repeats dropped: an implied predicate stays a key word.
+static bool foldk_rule(const rhj_query_desc *q, FoldPlan &plan) { return q->njoins > 0 && fold_plan_at(q, 0, DROP_REPEATS, plan) && !plan.twice; }
+// rhj_query_fold_plan's: every predicate joins two distinct nodes, so none is dropped (a repeat lies inside a merged node), none is on
+// one binding and none shares its pair of bindings with another.
+static bool fold_rule(const rhj_query_desc *q, FoldPlan &plan)
+{
+    if (q->njoins == 0 || !folds_rule(q, plan) || plan.twice || plan.dropped) return false;
+    for (int k = 0; k < plan.nsteps; ++k) if (plan.steps[k].nkeys > 1) return false;
+    return true;
 }
 
-// whether the fold route takes a query because of rhj_set_query_fold_self: the plan above, its steps within the key switch
-static bool query_folds_self(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels)
+// The entry points: -3 from query_levels before anything else, 0 where the rule refuses (nothing is written then), else the plan in
+// the function's own structure; every output may be NULL.
+static int query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_fold_step *steps)
 {
-    rhj_folds_plan plan;
-    if (query_folds_plan(q, nrel, rels, &plan) != 1) return false;
-    for (int k = 0; k < plan.nsteps; ++k) if (plan.steps[k].nkeys > 1 && !g_query_fold_keys) return false;
-    return true;
+    FoldPlan plan;
+    if (query_levels(q, nrel, rels, nullptr) < 0) return -3;
+    if (!fold_rule(q, plan)) return 0;
+    if (root) *root = plan.root;
+    for (int k = 0; steps && k < plan.nsteps; ++k) steps[k] = rhj_fold_step{plan.steps[k].child, plan.steps[k].parent, plan.steps[k].round};
+    return plan.nsteps;
+}
+
+static int query_foldk_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *root, rhj_foldk_step *steps)
+{
+    FoldPlan plan;
+    if (query_levels(q, nrel, rels, nullptr) < 0) return -3;
+    if (!foldk_rule(q, plan)) return 0;
+    if (root) *root = plan.root;
+    if (steps) memcpy(steps, plan.steps, (size_t)plan.nsteps * sizeof(rhj_foldk_step));
+    return plan.nsteps;
+}
+
+static int query_folds_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_folds_plan *out)
+{
+    FoldPlan plan;
+    if (query_levels(q, nrel, rels, nullptr) < 0) return -3;
+    if (!folds_rule(q, plan)) return 0;
+    if (!out) return 1;
+    memset(out, 0, sizeof(*out));
+    out->root = plan.root; out->nsteps = plan.nsteps; out->nself = plan.nself;
+    memcpy(out->steps, plan.steps, sizeof(out->steps)); memcpy(out->self, plan.self, sizeof(out->self));
+    return 1;
+}
+
+static int query_foldn_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, rhj_foldn_plan *out)
+{
+    FoldPlan plan;
+    if (query_levels(q, nrel, rels, nullptr) < 0) return -3;
+    if (!foldn_rule(q, plan)) return 0;
+    if (out) *out = plan;                                 // (the general plan's first part is this structure)
+    return 1;
+}
+
+// which rule lets a valid query of lv levels fold under the switches as they stand: 1 rhj_query_fold_plan's, 2 rhj_query_foldk_plan's,
+// 3 rhj_query_folds_plan's with its steps within the key switch, 0 none
+static int query_fold_how(const rhj_query_desc *q, int lv)
+{
+    FoldPlan plan;
+    if (!(g_query_fold && lv >= 0)) return 0;
+    if (fold_rule(q, plan)) return 1;
+    if (g_query_fold_keys && foldk_rule(q, plan)) return 2;
+    if (!(g_query_fold_self && folds_rule(q, plan))) return 0;
+    for (int k = 0; k < plan.nsteps; ++k) if (plan.steps[k].nkeys > 1 && !g_query_fold_keys) return 0;
+    return 3;
 }
 
 struct FoldQuery {                                        // a query on the fold route
@@ -3226,6 +3164,119 @@ struct FoldQuery {                                        // a query on the fold
     const uint64_t *w[RHJ_QUERY_MAX_RELS];                // node -> its weight vector; nullptr: ones.  (A node is a binding until levels have merged some: QueryState::node)
     const uint64_t *acc[RHJ_QUERY_MAX_RELS][RHJ_QUERY_MAX_VIEWS];     // node, view -> the view's partial sums per row, when the node carries the view
 };
+
+// The plan of a query on the fold route into f: how is QueryRun::folds's code, park the levels of a query with how 4.  The rule
+// accepted the query when the batch was validated, so a refusal here is an error, reported under the route's name; counted: the
+// query goes into the fold route's infos.
+static int fold_query(const rhj_query_desc &q, int how, int park, const char *route, bool counted, FoldQuery &f)
+{
+    FoldPlan plan;
+    if (how == 4) {                                       // parked alive after its level prefix
+        if (!foldn_rule(&q, plan) || plan.levels != park) { fprintf(stderr, "rhj: a parked query has no plan over its nodes\n"); return -1; }
+    } else if (!(how == 3 ? folds_rule(&q, plan) : foldk_rule(&q, plan))) {       // (3: possibly no step at all; 1: rhj_query_foldk_plan's is rhj_query_fold_plan's)
+        fprintf(stderr, "rhj: a query on the %s route has no fold plan\n", route);
+        return -1;
+    }
+    f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
+    memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
+    if (!counted) return 0;
+    if (how == 4) { ++g_query_fold_nodes_info.node_queries; g_query_fold_nodes_info.node_levels += (uint32_t)plan.levels; }
+    if (how == 3) ++g_query_fold_self_info.self_queries;
+    if (how == 2) ++g_query_foldk_info.foldk_queries;
+    return 0;
+}
+
+// One step's item before it is a descriptor of its kind: a fold of node `child` into node `parent`, stated over a QueryState (the
+// member bindings' vectors, a binding's node, a node's rows).  Key word t is predicate joins[t] of the step, the parent's column
+// read through the vector of the member binding the predicate names on that side, the child's likewise.
+struct FoldItem {
+    int             nkeys, memR[RHJ_FOLD_MAX_KEYS], memS[RHJ_FOLD_MAX_KEYS];      // a word's member binding, parent side and child side
+    const uint64_t *colR[RHJ_FOLD_MAX_KEYS], *colS[RHJ_FOLD_MAX_KEYS];
+    bool            one_member;                           // every word of a side names the member its word 0 names
+    uint64_t        nR, nS;
+    int             nvalues, nouts;
+    rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];
+    rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
+    std::array<int, RHJ_FOLD_MAX_OUTS> view;              // the view an output belongs to, -1 the weight
+};
+
+// Step k of query q as an item.  Unless it is the root's last fold (totals only) every output is a vector of the parent's rows:
+// take(o, rows) is asked for output o's, in order, and what it returns is the output's d_out.
+template <class Take>
+static FoldItem fold_item(const QueryRun &R, const rhj_query_desc &q, const QueryState &s, const FoldQuery &f, int k, Take take)
+{
+    const rhj_foldk_step &step = f.steps[k];
+    const int S = step.child, P = step.parent;
+    const bool last = k == f.nsteps - 1;
+    FoldItem d = {};
+    d.nkeys = step.nkeys;
+    d.one_member = true;
+    for (int t = 0; t < step.nkeys; ++t) {                // the predicates between the two: word t of both sides
+        const rhj_query_join &p = q.joins[step.joins[t]];
+        const bool a_is_parent = s.node[p.relA] == P;
+        d.memR[t] = a_is_parent ? p.relA : p.relB; d.memS[t] = a_is_parent ? p.relB : p.relA;
+        d.colR[t] = R.column(q, d.memR[t], a_is_parent ? p.colA : p.colB);
+        d.colS[t] = R.column(q, d.memS[t], a_is_parent ? p.colB : p.colA);
+        d.one_member &= d.memR[t] == d.memR[0] && d.memS[t] == d.memS[0];
+    }
+    d.nR = s.rows[P]; d.nS = s.rows[S];
+    int value_of[RHJ_QUERY_MAX_VIEWS];
+    d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
+    for (int v = 0; v < q.nviews; ++v) {
+        const int x = q.views[v].rel;
+        value_of[v] = -1;
+        if (s.node[x] == S)      d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], s.vec[x], R.column(q, x, q.views[v].col)};
+        else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
+    }
+    const auto out = [&](int value, rhj_fold_factor p, int v) {
+        d.view[(size_t)d.nouts] = v;
+        rhj_fold_out &o = d.outs[d.nouts];
+        o.value = value; o.p = p;
+        if (!last) o.d_out = take(d.nouts, d.nR);
+        ++d.nouts;
+    };
+    out(0, rhj_fold_factor{f.w[P], nullptr, nullptr}, -1);                         // the parent's new weight
+    for (int v = 0; v < q.nviews; ++v) {
+        const int x = q.views[v].rel;
+        if (value_of[v] >= 0)                out(value_of[v], rhj_fold_factor{f.w[P], nullptr, nullptr}, v);      // a view coming from the child
+        else if (f.acc[P][v])                out(0, rhj_fold_factor{f.acc[P][v], nullptr, nullptr}, v);           // a view the parent carried
+        else if (last && s.node[x] == P)     out(0, rhj_fold_factor{f.w[P], s.vec[x], R.column(q, x, q.views[v].col)}, v);   // a view on the root: lazy until now
+    }
+    return d;
+}
+
+// An item as the descriptor of its kind: on one key, on a tuple read through one vector a side (the item's one_member), or on a
+// tuple whose every word has its vector.
+static void fold_keys(rhj_join_fold_desc &d, const FoldItem &it, const QueryState &s)
+{
+    d.d_colR = it.colR[0]; d.d_selR = s.vec[it.memR[0]];
+    d.d_colS = it.colS[0]; d.d_selS = s.vec[it.memS[0]];
+}
+static void fold_keys(rhj_join_foldk_desc &d, const FoldItem &it, const QueryState &s)
+{
+    d.nkeys = it.nkeys;
+    for (int w = 0; w < it.nkeys; ++w) { d.d_colR[w] = it.colR[w]; d.d_colS[w] = it.colS[w]; }
+    d.d_selR = s.vec[it.memR[0]]; d.d_selS = s.vec[it.memS[0]];
+}
+static void fold_keys(rhj_join_foldn_desc &d, const FoldItem &it, const QueryState &s)
+{
+    d.nkeys = it.nkeys;
+    for (int w = 0; w < it.nkeys; ++w) {
+        d.d_colR[w] = it.colR[w]; d.d_selR[w] = s.vec[it.memR[w]];
+        d.d_colS[w] = it.colS[w]; d.d_selS[w] = s.vec[it.memS[w]];
+    }
+}
+template <class D>
+static void fold_desc(D &d, const FoldItem &it, const QueryState &s)    // d: all zero
+{
+    fold_keys(d, it, s);
+    d.nR = it.nR; d.nS = it.nS;
+    d.nvalues = it.nvalues; d.nouts = it.nouts;
+    memcpy(d.values, it.values, sizeof(d.values)); memcpy(d.outs, it.outs, sizeof(d.outs));
+}
+
+struct FoldOuts { rhj_fold_out *outs; int nouts; };       // an item's outputs, whatever its kind
+template <class D> static FoldOuts fold_outs(D &d) { return FoldOuts{d.outs, d.nouts}; }
 
 // Before round 0, ONE fold_self_batch call over the queries with predicates inside a node (rhj_set_query_fold_self's, whose nodes
 // are their bindings, and rhj_set_query_fold_nodes's): a node with such predicates gets its first weight vector (0 / 1 per row),
@@ -3296,24 +3347,7 @@ static int query_folds(QueryRun &R, bool nodes_pass)
         if (!R.folds[i] || !R.st[i].alive || (R.folds[i] == 4) != nodes_pass) continue;
         FoldQuery f = {};
         f.i = i;
-        if (R.folds[i] == 4) {                            // parked alive after its level prefix
-            rhj_foldn_plan plan;
-            if (query_foldn_plan(&R.queries[i], INT_MAX, nullptr, &plan) != 1 || plan.levels != R.park[i]) { fprintf(stderr, "rhj: a parked query has no plan over its nodes\n"); return -1; }
-            f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
-            memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
-            ++g_query_fold_nodes_info.node_queries;
-            g_query_fold_nodes_info.node_levels += (uint32_t)plan.levels;
-        } else if (R.folds[i] == 3) {                            // rhj_set_query_fold_self's: possibly no step at all
-            rhj_folds_plan plan;
-            if (query_folds_plan(&R.queries[i], INT_MAX, nullptr, &plan) != 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
-            f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
-            memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
-            ++g_query_fold_self_info.self_queries;
-        } else {
-            f.nsteps = query_foldk_plan(&R.queries[i], INT_MAX, nullptr, &f.root, f.steps);     // (validated already; query_fold_plan's where that has one)
-            if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the fold route has no fold plan\n"); return -1; }
-        }
-        if (R.folds[i] == 2) ++g_query_foldk_info.foldk_queries;
+        if (fold_query(R.queries[i], R.folds[i], R.folds[i] == 4 ? R.park[i] : 0, "fold", true, f)) return -1;
         if (f.nsteps && f.steps[f.nsteps - 1].round + 1 > rounds) rounds = f.steps[f.nsteps - 1].round + 1;
         fq.push_back(f);
     }
@@ -3335,72 +3369,16 @@ static int query_folds(QueryRun &R, bool nodes_pass)
             const rhj_query_desc &q = R.queries[f.i];
             const QueryState &s = R.st[f.i];
             for (; s.alive && f.next < f.nsteps && f.steps[f.next].round == r; ++f.next) {
-                const rhj_foldk_step &step = f.steps[f.next];
-                const int S = step.child, P = step.parent;
-                const bool last = f.next == f.nsteps - 1;  // the root's last fold: totals only
-                rhj_join_fold_desc d = {};
-                std::array<int, RHJ_FOLD_MAX_OUTS> ov;
-                const uint64_t *keyR[RHJ_FOLD_MAX_KEYS] = {}, *keyS[RHJ_FOLD_MAX_KEYS] = {};
-                int memR[RHJ_FOLD_MAX_KEYS] = {}, memS[RHJ_FOLD_MAX_KEYS] = {};     // the member binding a word is read through
-                bool one_member = true;                    // every word of a side names the member its word 0 names
-                for (int t = 0; t < step.nkeys; ++t) {     // the predicates between the two: word t of both sides
-                    const rhj_query_join &p = q.joins[step.joins[t]];
-                    const bool a_is_parent = s.node[p.relA] == P;
-                    memR[t] = a_is_parent ? p.relA : p.relB; memS[t] = a_is_parent ? p.relB : p.relA;
-                    keyR[t] = R.column(q, memR[t], a_is_parent ? p.colA : p.colB);
-                    keyS[t] = R.column(q, memS[t], a_is_parent ? p.colB : p.colA);
-                    one_member &= memR[t] == memR[0] && memS[t] == memS[0];
-                }
-                d.d_colR = keyR[0]; d.d_colS = keyS[0];
-                d.d_selR = s.vec[memR[0]]; d.nR = s.rows[P];
-                d.d_selS = s.vec[memS[0]]; d.nS = s.rows[S];
-                int value_of[RHJ_QUERY_MAX_VIEWS];
-                d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
-                for (int v = 0; v < q.nviews; ++v) {
-                    const int x = q.views[v].rel;
-                    value_of[v] = -1;
-                    if (s.node[x] == S)      d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], s.vec[x], R.column(q, x, q.views[v].col)};
-                    else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
-                }
-                const auto out = [&](int value, rhj_fold_factor p, int v) {
-                    if (!last) ob.take(where.size(), d.nouts, d.nR);
-                    ov[(size_t)d.nouts] = v;
-                    rhj_fold_out &o = d.outs[d.nouts++];
-                    o.value = value; o.p = p;
-                };
-                out(0, rhj_fold_factor{f.w[P], nullptr, nullptr}, -1);                         // the parent's new weight
-                for (int v = 0; v < q.nviews; ++v) {
-                    if (value_of[v] >= 0)                    out(value_of[v], rhj_fold_factor{f.w[P], nullptr, nullptr}, v);      // a view coming from the child
-                    else if (f.acc[P][v])                    out(0, rhj_fold_factor{f.acc[P][v], nullptr, nullptr}, v);           // a view the parent carried
-                    else if (last && s.node[q.views[v].rel] == P)    out(0, rhj_fold_factor{f.w[P], s.vec[q.views[v].rel], R.column(q, q.views[v].rel, q.views[v].col)}, v);   // a view on the root: lazy until now
-                }
-                who.push_back(k); par.push_back(P); view.push_back(ov);
-                if (step.nkeys == 1) { where.emplace_back(0, fd.size()); fd.push_back(d); continue; }
-                if (!one_member) {                         // the same item, every word through its member's vector
-                    rhj_join_foldn_desc t = {};
-                    t.nkeys = step.nkeys;
-                    for (int w = 0; w < step.nkeys; ++w) {
-                        t.d_colR[w] = keyR[w]; t.d_selR[w] = s.vec[memR[w]];
-                        t.d_colS[w] = keyS[w]; t.d_selS[w] = s.vec[memS[w]];
-                    }
-                    t.nR = d.nR; t.nS = d.nS;
-                    t.nvalues = d.nvalues; t.nouts = d.nouts;
-                    memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
-                    where.emplace_back(2, nd.size()); nd.push_back(t);
-                    continue;
-                }
-                rhj_join_foldk_desc t = {};                // the same item on its tuple of columns
-                t.nkeys = step.nkeys;
-                for (int w = 0; w < step.nkeys; ++w) { t.d_colR[w] = keyR[w]; t.d_colS[w] = keyS[w]; }
-                t.d_selR = d.d_selR; t.nR = d.nR; t.d_selS = d.d_selS; t.nS = d.nS;
-                t.nvalues = d.nvalues; t.nouts = d.nouts;
-                memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
-                where.emplace_back(1, kd.size()); kd.push_back(t);
+                const FoldItem it = fold_item(R, q, s, f, f.next, [&](int o, uint64_t rows) { ob.take(where.size(), o, rows); return (uint64_t *)nullptr; });
+                who.push_back(k); par.push_back(f.steps[f.next].parent); view.push_back(it.view);
+                if (it.nkeys == 1)       { where.emplace_back(0, fd.size()); fold_desc(fd.emplace_back(), it, s); }
+                else if (it.one_member)  { where.emplace_back(1, kd.size()); fold_desc(kd.emplace_back(), it, s); }
+                else                     { where.emplace_back(2, nd.size()); fold_desc(nd.emplace_back(), it, s); }
             }
         }
         if (where.empty()) continue;
-        const auto outs_of = [&](size_t a) { return where[a].first == 2 ? nd[where[a].second].outs : where[a].first ? kd[where[a].second].outs : fd[where[a].second].outs; };
-        if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { outs_of(a)[o].d_out = (uint64_t *)p; })) return -1;
+        const auto outs_of = [&](size_t a) { return where[a].first == 2 ? fold_outs(nd[where[a].second]) : where[a].first ? fold_outs(kd[where[a].second]) : fold_outs(fd[where[a].second]); };
+        if (ob.resolve(g_qb.fold[(size_t)r], [&](size_t a, int o, char *p) { outs_of(a).outs[o].d_out = (uint64_t *)p; })) return -1;
         if (!fd.empty()) {
             ++g_query_fold_info.fold_calls;
             g_query_fold_info.fold_items += (uint32_t)fd.size();
@@ -3420,8 +3398,7 @@ static int query_folds(QueryRun &R, bool nodes_pass)
             FoldQuery &f = fq[who[a]];
             rhj_query_desc &q = R.queries[f.i];
             QueryState &s = R.st[f.i];
-            const rhj_fold_out *outs = outs_of(a);
-            const int nouts = where[a].first == 2 ? nd[where[a].second].nouts : where[a].first ? kd[where[a].second].nouts : fd[where[a].second].nouts;
+            const auto [outs, nouts] = outs_of(a);
             if (!s.alive) continue;                       // (finished by another item of this round)
             if (outs[0].total == 0) { s.alive = false; continue; }           // the subtree's join is empty: rows = 0, sums 0
             const bool last = outs[0].d_out == nullptr;
@@ -3446,21 +3423,12 @@ static int query_folds(QueryRun &R, bool nodes_pass)
 // k_fold_pred, per round a memset and the fold batches' own launches, one copy back and one wait.  A weight or view vector is a
 // piece of ONE buffer a program (g_qb.prog), never reused inside it; until the buffer has its size a descriptor names such a vector
 // by its offset (ow_ref), and ow_run turns the offsets into addresses.
-// which plan lets a valid query of lv levels fold under the switches as they stand: 1 rhj_query_fold_plan, 2 rhj_query_foldk_plan,
-// 3 rhj_query_folds_plan, 0 none
-static int query_fold_how(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int lv)
-{
-    return !(g_query_fold && lv >= 0) ? 0 : lv > 0 && query_fold_plan(q, nrel, rels, nullptr, nullptr) > 0 ? 1 :
-           lv > 0 && g_query_fold_keys && query_foldk_plan(q, nrel, rels, nullptr, nullptr) > 0 ? 2 :
-           g_query_fold_self && query_folds_self(q, nrel, rels) ? 3 : 0;
-}
-
 static int query_one_wait_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels)
 {
     if (!q) return -3;
     const int lv = query_levels(q, nrel, rels, nullptr);
     if (lv < 0) return -3;
-    if (!rels || !query_fold_how(q, nrel, rels, lv)) return 0;
+    if (!rels || !query_fold_how(q, lv)) return 0;
     for (int b = 0; b < q->nrels; ++b) {
         const uint64_t rows = rels[q->rels[b]].num_tuples;
         if (rows < 1 || rows > g_query_fold_one_wait_rows) return 0;
@@ -3505,16 +3473,9 @@ static int ow_build(const QueryRun &R, uint64_t i, size_t vec_at, OwProgram &P)
     P.vec_at = vec_at;
     FoldQuery f = {};
     f.i = i;
-    if (R.folds[i] == 3) {
-        rhj_folds_plan plan;
-        if (query_folds_plan(&q, INT_MAX, nullptr, &plan) != 1) { fprintf(stderr, "rhj: a query on the one-wait route has no fold plan\n"); return -1; }
-        f.root = plan.root; f.nsteps = plan.nsteps; f.nself = plan.nself;
-        memcpy(f.steps, plan.steps, sizeof(f.steps)); memcpy(f.self, plan.self, sizeof(f.self));
-    } else {
-        f.nsteps = query_foldk_plan(&q, INT_MAX, nullptr, &f.root, f.steps);
-        if (f.nsteps < 1) { fprintf(stderr, "rhj: a query on the one-wait route has no fold plan\n"); return -1; }
-    }
-    const auto rows = [&](int b) { return R.rels[q.rels[b]].num_tuples; };
+    if (fold_query(q, R.folds[i], 0, "one-wait", false, f)) return -1;
+    QueryState s = {};                                    // every binding its whole relation, its own node
+    for (int b = 0; b < q.nrels; ++b) { s.node[b] = b; s.rows[b] = R.rels[q.rels[b]].num_tuples; }
     const auto take = [&](uint64_t n) { uint64_t *p = ow_ref(P.vec_at); P.vec_at += (size_t)((n + 1) / 2 * 2) * 8; return p; };
     // the pred items: a binding's filters and kept one-binding predicates as its first weight vector
     for (int b = 0; b < q.nrels; ++b) {
@@ -3531,7 +3492,7 @@ static int ow_build(const QueryRun &R, uint64_t i, size_t vec_at, OwProgram &P)
             d.eqs[d.neq++] = rhj_fold_eq_term{R.column(q, b, p.colA), nullptr, R.column(q, b, p.colB), nullptr};
         }
         if (d.nconst + d.neq == 0 && f.nsteps > 0) continue;       // no predicate of its own: the weight stays ones
-        d.n = rows(b);
+        d.n = s.rows[b];
         d.nouts = 1;                                      // output 0: ones, so its total is the rows that pass
         if (f.nsteps == 0) {                              // the whole query is this binding: the views' sums, nothing written
             for (int v = 0; v < q.nviews; ++v) d.outs[d.nouts++].p = rhj_fold_factor{nullptr, nullptr, R.column(q, q.views[v].rel, q.views[v].col)};
@@ -3542,63 +3503,26 @@ static int ow_build(const QueryRun &R, uint64_t i, size_t vec_at, OwProgram &P)
         P.pd.push_back(d); P.pwho.push_back(0); P.pfinal.push_back(f.nsteps == 0);
         P.ptiles += jsum_tiles(d.n);
     }
-    // the steps: query_folds's items, every side a whole relation
+    // the steps: query_folds's items.  (Every side is a whole relation, every node one binding: no vector, and no word of a key
+    // names another member than word 0's, so no item is rhj_join_foldn_batch_device's.)
     for (int k = 0; k < f.nsteps; ++k) {
         const rhj_foldk_step &step = f.steps[k];
-        const int S = step.child, Pn = step.parent;
         const bool last = k == f.nsteps - 1;
         if (P.rounds.size() <= (size_t)step.round) P.rounds.resize((size_t)step.round + 1);
         OwRound &rd = P.rounds[(size_t)step.round];
-        rhj_join_fold_desc d = {};
-        OwStep os = {};
-        os.who = 0; os.round = step.round; os.last = last;
-        const uint64_t *keyR[RHJ_FOLD_MAX_KEYS] = {}, *keyS[RHJ_FOLD_MAX_KEYS] = {};
-        for (int t = 0; t < step.nkeys; ++t) {
-            const rhj_query_join &p = q.joins[step.joins[t]];
-            const bool a_is_parent = p.relA == Pn;
-            keyR[t] = R.column(q, Pn, a_is_parent ? p.colA : p.colB);
-            keyS[t] = R.column(q, S, a_is_parent ? p.colB : p.colA);
-        }
-        d.d_colR = keyR[0]; d.d_colS = keyS[0];
-        d.nR = rows(Pn); d.nS = rows(S);
-        int value_of[RHJ_QUERY_MAX_VIEWS];
-        d.values[d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, nullptr};             // value 0: the child's weight
-        for (int v = 0; v < q.nviews; ++v) {
-            value_of[v] = -1;
-            if (q.views[v].rel == S) d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.w[S], nullptr, R.column(q, S, q.views[v].col)};
-            else if (f.acc[S][v])    d.values[value_of[v] = d.nvalues++] = rhj_fold_factor{f.acc[S][v], nullptr, nullptr};
-        }
-        const auto out = [&](int value, rhj_fold_factor p, int v) {
-            os.view[(size_t)d.nouts] = v;
-            rhj_fold_out &o = d.outs[d.nouts++];
-            o.value = value; o.p = p;
-            if (!last) o.d_out = take(d.nR);
-        };
-        out(0, rhj_fold_factor{f.w[Pn], nullptr, nullptr}, -1);                        // the parent's new weight
-        for (int v = 0; v < q.nviews; ++v) {
-            if (value_of[v] >= 0)                    out(value_of[v], rhj_fold_factor{f.w[Pn], nullptr, nullptr}, v);     // a view coming from the child
-            else if (f.acc[Pn][v])                   out(0, rhj_fold_factor{f.acc[Pn][v], nullptr, nullptr}, v);          // a view the parent carried
-            else if (last && q.views[v].rel == Pn)   out(0, rhj_fold_factor{f.w[Pn], nullptr, R.column(q, Pn, q.views[v].col)}, v);   // a view on the root: lazy until now
-        }
+        const FoldItem it = fold_item(R, q, s, f, k, [&](int, uint64_t rows) { return take(rows); });
         if (!last) {                                      // (a round's steps of one query share no node: what a step leaves is read by later rounds only)
-            f.w[Pn] = d.outs[0].d_out;
-            for (int o = 1; o < d.nouts; ++o) f.acc[Pn][os.view[(size_t)o]] = d.outs[o].d_out;
+            f.w[step.parent] = it.outs[0].d_out;
+            for (int o = 1; o < it.nouts; ++o) f.acc[step.parent][it.view[(size_t)o]] = it.outs[o].d_out;
         }
-        rd.tiles[step.nkeys > 1] += jsum_tiles(d.nR) + jsum_tiles(d.nS);
-        if (step.nkeys == 1) {
-            os.kind = 0; os.at = rd.fd.size();
-            rd.bytes += tbatch_table_bytes(d);
-            rd.fd.push_back(d);
+        rd.tiles[it.nkeys > 1] += jsum_tiles(it.nR) + jsum_tiles(it.nS);
+        OwStep os = {0, step.round, it.nkeys > 1, 0, last, it.view};
+        if (it.nkeys == 1) {
+            os.at = rd.fd.size(); fold_desc(rd.fd.emplace_back(), it, s);
+            rd.bytes += tbatch_table_bytes(rd.fd.back());
         } else {
-            rhj_join_foldk_desc t = {};
-            t.nkeys = step.nkeys;
-            for (int w = 0; w < step.nkeys; ++w) { t.d_colR[w] = keyR[w]; t.d_colS[w] = keyS[w]; }
-            t.nR = d.nR; t.nS = d.nS;
-            t.nvalues = d.nvalues; t.nouts = d.nouts;
-            memcpy(t.values, d.values, sizeof(t.values)); memcpy(t.outs, d.outs, sizeof(t.outs));
-            os.kind = 1; os.at = rd.kd.size();
-            rd.bytes += tbatch_table_bytes(t);
-            rd.kd.push_back(t);
+            os.at = rd.kd.size(); fold_desc(rd.kd.emplace_back(), it, s);
+            rd.bytes += tbatch_table_bytes(rd.kd.back());
         }
         P.steps.push_back(os);
     }
@@ -3757,9 +3681,9 @@ static int ow_run(QueryRun &R, OwProgram &P)
         for (size_t k = 0; k < P.rounds[r].fd.size(); ++k) tbatch_take(P.rounds[r].fd[k], back + wfold[r] + k * FOLD_WORDS);
         for (size_t k = 0; k < P.rounds[r].kd.size(); ++k) tbatch_take(P.rounds[r].kd[k], back + wfoldk[r] + k * FOLDK_WORDS);
     }
-    const auto outs_of = [&](const OwStep &s) { return s.kind ? P.rounds[(size_t)s.round].kd[s.at].outs : P.rounds[(size_t)s.round].fd[s.at].outs; };
+    const auto outs_of = [&](const OwStep &s) { return s.kind ? fold_outs(P.rounds[(size_t)s.round].kd[s.at]) : fold_outs(P.rounds[(size_t)s.round].fd[s.at]); };
     for (const OwStep &s : P.steps)
-        if (outs_of(s)[0].total == 0) dead[s.who] = 1;
+        if (outs_of(s).outs[0].total == 0) dead[s.who] = 1;
     for (size_t k = 0; k < np; ++k) {
         if (!P.pfinal[k] || dead[P.pwho[k]]) continue;
         rhj_query_desc &q = R.queries[P.who[P.pwho[k]]];
@@ -3769,8 +3693,7 @@ static int ow_run(QueryRun &R, OwProgram &P)
     for (const OwStep &s : P.steps) {
         if (!s.last || dead[s.who]) continue;
         rhj_query_desc &q = R.queries[P.who[s.who]];
-        const rhj_fold_out *outs = outs_of(s);
-        const int nouts = s.kind ? P.rounds[(size_t)s.round].kd[s.at].nouts : P.rounds[(size_t)s.round].fd[s.at].nouts;
+        const auto [outs, nouts] = outs_of(s);
         q.rows = outs[0].total;
         for (int o = 1; o < nouts; ++o) q.sums[s.view[(size_t)o]] = outs[o].total;
     }
@@ -3794,17 +3717,25 @@ static int query_one_wait(QueryRun &R)
     return P.who.empty() ? 0 : ow_run(R, P);
 }
 
+// whether every binding is small enough for a fold's side: fewer than 2^32 rows
+static bool fold_sides_fit(const rhj_query_desc &q, const rhj_device_relation *rels)
+{
+    for (int b = 0; b < q.nrels; ++b) if (rels[q.rels[b]].num_tuples >= JSUM_MAX_ROWS) return false;
+    return true;
+}
+
+// whether every merged node (a binding not its node's name lies in one) has few enough rows to be parked for the nodes' pass
+static bool fold_nodes_fit(const rhj_query_desc &q, const QueryState &s)
+{
+    for (int b = 0; b < q.nrels; ++b) if (s.node[b] != b && s.rows[s.node[b]] >= g_query_fold_node_rows) return false;
+    return true;
+}
+
 static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     if (n == 0) return 0;
     if (!queries || (nrel > 0 && !rels)) return -1;
-    memset(&g_query_info, 0, sizeof(g_query_info));
-    memset(&g_query_sum_info, 0, sizeof(g_query_sum_info));
-    memset(&g_query_fold_info, 0, sizeof(g_query_fold_info));
-    memset(&g_query_foldk_info, 0, sizeof(g_query_foldk_info));
-    memset(&g_query_fold_self_info, 0, sizeof(g_query_fold_self_info));
-    memset(&g_query_fold_nodes_info, 0, sizeof(g_query_fold_nodes_info));
-    memset(&g_query_one_wait_info, 0, sizeof(g_query_one_wait_info));
+    query_infos_clear();
     std::vector<char> one_wait;
     const bool hand_over = g_query_fold && g_query_fold_keys && g_query_fold_self && g_query_fold_nodes;
     std::vector<int> park;
@@ -3816,15 +3747,14 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
         const int lv = query_levels(&queries[i], nrel, rels, nullptr);
         queries[i].rc = lv < 0 ? -3 : 0;
         invalid |= lv < 0;
-        const int how = query_fold_how(&queries[i], nrel, rels, lv);
+        const int how = query_fold_how(&queries[i], lv);
         int prefix = 0;                                   // of a query none of the three plans takes: the levels before its nodes fold
         if (!how && hand_over && lv >= 0) {
             rhj_foldn_plan plan;
             if (query_foldn_plan(&queries[i], nrel, rels, &plan) == 1) prefix = plan.levels;         // (>= 1: at 0 levels query_folds_plan took it)
         }
         if (how || prefix) {
-            bool fits = true;                             // a fold's sides have fewer than 2^32 rows
-            for (int b = 0; b < queries[i].nrels; ++b) fits &= rels[queries[i].rels[b]].num_tuples < JSUM_MAX_ROWS;
+            const bool fits = fold_sides_fit(queries[i], rels);
             folds[i] = !fits ? 0 : how ? (char)how : 4;
             if (how && g_query_fold_one_wait && query_one_wait_plan(&queries[i], nrel, rels) == 1) {
                 if (one_wait.empty()) one_wait.assign(n, 0);
@@ -3863,10 +3793,7 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
             // fold's side: such a query stays on the levels to its end
             for (uint64_t i = 0; i < n && !R.park.empty(); ++i) {
                 if (R.park[i] != l + 1 || !R.st[i].alive) continue;
-                const QueryState &s = R.st[i];
-                bool fits = true;
-                for (int b = 0; b < queries[i].nrels; ++b) fits &= s.node[b] == b || s.rows[s.node[b]] < g_query_fold_node_rows;     // (a binding not its node's name: a merged node)
-                if (fits) continue;
+                if (fold_nodes_fit(queries[i], R.st[i])) continue;
                 R.park[i] = 0; R.folds[i] = 0;
                 if (queries[i].njoins > maxl) {
                     maxl = queries[i].njoins;
