@@ -213,7 +213,8 @@ int rhj_filter_eq2_batch_device(rhj_eq2_desc *items, uint64_t n);
  * The whole batch is validated before a device is touched: nrels outside 1..RHJ_QUERY_MAX_RELS, nviews outside
  * 1..RHJ_QUERY_MAX_VIEWS, a negative count, a binding, relation or column index out of range, a used column that is NULL in a
  * relation with rows, an operator outside '<', '>', '=', more than RHJ_FILTER_MAX_TERMS filters on one binding, or bindings
- * that are not all in one node after the last predicate (a cross product, CartesianInterResults: not executed here) give that
+ * that are not all in one node after the last predicate (a cross product, CartesianInterResults: taken only with
+ * rhj_set_query_products on, below, and then as the product of its components' answers, never materialised) give that
  * query rc -3; then nothing runs, no sums or rows are written and the call returns -3.  n == 0 returns 0.  Otherwise 0, or a
  * negative value on a HIP error.  The call holds the library lock throughout and keeps its intermediate vectors in workspace
  * buffers that grow and stay (rhj_release() frees them).  rhj_last_stats() afterwards: n_r the queries, matches the final rows
@@ -651,6 +652,37 @@ void rhj_set_query_fold_one_wait_rows(uint64_t limit);
 int rhj_query_one_wait_plan(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels);
 typedef struct rhj_query_batch_one_wait_info { uint32_t queries, programs, pred_items, fold_items, foldk_items, rounds, launches, memsets, waits; } rhj_query_batch_one_wait_info;
 const rhj_query_batch_one_wait_info *rhj_query_batch_last_one_wait_info(void);
+
+/* The components of one query, a pure function that needs no device: rhj_query_levels' validation without its last rule (all
+ * bindings in one node after the last predicate).  Returns the number of components (1 where rhj_query_levels accepts the query,
+ * more for a cross product, at most RHJ_QUERY_MAX_RELS), or -3 for exactly the other queries rhj_query_levels refuses.  comp[b],
+ * when given, is the component of binding b; components are numbered 0, 1, ... in the order of their lowest binding.  rels may be
+ * NULL as there. */
+int rhj_query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp);
+
+/* rhj_query_batch_device with the switch on (default off; environment RHJ_QUERY_PRODUCTS=1): a query of k > 1 components, a
+ * CROSS PRODUCT, is accepted.  The product is never built.  With T_c the rows of component c alone and S_v the
+ * sum of view v over the component c(v) its binding lies in,
+ *     rows    = product over c of T_c                        (mod 2^64)
+ *     sums[v] = S_v * product over c != c(v) of T_c          (mod 2^64)
+ * which is what wrap-around sums over CartesianInterResults' n1 * n2 * ... rows give.  The caller's batch is validated first
+ * (rhj_query_components: -3 and nothing ran for what that refuses; rc is set on the caller's descriptors).  If it holds such a
+ * query, the call runs an internal batch of its own in ONE pass through the stages above: every one-component query unchanged, and
+ * every other query as k component queries in its place - the component's bindings renumbered 0.. in ascending order, its filters,
+ * predicates and views in their order, and for a component without a view one stand-in view (the first column its first predicate
+ * names, else its first filter's, else the relation's first column) whose sum is not read.  A component that is one binding with
+ * no filter, no view and no column has its relation's rows and takes no place in that batch.  All components of all queries share
+ * the filter batch, the levels, the fold rounds and the programs, each on the route the other switches give a query of its
+ * shape; the products are taken on the host.  rows == 0 reads as empty, as everywhere: when a component is empty, or the
+ * product is 0 modulo 2^64 (2^22 * 2^22 * 2^20 rows), rows and every sum are 0.  The one-component queries of such a batch get bit
+ * for bit the answers of a call without the others.  A batch without a cross product runs exactly as with the switch off.
+ * rhj_query_levels and the plan functions do not look at the switch: they keep -3 for a cross product.
+ * rhj_query_batch_last_products_info(): the caller's queries of several components in the last rhj_query_batch_device, and
+ * their components (zero with the switch off or none in the batch); every other info struct then counts the internal batch
+ * (fold_queries counts components).  rhj_last_stats(): n_r the caller's queries, matches the sum of their rows, reserved 10. */
+void rhj_set_query_products(int on);
+typedef struct { uint32_t product_queries, components; } rhj_query_batch_products_info;
+const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void);
 
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);

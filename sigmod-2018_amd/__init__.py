@@ -47,6 +47,7 @@ INTER_SYMBOLS = [
     "rhj_fold_self_batch_device", "rhj_query_folds_plan", "rhj_set_query_fold_self", "rhj_query_batch_last_fold_self_info",
     "rhj_join_foldn_batch_device", "rhj_query_foldn_plan", "rhj_set_query_fold_nodes", "rhj_set_query_fold_node_rows", "rhj_query_batch_last_fold_nodes_info",
     "rhj_fold_pred_batch_device", "rhj_query_one_wait_plan", "rhj_set_query_fold_one_wait", "rhj_set_query_fold_one_wait_rows", "rhj_query_batch_last_one_wait_info",
+    "rhj_query_components", "rhj_set_query_products", "rhj_query_batch_last_products_info",
 ]
 
 
@@ -356,6 +357,30 @@ class QueryBatchOneWaitInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class QueryBatchProductsInfo(C.Structure):
+    """rhj_query_batch_products_info (include/rhj_inter.h): the queries of several components (cross products) the last
+    rhj_query_batch_device took, and their components"""
+    _fields_ = [("product_queries", C.c_uint32), ("components", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def query_components(lib, query, nrel=None):
+    """rhj_query_components on one query (relations, joins, filters, views): [component of every binding], the components
+    numbered 0, 1, ... in the order of their lowest binding (one component unless the query is a cross product); ValueError on -3"""
+    arr, keep = query_descs([query])
+    comp = (C.c_int * QUERY_MAX_RELS)()
+    rc = lib.rhj_query_components(C.byref(arr[0]), nrel if nrel is not None else max(query[0]) + 1, None, comp)
+    del keep
+    if rc == -3:
+        raise ValueError("rhj_query_components refused the query")
+    got = list(comp[:len(query[0])])
+    if rc != max(got) + 1:
+        raise RuntimeError("rhj_query_components returned %d for the components %s" % (rc, got))
+    return got
+
+
 def query_one_wait_plan(lib, query, rels=None, nrel=None):
     """rhj_query_one_wait_plan on one query (relations, joins, filters, views): 1 when it takes the one-wait route under the
     switches and the row limit as they stand, 0 when it does not; ValueError on -3.  rels: a DeviceRelation array (the rule reads
@@ -408,6 +433,7 @@ class QueryInfo(dict):
     fold_self_info = None
     fold_nodes_info = None
     one_wait_info = None
+    products_info = None
 
 
 def query_descs(queries):
@@ -575,6 +601,11 @@ def load_library(path=None):
         L.rhj_set_query_fold_one_wait_rows.argtypes = [C.c_uint64]
         L.rhj_set_query_fold_one_wait_rows.restype = None
         L.rhj_query_batch_last_one_wait_info.restype = C.POINTER(QueryBatchOneWaitInfo)
+    if hasattr(L, "rhj_query_components"):            # (A/B runs load earlier builds through this module too)
+        L.rhj_query_components.argtypes = [C.POINTER(QueryDesc), C.c_int, C.POINTER(DeviceRelation), C.POINTER(C.c_int)]
+        L.rhj_set_query_products.argtypes = [C.c_int]
+        L.rhj_set_query_products.restype = None
+        L.rhj_query_batch_last_products_info.restype = C.POINTER(QueryBatchProductsInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -1022,6 +1053,12 @@ class RHJ:
         """a query takes the one-wait route only while every binding's relation has at most this many rows (default 4096)"""
         self.lib.rhj_set_query_fold_one_wait_rows(int(limit))
 
+    def set_query_products(self, on):
+        """query_batch_device takes a query whose bindings end in several components, a cross product, as one query per
+        component in the same batch and multiplies their rows and sums on the host; nothing of the product is built (default
+        off: such a query is refused)"""
+        self.lib.rhj_set_query_products(1 if on else 0)
+
     def set_query_fold_self(self, on):
         """with set_query_fold: the queries that fold once their one-binding predicates are 0/1 factors on a binding's weight and
         their implied predicates are dropped fold too, queries without a join among them (default off)"""
@@ -1149,6 +1186,8 @@ class RHJ:
         info.fold_nodes_info = self.lib.rhj_query_batch_last_fold_nodes_info().contents.as_dict()
         if hasattr(self.lib, "rhj_query_batch_last_one_wait_info"):
             info.one_wait_info = self.lib.rhj_query_batch_last_one_wait_info().contents.as_dict()
+        if hasattr(self.lib, "rhj_query_batch_last_products_info"):
+            info.products_info = self.lib.rhj_query_batch_last_products_info().contents.as_dict()
         return res, info
 
     def column_stats_batch_device(self, cols, with_info=False):

@@ -174,6 +174,7 @@ uint64_t g_query_fold_node_rows = 1ull << 32;            // a query hands over o
 int g_query_fold_one_wait = 0;       // 1: with g_query_fold, the folding queries over relations of 1..g_query_fold_one_wait_rows rows run as fold programs with one wait each, their filters 0/1 weights (rhj_set_query_fold_one_wait, env RHJ_QUERY_FOLD_ONE_WAIT)
 uint64_t g_query_fold_one_wait_rows = 4096;              // the most rows of a relation on that route (rhj_set_query_fold_one_wait_rows): the largest size at which whole relations under weights measured no slower than hit lists
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
+int g_query_products = 0;            // 1: rhj_query_batch_device takes a query whose bindings end in several nodes (a cross product) as one query per component and multiplies their answers on the host (rhj_set_query_products, env RHJ_QUERY_PRODUCTS)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
 struct EnvDefaults {
@@ -208,6 +209,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_FOLD_SELF"))) g_query_fold_self = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_NODES"))) g_query_fold_nodes = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_ONE_WAIT"))) g_query_fold_one_wait = atoi(e) != 0;
+        if ((e = getenv("RHJ_QUERY_PRODUCTS"))) g_query_products = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -2639,7 +2641,9 @@ static void query_release()
     g_qb.fold.clear();
 }
 
-static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds)
+// query_check is the validation of one query but for its last rule (all bindings in one node): njoins or -3, and node[b] the
+// node of binding b after the last predicate (two merged nodes are the A side's).
+static int query_check(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds, int *node)
 {
     if (!q || q->nrels < 1 || q->nrels > RHJ_QUERY_MAX_RELS || !q->rels || q->nviews < 1 || q->nviews > RHJ_QUERY_MAX_VIEWS || !q->views) return -3;
     if (q->nfilters < 0 || q->njoins < 0 || (q->nfilters && !q->filters) || (q->njoins && !q->joins)) return -3;
@@ -2658,7 +2662,6 @@ static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_rela
         const rhj_query_filter &p = q->filters[f];
         if (!col_ok(p.rel, p.col) || op_code(p.op) < 0 || ++per_binding[p.rel] > RHJ_FILTER_MAX_TERMS) return -3;
     }
-    int node[RHJ_QUERY_MAX_RELS];
     for (int b = 0; b < q->nrels; ++b) node[b] = b;
     for (int l = 0; l < q->njoins; ++l) {
         const rhj_query_join &p = q->joins[l];
@@ -2668,8 +2671,29 @@ static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_rela
         for (int x = 0; x < q->nrels; ++x) if (node[x] == nb) node[x] = na;      // the two nodes merge into A's
     }
     for (int v = 0; v < q->nviews; ++v) if (!col_ok(q->views[v].rel, q->views[v].col)) return -3;
-    for (int b = 1; b < q->nrels; ++b) if (node[b] != node[0]) return -3;          // a cross product is not executed here
     return q->njoins;
+}
+
+static int query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds)
+{
+    int node[RHJ_QUERY_MAX_RELS];
+    const int lv = query_check(q, nrel, rels, kinds, node);
+    if (lv < 0) return -3;
+    for (int b = 1; b < q->nrels; ++b) if (node[b] != node[0]) return -3;          // a cross product is not executed here (query_products below runs it as its components)
+    return lv;
+}
+
+// The components of one query (rhj_query_components): query_check's nodes numbered 0, 1, ... in the order of their lowest binding.
+static int query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp)
+{
+    int node[RHJ_QUERY_MAX_RELS], id[RHJ_QUERY_MAX_RELS], k = 0;
+    if (query_check(q, nrel, rels, nullptr, node) < 0) return -3;
+    for (int b = 0; b < q->nrels; ++b) id[b] = -1;
+    for (int b = 0; b < q->nrels; ++b) {
+        if (id[node[b]] < 0) id[node[b]] = k++;
+        if (comp) comp[b] = id[node[b]];
+    }
+    return k;
 }
 
 struct QueryState {
@@ -2712,10 +2736,11 @@ rhj_query_batch_foldk_info g_query_foldk_info = {};
 rhj_query_batch_fold_self_info g_query_fold_self_info = {};
 rhj_query_batch_fold_nodes_info g_query_fold_nodes_info = {};
 rhj_query_batch_one_wait_info g_query_one_wait_info = {};
+rhj_query_batch_products_info g_query_products_info = {};
 static void query_infos_clear()
 {
     g_query_info = {}; g_query_sum_info = {}; g_query_fold_info = {}; g_query_foldk_info = {};
-    g_query_fold_self_info = {}; g_query_fold_nodes_info = {}; g_query_one_wait_info = {};
+    g_query_fold_self_info = {}; g_query_fold_nodes_info = {}; g_query_one_wait_info = {}; g_query_products_info = {};
 }
 
 struct QueryRun {                                         // what the stages of one call share
@@ -3818,6 +3843,134 @@ static int query_batch(const rhj_device_relation *rels, int nrel, rhj_query_desc
     return 0;
 }
 
+// rhj_set_query_products: a query whose bindings end in k > 1 nodes is the cross product of its k components, and the batch
+// answers in sums and a row count alone, so nothing of the product is ever built: with T_c the rows of
+// component c and S_v the sum of view v over its own component c(v),
+//     rows = product of the T_c          sums[v] = S_v * product of the T_c, c != c(v)          (mod 2^64)
+// Each component is a query of its own that query_batch takes on whatever route the switches give it.  So the caller's batch
+// is validated here (query_components; -3 and nothing ran, as always), rewritten into an internal batch in which every such
+// query stands as its k components, run by ONE query_batch call, and the answers are multiplied on the host.  A batch without
+// such a query goes to query_batch as it came.
+struct QueryPart {                                        // what one component's descriptor points to
+    int                           rels[RHJ_QUERY_MAX_RELS];
+    rhj_query_view                views[RHJ_QUERY_MAX_VIEWS];
+    std::vector<rhj_query_filter> filters;
+    std::vector<rhj_query_join>   joins;
+};
+struct QueryProduct {                                     // a caller's query of k > 1 components
+    uint64_t query;
+    int      k, comp[RHJ_QUERY_MAX_RELS];                 // binding -> component
+    int64_t  item[RHJ_QUERY_MAX_RELS];                    // component -> its query of the internal batch; -1: it needed no device work ...
+    uint64_t rows[RHJ_QUERY_MAX_RELS];                    // ... and has this many rows
+};
+
+// the query of component c of q, its bindings renumbered 0.. in ascending order, everything else in its order; false when the
+// component has nothing a device could be asked for: one binding, no filter, no view and no column to stand in for one
+static bool query_component(const rhj_query_desc &q, const int *comp, int c, const rhj_device_relation *rels, QueryPart &P,
+                            rhj_query_desc &out)
+{
+    int id[RHJ_QUERY_MAX_RELS], nb = 0, nv = 0;
+    for (int b = 0; b < q.nrels; ++b) if (comp[b] == c) { id[b] = nb; P.rels[nb++] = q.rels[b]; }
+    for (int f = 0; f < q.nfilters; ++f) {
+        const rhj_query_filter &p = q.filters[f];
+        if (comp[p.rel] == c) P.filters.push_back({id[p.rel], p.col, p.op, p.value});
+    }
+    for (int l = 0; l < q.njoins; ++l) {
+        const rhj_query_join &p = q.joins[l];
+        if (comp[p.relA] == c) P.joins.push_back({id[p.relA], p.colA, id[p.relB], p.colB});      // (relB is in the same component: the predicate made it so)
+    }
+    for (int v = 0; v < q.nviews; ++v) if (comp[q.views[v].rel] == c) P.views[nv++] = {id[q.views[v].rel], q.views[v].col};
+    if (nv == 0) {                                        // a stand-in view, for nviews >= 1: its sum is not read
+        if (!P.joins.empty()) P.views[nv++] = {P.joins[0].relA, P.joins[0].colA};
+        else if (!P.filters.empty()) P.views[nv++] = {P.filters[0].rel, P.filters[0].col};
+        else {                                            // (no predicate: the component is one binding)
+            const rhj_device_relation &R = rels[P.rels[0]];
+            for (uint64_t col = 0; col < R.num_columns && nv == 0; ++col)
+                if (R.num_tuples == 0 || R.d_columns[col]) P.views[nv++] = {0, (int)col};
+            if (nv == 0) return false;
+        }
+    }
+    out = rhj_query_desc{};
+    out.nrels = nb; out.rels = P.rels;
+    out.nfilters = (int)P.filters.size(); out.filters = P.filters.empty() ? nullptr : P.filters.data();
+    out.njoins = (int)P.joins.size(); out.joins = P.joins.empty() ? nullptr : P.joins.data();
+    out.nviews = nv; out.views = P.views;
+    return true;
+}
+
+static int query_products(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
+{
+    if (n == 0 || !queries || (nrel > 0 && !rels)) return query_batch(rels, nrel, queries, n);
+    query_infos_clear();
+    bool invalid = false;                                 // the caller's batch is validated before anything else
+    uint64_t nprod = 0, ncomp = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int k = query_components(&queries[i], nrel, rels, nullptr);
+        queries[i].rc = k < 0 ? -3 : 0;
+        invalid |= k < 0;
+        if (k > 1) { ++nprod; ncomp += (uint64_t)k; }
+    }
+    if (invalid) return -3;
+    if (nprod == 0) return query_batch(rels, nrel, queries, n);
+    // the internal batch, in the caller's order: a query of one component as it is, any other as its components
+    std::vector<rhj_query_desc> iq;
+    std::vector<uint64_t>       at(n);                    // a one-component query -> its place in iq
+    std::vector<QueryPart>      parts(ncomp);             // (sized once: the descriptors point into them)
+    std::vector<QueryProduct>   prods(nprod);
+    iq.reserve(n - nprod + ncomp);
+    uint64_t np = 0, npart = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const rhj_query_desc &q = queries[i];
+        int comp[RHJ_QUERY_MAX_RELS];
+        const int k = query_components(&q, nrel, rels, comp);
+        if (k == 1) { at[i] = iq.size(); iq.push_back(q); continue; }
+        QueryProduct &X = prods[np++];
+        X.query = i; X.k = k;
+        memcpy(X.comp, comp, sizeof(comp));
+        for (int c = 0; c < X.k; ++c) {
+            rhj_query_desc d;
+            if (query_component(q, X.comp, c, rels, parts[npart++], d)) { X.item[c] = (int64_t)iq.size(); iq.push_back(d); continue; }
+            X.item[c] = -1;
+            for (int b = 0; b < q.nrels; ++b) if (X.comp[b] == c) X.rows[c] = rels[q.rels[b]].num_tuples;
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) { memset(queries[i].sums, 0, sizeof(queries[i].sums)); queries[i].rows = 0; }
+    const int rc = query_batch(rels, nrel, iq.data(), iq.size());       // (iq is not empty: the component of a query's first view has a query)
+    g_query_products_info.product_queries = (uint32_t)nprod;
+    g_query_products_info.components = (uint32_t)ncomp;
+    if (rc) return rc;
+    // the answers.  A product of 0 rows, a component's or the wrapped product's, reads as empty: rows 0 and sums 0, the batch's rule.
+    uint64_t total = 0;
+    np = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        rhj_query_desc &q = queries[i];
+        if (np == nprod || prods[np].query != i) {
+            memcpy(q.sums, iq[at[i]].sums, sizeof(q.sums));
+            q.rows = iq[at[i]].rows;
+            total += q.rows;
+            continue;
+        }
+        QueryProduct &X = prods[np++];
+        uint64_t rows = 1;
+        for (int c = 0; c < X.k; ++c) {
+            if (X.item[c] >= 0) X.rows[c] = iq[(size_t)X.item[c]].rows;
+            rows *= X.rows[c];
+        }
+        if (rows == 0) continue;
+        int seen[RHJ_QUERY_MAX_RELS] = {};                // component -> its views taken so far: view v is its component's next one
+        for (int v = 0; v < q.nviews; ++v) {
+            const int c = X.comp[q.views[v].rel];
+            uint64_t s = iq[(size_t)X.item[c]].sums[seen[c]++];
+            for (int o = 0; o < X.k; ++o) if (o != c) s *= X.rows[o];
+            q.sums[v] = s;
+        }
+        q.rows = rows;
+        total += rows;
+    }
+    g.stats.n_r = n; g.stats.matches = total;             // the caller's batch, not the internal one: its queries and their rows
+    return 0;
+}
+
 // stable selection of the tuples whose bucket lies in [bucket_lo, bucket_hi) (on the calling thread's context, no API lock)
 static int select_range(const rhj_tuple *d_in, uint64_t n, uint32_t bucket_lo, uint32_t bucket_hi, rhj_tuple *d_out, uint64_t capacity,
                         uint64_t *count)
@@ -4359,8 +4512,11 @@ const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void) { return &
 int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     RhjApiLock api_lock;
-    return query_batch(rels, nrel, queries, n);
+    return g_query_products ? query_products(rels, nrel, queries, n) : query_batch(rels, nrel, queries, n);
 }
+int rhj_query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp) { return query_components(q, nrel, rels, comp); }
+void rhj_set_query_products(int on) { RhjApiLock api_lock; g_query_products = on != 0; }
+const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void) { return &g_query_products_info; }
 int rhj_query_levels(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *kinds) { return query_levels(q, nrel, rels, kinds); }
 const rhj_query_batch_info *rhj_query_batch_last_info(void) { return &g_query_info; }
 const rhj_query_batch_sum_info *rhj_query_batch_last_sum_info(void) { return &g_query_sum_info; }
