@@ -684,6 +684,32 @@ void rhj_set_query_products(int on);
 typedef struct { uint32_t product_queries, components; } rhj_query_batch_products_info;
 const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void);
 
+/* The four table batches with this switch on (rhj_join_sum_batch_device, rhj_join_fold_batch_device, rhj_join_foldk_batch_device,
+ * rhj_join_foldn_batch_device; environment RHJ_FOLD_COMBINE=0|1; DEFAULT ON: the uniform cases measured within the spread of the
+ * build before it): a WORKGROUP-LEVEL COMBINER in their add launches (csrc/rhj_slot_combine.hip.h).
+ * Without it every row sends one device-scope atomic per value into the slot of its key, and one address takes about 80 adds a
+ * microsecond: a side of few distinct keys costs the multiplicity of its hottest key.  With it the adds of a 2048-row tile to one
+ * slot meet in LDS (2048 entries, a row's entry the low bits of its slot index; a row that finds another slot in its entry adds
+ * by itself, as before) and ONE atomic per (tile, slot, value) goes to the table.  A tile with fewer than 64 rows that found
+ * their slot's entry taken by their own slot adds per row, as with the switch off.  Sums modulo 2^64 and counts do not depend on
+ * the order of their terms: every output vector, total, match count and sum is bit for bit the same under both settings.  The
+ * switch reaches the batches wherever they are issued: the four entry points, the fold route of rhj_query_batch_device and its
+ * one-wait programs.  Tables, chunks, launch counts, path ids and every struct above are as with the switch off.
+ *
+ * rhj_table_batch_last_combine_info(): `tiles` the add launches' tiles (a fold's child-side tiles; both count launches' of a join
+ * sum), `combined_tiles` those that combined, `slot_adds` the device-scope adds into table slots that were issued (owners' sums,
+ * rows that went by themselves, a non-combining tile's adds; adds of 0 are never issued, and the empty key's words are no slot).
+ * Reset on entry to each of the four batches and to rhj_query_batch_device, whose inner table batches sum into it; all zero with
+ * the switch off, and after a batch that was refused (-3). */
+void rhj_set_fold_combine(int on);
+int rhj_get_fold_combine(void);          /* the switch as it stands: the default, the environment's value or the last call's */
+typedef struct {
+    uint64_t tiles;           /* add-launch tiles with the switch on */
+    uint64_t combined_tiles;
+    uint64_t slot_adds;
+} rhj_table_batch_combine_info;
+const rhj_table_batch_combine_info *rhj_table_batch_last_combine_info(void);
+
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);
 int rhj_resident_result(const rhj_result *res);

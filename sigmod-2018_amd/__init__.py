@@ -48,6 +48,7 @@ INTER_SYMBOLS = [
     "rhj_join_foldn_batch_device", "rhj_query_foldn_plan", "rhj_set_query_fold_nodes", "rhj_set_query_fold_node_rows", "rhj_query_batch_last_fold_nodes_info",
     "rhj_fold_pred_batch_device", "rhj_query_one_wait_plan", "rhj_set_query_fold_one_wait", "rhj_set_query_fold_one_wait_rows", "rhj_query_batch_last_one_wait_info",
     "rhj_query_components", "rhj_set_query_products", "rhj_query_batch_last_products_info",
+    "rhj_set_fold_combine", "rhj_get_fold_combine", "rhj_table_batch_last_combine_info",
 ]
 
 
@@ -366,6 +367,16 @@ class QueryBatchProductsInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TableBatchCombineInfo(C.Structure):
+    """rhj_table_batch_combine_info (include/rhj_inter.h): the add launches' tiles of the last table batch (or of the table
+    batches inside the last rhj_query_batch_device) with rhj_set_fold_combine on, those that combined, and the device-scope adds
+    into table slots they issued"""
+    _fields_ = [("tiles", C.c_uint64), ("combined_tiles", C.c_uint64), ("slot_adds", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def query_components(lib, query, nrel=None):
     """rhj_query_components on one query (relations, joins, filters, views): [component of every binding], the components
     numbered 0, 1, ... in the order of their lowest binding (one component unless the query is a cross product); ValueError on -3"""
@@ -606,6 +617,11 @@ def load_library(path=None):
         L.rhj_set_query_products.argtypes = [C.c_int]
         L.rhj_set_query_products.restype = None
         L.rhj_query_batch_last_products_info.restype = C.POINTER(QueryBatchProductsInfo)
+    if hasattr(L, "rhj_set_fold_combine"):            # (A/B runs load earlier builds through this module too)
+        L.rhj_set_fold_combine.argtypes = [C.c_int]
+        L.rhj_set_fold_combine.restype = None
+        L.rhj_get_fold_combine.restype = C.c_int
+        L.rhj_table_batch_last_combine_info.restype = C.POINTER(TableBatchCombineInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -1132,6 +1148,16 @@ class RHJ:
         for d, mine in zip(arr, places):
             res.append([(None if a is None else buf[a:a + d.nR] if isinstance(a, int) else a[:d.nR], d.outs[k].total) for k, a in enumerate(mine)])
         return (res, [arr[i].path for i in range(n)]) if with_info else res
+
+    def set_fold_combine(self, on):
+        """the add launches of the four table batches (join sums, folds, folds on tuple keys and on the keys of nodes), wherever
+        they are issued, combine a tile's adds to one table slot in LDS and send one atomic per (tile, slot, value) (default
+        on); every answer is bit for bit the same under both settings"""
+        self.lib.rhj_set_fold_combine(1 if on else 0)
+
+    def table_batch_last_combine_info(self):
+        """rhj_table_batch_last_combine_info() as a dict: tiles, combined_tiles, slot_adds (all 0 with set_fold_combine off)"""
+        return self.lib.rhj_table_batch_last_combine_info().contents.as_dict()
 
     def set_query_fold(self, on):
         """query_batch_device sums the queries whose join predicates form a tree over their bindings by rounds of weighted join

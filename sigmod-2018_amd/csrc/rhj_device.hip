@@ -174,6 +174,7 @@ uint64_t g_query_fold_node_rows = 1ull << 32;            // a query hands over o
 int g_query_fold_one_wait = 0;       // 1: with g_query_fold, the folding queries over relations of 1..g_query_fold_one_wait_rows rows run as fold programs with one wait each, their filters 0/1 weights (rhj_set_query_fold_one_wait, env RHJ_QUERY_FOLD_ONE_WAIT)
 uint64_t g_query_fold_one_wait_rows = 4096;              // the most rows of a relation on that route (rhj_set_query_fold_one_wait_rows): the largest size at which whole relations under weights measured no slower than hit lists
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
+int g_fold_combine = 1;              // 1: the add launches of the four table batches combine a tile's adds to one slot in LDS and send one atomic per (tile, slot, value) (rhj_slot_combine.hip.h; rhj_set_fold_combine, env RHJ_FOLD_COMBINE)
 int g_query_products = 0;            // 1: rhj_query_batch_device takes a query whose bindings end in several nodes (a cross product) as one query per component and multiplies their answers on the host (rhj_set_query_products, env RHJ_QUERY_PRODUCTS)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -210,6 +211,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_FOLD_NODES"))) g_query_fold_nodes = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_FOLD_ONE_WAIT"))) g_query_fold_one_wait = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_PRODUCTS"))) g_query_products = atoi(e) != 0;
+        if ((e = getenv("RHJ_FOLD_COMBINE"))) g_fold_combine = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -2215,10 +2217,31 @@ template <class D> static inline bool tbatch_sides_valid(const D &q) { return !(
 // zeroed and taken, a table's bytes, how a descriptor is filled and what tiles the item adds to the three launches, the three
 // kernels, the path id, the noun of the error text, and whether the statistics count matches.
 template <class D> struct tbatch_dev;
-template <> struct tbatch_dev<rhj_join_sum_desc> { using type = JoinSumDesc; static constexpr size_t words = JSUM_WORDS; };
-template <> struct tbatch_dev<rhj_join_fold_desc> { using type = JoinFoldDesc; static constexpr size_t words = FOLD_WORDS; };
-template <> struct tbatch_dev<rhj_join_foldk_desc> { using type = JoinFoldKDesc; static constexpr size_t words = FOLDK_WORDS; };
-template <> struct tbatch_dev<rhj_join_foldn_desc> { using type = JoinFoldNDesc; static constexpr size_t words = FOLDK_WORDS; };
+template <> struct tbatch_dev<rhj_join_sum_desc> { using type = JoinSumDesc; static constexpr size_t words = JSUM_WORDS; static constexpr bool first_adds = true; };
+template <> struct tbatch_dev<rhj_join_fold_desc> { using type = JoinFoldDesc; static constexpr size_t words = FOLD_WORDS; static constexpr bool first_adds = false; };
+template <> struct tbatch_dev<rhj_join_foldk_desc> { using type = JoinFoldKDesc; static constexpr size_t words = FOLDK_WORDS; static constexpr bool first_adds = false; };
+template <> struct tbatch_dev<rhj_join_foldn_desc> { using type = JoinFoldNDesc; static constexpr size_t words = FOLDK_WORDS; static constexpr bool first_adds = false; };
+static_assert(JSUM_W_COMBINE + COMBINE_WORDS == JSUM_WORDS && FOLD_W_COMBINE + COMBINE_WORDS == FOLD_WORDS && FOLDK_W_COMBINE + COMBINE_WORDS == FOLDK_WORDS,
+              "the combiner's counters are the last words of an item (tbatch_combine_take)");
+
+// The combiner of the add launches (rhj_slot_combine.hip.h).  g_fold_combine goes into every device descriptor
+// (tbatch_fill) and sizes the add launches' LDS (tbatch_launch).  g_combine_info sums, over the table batches of one public call
+// (the four entry points reset it, and rhj_query_batch_device does for the batches inside it): the add launches' tiles, taken
+// from the launch counts, and the two counters every item brings back in its last two words.  All zero with the switch off.
+rhj_table_batch_combine_info g_combine_info = {};
+static inline size_t combine_lds_bytes(bool sums) { return !g_fold_combine ? 0 : sums ? sizeof(CombineLds<unsigned long long>) : sizeof(CombineLds<uint32_t>); }
+// a group of items' launches (t: their tiles in the three launches) and their words as copied back
+template <class D>
+static void tbatch_combine_take(const uint32_t (&t)[3], const unsigned long long *back, size_t ni)
+{
+    if (!g_fold_combine) return;
+    constexpr size_t WORDS = tbatch_dev<D>::words;
+    g_combine_info.tiles += t[1] + (tbatch_dev<D>::first_adds ? t[0] : 0u);
+    for (size_t k = 0; k < ni; ++k) {
+        g_combine_info.combined_tiles += back[k * WORDS + WORDS - COMBINE_WORDS + COMBINE_W_TILES];
+        g_combine_info.slot_adds += back[k * WORDS + WORDS - COMBINE_WORDS + COMBINE_W_ADDS];
+    }
+}
 
 static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
@@ -2270,6 +2293,7 @@ static void tbatch_common(const D &q, unsigned long long *table, unsigned long l
     d.build = jsum_build_side(q.nR, q.nS);
     d.log2_slots = jsum_log2_slots(d.n[d.build]);
     d.table = table; d.words = words;
+    d.combine = g_fold_combine;
 }
 
 // fills d and adds the item's tiles to the three launches' counts: the build side's, the other side's, both sides'
@@ -2311,6 +2335,7 @@ static void tbatch_fill(const rhj_join_foldk_desc &q, unsigned long long *table,
     d.log2_slots = jsum_log2_slots(d.n[d.build]);
     d.table = table; d.words = words;
     d.nkeys = q.nkeys;
+    d.combine = g_fold_combine;
     tbatch_fill_fold(q, d, t);
 }
 static void tbatch_fill(const rhj_join_foldn_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldNDesc &d, uint32_t (&t)[3])
@@ -2325,31 +2350,32 @@ static void tbatch_fill(const rhj_join_foldn_desc &q, unsigned long long *table,
     d.log2_slots = jsum_log2_slots(d.n[d.build]);
     d.table = table; d.words = words;
     d.nkeys = q.nkeys;
+    d.combine = g_fold_combine;
     tbatch_fill_fold(q, d, t);
 }
 
 static void tbatch_launch(const rhj_join_sum_desc &, const JoinSumDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
 {
-    RHJ_LAUNCH(k_jsum_insert, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
-    RHJ_LAUNCH(k_jsum_count, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_jsum_insert, dim3(t[0]), dim3(256), combine_lds_bytes(false), g.stream, dd, ts[0], ni);
+    RHJ_LAUNCH(k_jsum_count, dim3(t[1]), dim3(256), combine_lds_bytes(false), g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_jsum_sum, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
 static void tbatch_launch(const rhj_join_fold_desc &, const JoinFoldDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
 {
     if (t[0]) RHJ_LAUNCH(k_fold_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
-    RHJ_LAUNCH(k_fold_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_fold_add, dim3(t[1]), dim3(256), combine_lds_bytes(true), g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_fold_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
 static void tbatch_launch(const rhj_join_foldk_desc &, const JoinFoldKDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
 {
     if (t[0]) RHJ_LAUNCH(k_foldk_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
-    RHJ_LAUNCH(k_foldk_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_foldk_add, dim3(t[1]), dim3(256), combine_lds_bytes(true), g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_foldk_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
 static void tbatch_launch(const rhj_join_foldn_desc &, const JoinFoldNDesc *dd, uint32_t ni, uint32_t *const (&ts)[3], const uint32_t (&t)[3])
 {
     if (t[0]) RHJ_LAUNCH(k_foldn_claim, dim3(t[0]), dim3(256), 0, g.stream, dd, ts[0], ni);
-    RHJ_LAUNCH(k_foldn_add, dim3(t[1]), dim3(256), 0, g.stream, dd, ts[1], ni);
+    RHJ_LAUNCH(k_foldn_add, dim3(t[1]), dim3(256), combine_lds_bytes(true), g.stream, dd, ts[1], ni);
     RHJ_LAUNCH(k_foldn_apply, dim3(t[2]), dim3(256), 0, g.stream, dd, ts[2], ni);
 }
 
@@ -2417,6 +2443,7 @@ static int tbatch_chunk(D *items, const uint64_t *which, size_t lo, size_t hi, u
         tbatch_take(q, back + k * WORDS);
         q.path = tbatch_path(q);
     }
+    tbatch_combine_take<D>(t, back, ni);
     return 0;
 }
 
@@ -3705,6 +3732,8 @@ static int ow_run(QueryRun &R, OwProgram &P)
     for (size_t r = 0; r < nr; ++r) {
         for (size_t k = 0; k < P.rounds[r].fd.size(); ++k) tbatch_take(P.rounds[r].fd[k], back + wfold[r] + k * FOLD_WORDS);
         for (size_t k = 0; k < P.rounds[r].kd.size(); ++k) tbatch_take(P.rounds[r].kd[k], back + wfoldk[r] + k * FOLDK_WORDS);
+        tbatch_combine_take<rhj_join_fold_desc>(rp[r].t[0], back + wfold[r], P.rounds[r].fd.size());
+        tbatch_combine_take<rhj_join_foldk_desc>(rp[r].t[1], back + wfoldk[r], P.rounds[r].kd.size());
     }
     const auto outs_of = [&](const OwStep &s) { return s.kind ? fold_outs(P.rounds[(size_t)s.round].kd[s.at]) : fold_outs(P.rounds[(size_t)s.round].fd[s.at]); };
     for (const OwStep &s : P.steps)
@@ -4512,8 +4541,12 @@ const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void) { return &
 int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     RhjApiLock api_lock;
+    g_combine_info = {};
     return g_query_products ? query_products(rels, nrel, queries, n) : query_batch(rels, nrel, queries, n);
 }
+void rhj_set_fold_combine(int on) { RhjApiLock api_lock; g_fold_combine = on != 0; }
+int rhj_get_fold_combine(void) { return g_fold_combine; }
+const rhj_table_batch_combine_info *rhj_table_batch_last_combine_info(void) { return &g_combine_info; }
 int rhj_query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp) { return query_components(q, nrel, rels, comp); }
 void rhj_set_query_products(int on) { RhjApiLock api_lock; g_query_products = on != 0; }
 const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void) { return &g_query_products_info; }
@@ -4542,24 +4575,28 @@ int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_rela
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
+    g_combine_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
+    g_combine_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
+    g_combine_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
+    g_combine_info = {};
     return table_batch(items, n);
 }
 

@@ -29,7 +29,9 @@
 // one value or one output factor go out together, outside any per-lane branch (a row out of bounds reads position 0 and takes
 // no part); the values and the outputs are looped over one at a time, so the registers hold one value's worth.  When all rows
 // of a wave's round that have a slot have the SAME slot (an item on one hot key), the wave adds their values up by shuffles and
-// one lane issues the atomic; any other mix of keys adds per lane.
+// one lane issues the atomic; any other mix of keys adds per lane.  With the descriptor's `combine` field set
+// (rhj_set_fold_combine) a tile with enough rows on shared slots sends those adds into LDS entries instead and one
+// atomic per (tile, slot, value) to the table (rhj_slot_combine.hip.h; fold_add_values below, shared with the tuple-key folds).
 #pragma once
 #include "rhj.h"
 #include "rhj_inter.h"
@@ -39,7 +41,8 @@ namespace rhj {
 
 constexpr int FOLD_W_EMPTY = 0;                      // an item's words: the empty key's A_c ...
 constexpr int FOLD_W_TOTAL = RHJ_FOLD_MAX_VALUES;    // ... then the outputs' totals
-constexpr int FOLD_WORDS = RHJ_FOLD_MAX_VALUES + RHJ_FOLD_MAX_OUTS;
+constexpr int FOLD_W_COMBINE = RHJ_FOLD_MAX_VALUES + RHJ_FOLD_MAX_OUTS;      // ... then the combiner's two counters
+constexpr int FOLD_WORDS = FOLD_W_COMBINE + (int)COMBINE_WORDS;
 constexpr uint64_t FOLD_OUTSIDE = JSUM_NONE - 1;     // no slot: the empty key, kept in the item's words
 
 struct FoldFactor {
@@ -65,7 +68,7 @@ struct JoinFoldDesc {
     uint32_t            slot_words;          // 1 + nvalues
     int                 build;   // the side that claims the slots
     int                 nvalues, nouts;
-    int                 pad;
+    int                 combine; // 1: the add launch combines equal slots per tile in LDS (rhj_slot_combine.hip.h)
     FoldFactor          v[RHJ_FOLD_MAX_VALUES];
     FoldOutDesc         o[RHJ_FOLD_MAX_OUTS];
 };
@@ -89,6 +92,85 @@ __device__ __forceinline__ void fold_factor(const FoldFactor &f, const uint64_t 
 #pragma unroll
         for (int k = 0; k < JSUM_ROUNDS; ++k) v[k] *= col[q[k]];
     }
+}
+
+// one add of x into the word `at` of slot `slot`: into the slot's LDS entry when the row has one (`entry`: the tile combines and
+// the row is the entry's owner or a rider), else the device-scope atomic, which `adds` counts
+__device__ __forceinline__ void fold_slot_add(jsum_gull at, uint64_t slot, unsigned long long x, bool entry, uint32_t &adds)
+{
+    if (entry) { combine_add(combine_lds<unsigned long long>(), slot, x); return; }
+    __hip_atomic_fetch_add(at, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ++adds;
+}
+
+// the end of a value in a combining tile: behind a barrier every owner takes its entry's sum and adds a non-zero one to the table;
+// a second barrier keeps the next value's adds behind the zero the owner left.  Every thread of the workgroup comes here.
+__device__ __forceinline__ void fold_flush(jsum_gull table, uint32_t sw, int c, const uint64_t (&slot)[JSUM_ROUNDS], uint32_t roles, uint32_t &adds)
+{
+    CombineLds<unsigned long long> &L = combine_lds<unsigned long long>();
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < JSUM_ROUNDS; ++k) {
+        if (combine_role(roles, k) != COMBINE_OWNER) continue;
+        const unsigned long long sum = combine_take(L, slot[k]);
+        if (sum) {
+            __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ++adds;
+        }
+    }
+    __syncthreads();
+}
+
+// The value loop of an add launch's tile, behind the slot resolution (slot[k] >= FOLD_OUTSIDE: no slot in the table; lead[k]: the
+// lane that adds for the wave when the round's slots are one, else 64), for the folds on one key (OUTSIDE: the empty key's rows add
+// to the item's words) and on tuple keys.  COMBINED (a tile that combines, rhj_slot_combine.hip.h): a row whose slot has an entry
+// adds into it, the wave's sum of a hot round first as ever, and the entry's owner adds the tile's sum to the table.
+template <bool COMBINED, bool OUTSIDE, class Desc>
+__device__ __forceinline__ void fold_add_loop(const Desc &d, jsum_gull table, uint32_t sw, const uint64_t (&slot)[JSUM_ROUNDS], const uint64_t (&pos)[JSUM_ROUNDS],
+                                              const uint32_t (&lead)[JSUM_ROUNDS], uint32_t roles, uint32_t &adds)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const int nvalues = d.nvalues;
+    for (int c = 0; c < nvalues; ++c) {
+        uint64_t v[JSUM_ROUNDS];
+        fold_factor(d.v[c], pos, v);
+        unsigned long long outside = 0;
+#pragma unroll
+        for (int k = 0; k < JSUM_ROUNDS; ++k) {
+            const bool in_table = slot[k] < FOLD_OUTSIDE;
+            const bool entry = COMBINED && combine_role(roles, k) != COMBINE_BYPASS;
+            if (OUTSIDE && slot[k] == FOLD_OUTSIDE) outside += v[k];
+            if (lead[k] < 64u) {                         // (wave-uniform)
+                const unsigned long long sum = jsum_wave_sum(in_table ? v[k] : 0);
+                if (lane == lead[k] && sum) fold_slot_add(&table[sw * slot[k] + 1 + c], slot[k], sum, entry, adds);
+            } else if (in_table && v[k]) {
+                fold_slot_add(&table[sw * slot[k] + 1 + c], slot[k], (unsigned long long)v[k], entry, adds);
+            }
+        }
+        if (OUTSIDE) {
+            outside = jsum_wave_sum(outside);
+            if (lane == 0 && outside) __hip_atomic_fetch_add(&d.words[FOLD_W_EMPTY + c], outside, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (COMBINED) fold_flush(table, sw, c, slot, roles, adds);
+    }
+}
+
+// the values of a tile under the descriptor's switch: off, the per-lane adds alone; on, the tile's claims, the loop in the form
+// the riders' count chose (workgroup-uniform: combine_claim), and the counters into the item's words from `w_combine` on
+template <bool OUTSIDE, class Desc>
+__device__ __forceinline__ void fold_add_values(const Desc &d, jsum_gull table, uint32_t sw, int w_combine, const uint64_t (&slot)[JSUM_ROUNDS],
+                                                const uint64_t (&pos)[JSUM_ROUNDS], const uint32_t (&lead)[JSUM_ROUNDS])
+{
+    uint32_t roles = 0, adds = 0;
+    if (!d.combine) {                                    // (workgroup-uniform)
+        fold_add_loop<false, OUTSIDE>(d, table, sw, slot, pos, lead, roles, adds);
+        return;
+    }
+    CombineLds<unsigned long long> &L = combine_lds<unsigned long long>();
+    const bool combined = combine_claim(L, slot, FOLD_OUTSIDE, roles);
+    if (combined) fold_add_loop<true, OUTSIDE>(d, table, sw, slot, pos, lead, roles, adds);
+    else fold_add_loop<false, OUTSIDE>(d, table, sw, slot, pos, lead, roles, adds);
+    combine_report(L, d.words + w_combine, combined, adds);
 }
 
 __global__ __launch_bounds__(256) void k_fold_claim(const JoinFoldDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
@@ -120,7 +202,6 @@ __global__ __launch_bounds__(256) void k_fold_add(const JoinFoldDesc *__restrict
     const uint32_t log2_slots = d.log2_slots, sw = d.slot_words;
     const jsum_gull table = (jsum_gull)d.table;
     const bool claims = d.build == 1;                    // (workgroup-uniform)
-    const int nvalues = d.nvalues;
     uint64_t slot[JSUM_ROUNDS], pos[JSUM_ROUNDS];
     uint32_t lead[JSUM_ROUNDS];                          // the lane that adds for the wave when the round's slots are one, else 64
     {
@@ -142,24 +223,7 @@ __global__ __launch_bounds__(256) void k_fold_add(const JoinFoldDesc *__restrict
             lead[k] = (have & (have - 1)) && (have & ~same) == 0 ? first : 64u;       // two or more rows, all in one slot
         }
     }
-    for (int c = 0; c < nvalues; ++c) {
-        uint64_t v[JSUM_ROUNDS];
-        fold_factor(d.v[c], pos, v);
-        unsigned long long outside = 0;
-#pragma unroll
-        for (int k = 0; k < JSUM_ROUNDS; ++k) {
-            const bool in_table = slot[k] < FOLD_OUTSIDE;
-            if (slot[k] == FOLD_OUTSIDE) outside += v[k];
-            if (lead[k] < 64u) {                         // (wave-uniform)
-                const unsigned long long sum = jsum_wave_sum(in_table ? v[k] : 0);
-                if (lane == lead[k] && sum) __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else if (in_table && v[k]) {
-                __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], (unsigned long long)v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        outside = jsum_wave_sum(outside);
-        if (lane == 0 && outside) __hip_atomic_fetch_add(&d.words[FOLD_W_EMPTY + c], outside, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    fold_add_values<true>(d, table, sw, FOLD_W_COMBINE, slot, pos, lead);
 }
 
 __global__ __launch_bounds__(256) void k_fold_apply(const JoinFoldDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)

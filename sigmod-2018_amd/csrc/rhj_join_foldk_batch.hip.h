@@ -38,7 +38,8 @@
 
 namespace rhj {
 
-constexpr int FOLDK_WORDS = RHJ_FOLD_MAX_OUTS;           // an item's words: the outputs' totals
+constexpr int FOLDK_W_COMBINE = RHJ_FOLD_MAX_OUTS;       // an item's words: the outputs' totals, then the combiner's two counters
+constexpr int FOLDK_WORDS = FOLDK_W_COMBINE + (int)COMBINE_WORDS;
 static_assert(RHJ_FOLD_MAX_KEYS == 4, "the kernels name a tuple's four words");
 
 // the hash of a tuple, one word at a time (h = 0 before the first), and the two things read off it
@@ -58,6 +59,8 @@ struct JoinFoldKDesc {
     int                 build;   // the side that claims the slots
     int                 nvalues, nouts;
     int                 nkeys;
+    int                 combine; // 1: the add launch combines equal slots per tile in LDS (rhj_slot_combine.hip.h)
+    int                 pad;
     FoldFactor          v[RHJ_FOLD_MAX_VALUES];
     FoldOutDesc         o[RHJ_FOLD_MAX_OUTS];
 };
@@ -198,7 +201,7 @@ __device__ __forceinline__ void foldk_add_tile(const Desc *__restrict__ descs, c
     const uint32_t log2_slots = d.log2_slots, sw = d.slot_words;
     const jsum_gull table = (jsum_gull)d.table;
     const bool claims = d.build == 1;                    // (workgroup-uniform)
-    const int nvalues = d.nvalues, nkeys = d.nkeys;
+    const int nkeys = d.nkeys;
     uint64_t slot[JSUM_ROUNDS], pos[JSUM_ROUNDS];
     uint32_t lead[JSUM_ROUNDS];                          // the lane that adds for the wave when the round's slots are one, else 64
     {
@@ -221,20 +224,7 @@ __device__ __forceinline__ void foldk_add_tile(const Desc *__restrict__ descs, c
             lead[k] = (have & (have - 1)) && (have & ~same) == 0 ? first : 64u;       // two or more rows, all in one slot
         }
     }
-    for (int c = 0; c < nvalues; ++c) {
-        uint64_t v[JSUM_ROUNDS];
-        fold_factor(d.v[c], pos, v);
-#pragma unroll
-        for (int k = 0; k < JSUM_ROUNDS; ++k) {
-            const bool in_table = slot[k] != JSUM_NONE;
-            if (lead[k] < 64u) {                         // (wave-uniform)
-                const unsigned long long sum = jsum_wave_sum(in_table ? v[k] : 0);
-                if (lane == lead[k] && sum) __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else if (in_table && v[k]) {
-                __hip_atomic_fetch_add(&table[sw * slot[k] + 1 + c], (unsigned long long)v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    fold_add_values<false>(d, table, sw, FOLDK_W_COMBINE, slot, pos, lead);     // (a tuple's slot is below FOLD_OUTSIDE wherever it is not JSUM_NONE)
 }
 
 template <class Desc>

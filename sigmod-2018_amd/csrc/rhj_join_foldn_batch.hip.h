@@ -38,6 +38,8 @@ struct JoinFoldNDesc {
     int                 build;   // the side that claims the slots
     int                 nvalues, nouts;
     int                 nkeys;
+    int                 combine; // 1: the add launch combines equal slots per tile in LDS (rhj_slot_combine.hip.h)
+    int                 pad;
     FoldFactor          v[RHJ_FOLD_MAX_VALUES];
     FoldOutDesc         o[RHJ_FOLD_MAX_OUTS];
 };

@@ -30,10 +30,15 @@
 // a term's 8 rows go out together, outside any per-lane branch; a row out of bounds reads row 0 and has w = 0.  Sums go per
 // wave by shuffles, per workgroup through LDS, then one atomic add per word and workgroup into the item's accumulator words,
 // which the host copies back, the whole chunk's in one copy, behind the third launch.
+//
+// With the descriptor's `combine` field set (rhj_set_fold_combine) the two count launches run the combiner of
+// rhj_slot_combine.hip.h: a tile's rows of one slot count up in LDS and the slot's count word takes ONE add a tile
+// (jsum_combine_counts); with it clear they add 1 a row, as written below.  The counts, and so every answer, are the same.
 #pragma once
 #include "rhj.h"
 #include "rhj_inter.h"
 #include "rhj_filter_batch.hip.h"
+#include "rhj_slot_combine.hip.h"
 
 namespace rhj {
 
@@ -46,7 +51,9 @@ constexpr uint64_t JSUM_SLOT_BYTES = 16;             // {u64 key, u32 build coun
 constexpr uint32_t JSUM_SLOT_WORDS = 2;              // the same in u64 words: what these kernels pass the table's functions
 constexpr uint64_t JSUM_NONE = ~(uint64_t)0;         // no slot: the key is not in the table
 constexpr int JSUM_W_MATCHES = 0, JSUM_W_SUM = 1, JSUM_W_EMPTY = 1 + RHJ_JOIN_SUM_MAX_TERMS;
-constexpr int JSUM_WORDS = 12;                       // an item's accumulator words: matches, the sums, the empty key's rows of R and of S, one spare
+constexpr int JSUM_WORDS = 11 + (int)COMBINE_WORDS;   // an item's accumulator words: matches, the sums, the empty key's rows of R and of S, the combiner's two counters
+constexpr int JSUM_W_COMBINE = JSUM_WORDS - (int)COMBINE_WORDS;
+static_assert(JSUM_ROUNDS == COMBINE_ROWS && JSUM_TILE == COMBINE_ENTRIES && JSUM_W_COMBINE == JSUM_W_EMPTY + 2, "the combiner's tile is this file's, its counters follow the words above");
 
 // log2 of the slots of a table built from `rows` rows: the smallest power of two that is >= JSUM_SLOTS_PER_ROW * rows, at least 2
 constexpr uint32_t jsum_log2_slots(uint64_t rows)
@@ -80,6 +87,8 @@ struct JoinSumDesc {
     int                 build;   // the side that builds
     uint32_t            tilesR;  // the sum phase: the item's tiles below this one are R's, the others S's
     int                 nterms;
+    int                 combine; // 1: the two count launches combine equal slots per tile in LDS (rhj_slot_combine.hip.h)
+    int                 pad;
     JoinSumTermDesc     t[RHJ_JOIN_SUM_MAX_TERMS];
 };
 
@@ -149,6 +158,32 @@ __device__ __forceinline__ void jsum_count_empty(unsigned long long *words, int 
     if ((threadIdx.x & 63) == 0 && mine) __hip_atomic_fetch_add(&words[JSUM_W_EMPTY + side], (unsigned long long)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// a count launch's tile with the combiner on: the tile's rows of one slot meet in LDS and the slot's count word (`word`: 0 the
+// build side's, 1 the other's) takes one add a tile; a bypassing row and a bailed-out tile add 1 a row, as without it
+__device__ __forceinline__ void jsum_combine_counts(jsum_gull table, int word, const uint64_t (&slot)[JSUM_ROUNDS], unsigned long long *words)
+{
+    CombineLds<uint32_t> &L = combine_lds<uint32_t>();
+    uint32_t roles, adds = 0;
+    const bool combined = combine_claim(L, slot, JSUM_NONE, roles);          // (workgroup-uniform)
+#pragma unroll
+    for (int k = 0; k < JSUM_ROUNDS; ++k) {
+        if (slot[k] == JSUM_NONE) continue;
+        if (combined && combine_role(roles, k) != COMBINE_BYPASS) { combine_add(L, slot[k], 1u); continue; }
+        __hip_atomic_fetch_add((jsum_gu32)(table + JSUM_SLOT_WORDS * slot[k] + 1) + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ++adds;
+    }
+    if (combined) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < JSUM_ROUNDS; ++k) {
+            if (combine_role(roles, k) != COMBINE_OWNER) continue;
+            __hip_atomic_fetch_add((jsum_gu32)(table + JSUM_SLOT_WORDS * slot[k] + 1) + word, combine_take(L, slot[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ++adds;                                      // (an owner counts itself: never 0)
+        }
+    }
+    combine_report(L, words + JSUM_W_COMBINE, combined, adds);
+}
+
 __global__ __launch_bounds__(256) void k_jsum_insert(const JoinSumDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
@@ -162,6 +197,19 @@ __global__ __launch_bounds__(256) void k_jsum_insert(const JoinSumDesc *__restri
     uint64_t key[JSUM_ROUNDS];
     jsum_keys((fb_gcu64)d.col[side], (fb_gcu64)d.sel[side], n, base, key);
     uint32_t empty = 0;
+    if (d.combine) {                                     // (workgroup-uniform)
+        uint64_t slot[JSUM_ROUNDS];
+#pragma unroll
+        for (int k = 0; k < JSUM_ROUNDS; ++k) {
+            slot[k] = JSUM_NONE;
+            if (base + (uint64_t)k * 256 >= n) continue;
+            if (key[k] == JSUM_EMPTY) { ++empty; continue; }
+            slot[k] = jsum_claim(table, JSUM_SLOT_WORDS, log2_slots, key[k]);
+        }
+        jsum_combine_counts(table, 0, slot, d.words);
+        jsum_count_empty(d.words, side, empty);
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < JSUM_ROUNDS; ++k) {
         if (base + (uint64_t)k * 256 >= n) continue;
@@ -186,6 +234,19 @@ __global__ __launch_bounds__(256) void k_jsum_count(const JoinSumDesc *__restric
     uint64_t key[JSUM_ROUNDS];
     jsum_keys((fb_gcu64)d.col[side], (fb_gcu64)d.sel[side], n, base, key);
     uint32_t empty = 0;
+    if (d.combine) {                                     // (workgroup-uniform)
+        uint64_t slot[JSUM_ROUNDS];
+#pragma unroll
+        for (int k = 0; k < JSUM_ROUNDS; ++k) {
+            slot[k] = JSUM_NONE;
+            if (base + (uint64_t)k * 256 >= n) continue;
+            if (key[k] == JSUM_EMPTY) { ++empty; continue; }
+            slot[k] = jsum_find(table, JSUM_SLOT_WORDS, log2_slots, key[k]);
+        }
+        jsum_combine_counts(table, 1, slot, d.words);
+        jsum_count_empty(d.words, side, empty);
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < JSUM_ROUNDS; ++k) {
         if (base + (uint64_t)k * 256 >= n) continue;

@@ -43,6 +43,7 @@
 //   rhj_eq2_batch.hip.h    many two-column equalities (colA[selA[i]] == colB[selB[i]]) in the same two launches.
 //   rhj_apply_batch.hip.h  many row-id rebuilds and view sums in one launch: an index list applied to up to 8 terms per item.
 //   rhj_stats_batch.hip.h  the statistics of many columns in three launches: min / max, one bit per flag, popcounts.
+//   rhj_slot_combine.hip.h a tile's adds to one table slot meet in LDS: the combiner of the four table batches' add launches.
 //   rhj_join_sum_batch.hip.h  the row counts and view sums of many final joins in three launches, without their pairs: per
 //                          item a table of {key, count of R, count of S}.
 //   rhj_join_fold_batch.hip.h many weighted join folds in three launches: a child side's values summed per key in the same
@@ -75,6 +76,7 @@
 #include "rhj_eq2_batch.hip.h"
 #include "rhj_apply_batch.hip.h"
 #include "rhj_stats_batch.hip.h"
+#include "rhj_slot_combine.hip.h"
 #include "rhj_join_sum_batch.hip.h"
 #include "rhj_join_fold_batch.hip.h"
 #include "rhj_join_foldk_batch.hip.h"
