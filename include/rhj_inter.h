@@ -374,7 +374,7 @@ typedef struct rhj_join_fold_desc {
     rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
     rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
     int rc;                  /* out */
-    int path;                /* out: 13, or 0 when nothing was launched */
+    int path;                /* out: 13 (18 for a resident item, rhj_set_fold_resident below), or 0 when nothing was launched */
 } rhj_join_fold_desc;
 int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n);
 
@@ -709,6 +709,33 @@ typedef struct {
     uint64_t slot_adds;
 } rhj_table_batch_combine_info;
 const rhj_table_batch_combine_info *rhj_table_batch_last_combine_info(void);
+
+/* rhj_join_fold_batch_device with this switch on (DEFAULT OFF; environment RHJ_FOLD_RESIDENT=0|1): an item whose
+ * table fits a workgroup's LDS is RESIDENT (csrc/rhj_fold_lds.hip.h): ONE workgroup folds it in ONE launch, k_fold_lds, the table
+ * in LDS.  Such an item has no table in the arena, so it counts 0 bytes where a batch is cut into chunks (its tiles and itself
+ * count as ever: 4096 items and 2^24 tiles still cut), it is not part of the chunk's memset and it has no tile in the three
+ * launches.  A chunk is still one upload, one copy back and one stream synchronisation; its resident items are one k_fold_lds
+ * launch, if it has any, and the others the memset of their tables and the three launches, if it has any.  Every d_out word and
+ * every total is bit for bit what the table form gives (sums modulo 2^64 do not depend on the order of their terms); call order
+ * of the results, rc, validation, empty sides and the refusal of a whole batch are unchanged.  A resident item reports path 18;
+ * rhj_last_stats().reserved of the call stays 13.  It brings no combiner counters and no tile to
+ * rhj_table_batch_last_combine_info(), which counts the table items only.  The switch reaches the fold batches on one key
+ * wherever they are issued: the entry point, the fold route of rhj_query_batch_device by waits, and its one-wait programs, where
+ * a round whose items are all resident issues no memset and one launch (rhj_query_batch_one_wait_info counts what was issued).
+ * The folds on tuple keys and the join sums have no resident form.
+ *
+ * rhj_fold_resident_rule(nR, nS, nvalues), a pure function that needs no device: 1 when an item of these sizes is resident
+ * while the switch is on, else 0.  All of: both sides have rows; slots * (1 + nvalues) <= 16 384 u64 words (128 KiB), slots the
+ * table's rule (the smallest power of two that is at least twice the rows of the side that builds: the smaller, R on a tie); and
+ * the other side, which the one workgroup walks alone, has at most 16 384 rows (both constants in csrc/rhj_fold_lds.hip.h; DESIGN.md 6 has the measurement behind the second).
+ *
+ * rhj_table_batch_last_resident_info(): the resident items, the k_fold_lds launches and the table items of the fold batches on
+ * one key.  Reset where rhj_table_batch_last_combine_info() is; all zero with the switch off. */
+void rhj_set_fold_resident(int on);
+int rhj_get_fold_resident(void);         /* the switch as it stands: the default, the environment's value or the last call's */
+int rhj_fold_resident_rule(uint64_t nR, uint64_t nS, int nvalues);
+typedef struct { uint32_t resident_items, resident_launches, table_items; } rhj_table_batch_resident_info;
+const rhj_table_batch_resident_info *rhj_table_batch_last_resident_info(void);
 
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);

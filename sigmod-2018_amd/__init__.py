@@ -49,6 +49,7 @@ INTER_SYMBOLS = [
     "rhj_fold_pred_batch_device", "rhj_query_one_wait_plan", "rhj_set_query_fold_one_wait", "rhj_set_query_fold_one_wait_rows", "rhj_query_batch_last_one_wait_info",
     "rhj_query_components", "rhj_set_query_products", "rhj_query_batch_last_products_info",
     "rhj_set_fold_combine", "rhj_get_fold_combine", "rhj_table_batch_last_combine_info",
+    "rhj_set_fold_resident", "rhj_get_fold_resident", "rhj_fold_resident_rule", "rhj_table_batch_last_resident_info",
 ]
 
 
@@ -377,6 +378,16 @@ class TableBatchCombineInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TableBatchResidentInfo(C.Structure):
+    """rhj_table_batch_resident_info (include/rhj_inter.h): the items of the last fold batch on one key (or of those inside the
+    last rhj_query_batch_device) that one workgroup folded in LDS with rhj_set_fold_resident on, their launches, and the items
+    that took the table form"""
+    _fields_ = [("resident_items", C.c_uint32), ("resident_launches", C.c_uint32), ("table_items", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def query_components(lib, query, nrel=None):
     """rhj_query_components on one query (relations, joins, filters, views): [component of every binding], the components
     numbered 0, 1, ... in the order of their lowest binding (one component unless the query is a cross product); ValueError on -3"""
@@ -622,6 +633,13 @@ def load_library(path=None):
         L.rhj_set_fold_combine.restype = None
         L.rhj_get_fold_combine.restype = C.c_int
         L.rhj_table_batch_last_combine_info.restype = C.POINTER(TableBatchCombineInfo)
+    if hasattr(L, "rhj_set_fold_resident"):           # (A/B runs load earlier builds through this module too)
+        L.rhj_set_fold_resident.argtypes = [C.c_int]
+        L.rhj_set_fold_resident.restype = None
+        L.rhj_get_fold_resident.restype = C.c_int
+        L.rhj_fold_resident_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
+        L.rhj_fold_resident_rule.restype = C.c_int
+        L.rhj_table_batch_last_resident_info.restype = C.POINTER(TableBatchResidentInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -1088,7 +1106,7 @@ class RHJ:
         for the total only, True for a vector of this call's, or an int64 tensor of at least nR elements to write into).
         Returns per item a list of (vector or None, total): d_out[i] = P(i) * A_value(keyR(i)) and its sum, Python ints below
         2^64.  The vectors this call makes are views of one allocation.  with_info: also the list of the items' path ids (13:
-        the batched launches, 0: an item with an empty side, whose vectors are left as they were)."""
+        the batched launches, 18: one workgroup with the table in LDS, set_fold_resident, 0: an item with an empty side, whose vectors are left as they were)."""
         return self._fold_batch(JoinFoldDesc, "rhj_join_fold_batch_device", items, with_info)
 
     def _fold_batch(self, Desc, entry, items, with_info):
@@ -1158,6 +1176,21 @@ class RHJ:
     def table_batch_last_combine_info(self):
         """rhj_table_batch_last_combine_info() as a dict: tiles, combined_tiles, slot_adds (all 0 with set_fold_combine off)"""
         return self.lib.rhj_table_batch_last_combine_info().contents.as_dict()
+
+    def set_fold_resident(self, on):
+        """an item of join_fold_batch_device whose table fits a workgroup's LDS (fold_resident_rule) is folded by one workgroup
+        in one launch, wherever the fold batches on one key are issued (default off); it reports path 18, and every answer is
+        bit for bit the same under both settings"""
+        self.lib.rhj_set_fold_resident(1 if on else 0)
+
+    def fold_resident_rule(self, nR, nS, nvalues):
+        """rhj_fold_resident_rule: whether an item of these sizes is resident while set_fold_resident is on (no device needed)"""
+        return bool(self.lib.rhj_fold_resident_rule(int(nR), int(nS), int(nvalues)))
+
+    def table_batch_last_resident_info(self):
+        """rhj_table_batch_last_resident_info() as a dict: resident_items, resident_launches, table_items (all 0 with
+        set_fold_resident off)"""
+        return self.lib.rhj_table_batch_last_resident_info().contents.as_dict()
 
     def set_query_fold(self, on):
         """query_batch_device sums the queries whose join predicates form a tree over their bindings by rounds of weighted join

@@ -72,6 +72,8 @@ constexpr uint32_t FUSED_LDS = LDS_BUDGET - FJ_LDS_EXTRA;                     //
 constexpr uint32_t LDS_MAX_SLOTS = LDS_BUDGET / 4 / 4 * 4;                    // tiled path: k_build_lds owns the whole LDS
 constexpr uint32_t FUSED_LDS_CAP = (FUSED_LDS - 128) * 2 / 9;                 // fused: 4 B entry + >= 0.5 B of slot starts per build tuple
 static_assert(LDS_MAX_SLOTS * 4 / 5 <= 65534 && FUSED_LDS_CAP <= 65534, "LDS-indexed build sides: 16-bit position + 1");
+constexpr uint32_t FOLD_LDS_MAX_BYTES = (uint32_t)(FOLD_LDS_FIXED_WORDS + FOLD_LDS_WORDS) * 8;        // k_fold_lds: the largest resident table and the fixed words
+static_assert(FOLD_LDS_MAX_BYTES <= LDS_BUDGET, "a resident fold's table and its fixed words fit a workgroup's LDS");
 constexpr uint32_t BUILD_CHUNK = 4096;            // build tuples per 64-bit-table build unit
 
 enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSETS, ST_PROBE, ST_END, ST_N };
@@ -175,6 +177,7 @@ int g_query_fold_one_wait = 0;       // 1: with g_query_fold, the folding querie
 uint64_t g_query_fold_one_wait_rows = 4096;              // the most rows of a relation on that route (rhj_set_query_fold_one_wait_rows): the largest size at which whole relations under weights measured no slower than hit lists
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 int g_fold_combine = 1;              // 1: the add launches of the four table batches combine a tile's adds to one slot in LDS and send one atomic per (tile, slot, value) (rhj_slot_combine.hip.h; rhj_set_fold_combine, env RHJ_FOLD_COMBINE)
+int g_fold_resident = 0;             // 1: an item of rhj_join_fold_batch_device whose table fits a workgroup's LDS (fold_resident_rule) is folded by one workgroup in one k_fold_lds launch, with no table in the arena (rhj_fold_lds.hip.h; rhj_set_fold_resident, env RHJ_FOLD_RESIDENT)
 int g_query_products = 0;            // 1: rhj_query_batch_device takes a query whose bindings end in several nodes (a cross product) as one query per component and multiplies their answers on the host (rhj_set_query_products, env RHJ_QUERY_PRODUCTS)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -212,6 +215,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_FOLD_ONE_WAIT"))) g_query_fold_one_wait = atoi(e) != 0;
         if ((e = getenv("RHJ_QUERY_PRODUCTS"))) g_query_products = atoi(e) != 0;
         if ((e = getenv("RHJ_FOLD_COMBINE"))) g_fold_combine = atoi(e) != 0;
+        if ((e = getenv("RHJ_FOLD_RESIDENT"))) g_fold_resident = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -293,6 +297,7 @@ int ctx_init()
     HIP_TRY(hipFuncSetAttribute((const void *)k_scatter_runs<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
     HIP_TRY(hipFuncSetAttribute((const void *)k_scatter_runs<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
     HIP_TRY(hipFuncSetAttribute((const void *)k_lr_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lr_lds_bytes(PT_MAX_BITS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_fold_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLD_LDS_MAX_BYTES));
     g.ready = true;
     return 0;
 }
@@ -1376,7 +1381,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16, PATH_BATCH_FOLD_PRED = 17 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16, PATH_BATCH_FOLD_PRED = 17, PATH_BATCH_JOIN_FOLD_LDS = 18 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2202,7 +2207,10 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
 // by the first two into groups, a group by the third into chunks.  A chunk takes its first item whatever its table needs.  A
 // chunk is one upload, one memset of exactly its tables, three launches (the folds' first only when some item's R builds), one
 // copy of its accumulator words and one stream synchronisation; the uploaded block is
-//   [descriptors][items + 1 tile starts of the first launch][of the second][of the third][the item's accumulator words, zero]
+//   [descriptors][items + 1 tile starts of the first launch][of the second][of the third][the indices of the resident items][the
+//   item's accumulator words, zero]
+// (the resident items: those of rhj_join_fold_batch_device that one workgroup folds in LDS with rhj_set_fold_resident on; they have
+// no table, no tile in the three launches and a launch of their own, and a chunk of them alone has no memset: tbatch_resident below)
 constexpr size_t JSUM_MAX_ITEMS = 4096;
 constexpr uint64_t JSUM_MAX_TILES = 1ull << 24;
 constexpr uint64_t JSUM_MAX_ROWS = 1ull << 32;            // a side has fewer rows than this: a slot's counts are 32-bit words
@@ -2243,6 +2251,28 @@ static void tbatch_combine_take(const uint32_t (&t)[3], const unsigned long long
     }
 }
 
+// The resident form of the folds on one key (rhj_fold_lds.hip.h).  With g_fold_resident on, an item that
+// fold_resident_rule names has no table in the arena (tbatch_table_bytes 0), no tile in the three launches (tbatch_fill) and path
+// 18; a chunk's such items are ONE k_fold_lds launch over an index array that is uploaded with the chunk.  The descriptors stay
+// one array in call order, so fbatch_find passes over a resident item as over any item without a tile in a launch.  The other
+// three descriptors have no resident form.  g_resident_info counts, where g_combine_info counts, the resident items, their
+// launches and the table items of the fold batches on one key; all zero with the switch off.
+rhj_table_batch_resident_info g_resident_info = {};
+template <class D> static inline bool tbatch_resident(const D &) { return false; }
+static inline bool tbatch_resident(const rhj_join_fold_desc &q) { return g_fold_resident && fold_resident_rule(q.nR, q.nS, q.nvalues); }
+template <class D> static inline size_t tbatch_resident_lds(const D &) { return 0; }
+static inline size_t tbatch_resident_lds(const rhj_join_fold_desc &q) { return fold_lds_bytes(q.nR, q.nS, q.nvalues); }
+// a group of fold items' resident launch, if it has any: `res` their indices among the descriptors dd, `lds` the largest's bytes
+static void tbatch_launch_resident(const JoinFoldDesc *dd, const uint32_t *d_res, uint32_t nres, size_t lds, size_t ni)
+{
+    if (nres) {
+        RHJ_LAUNCH(k_fold_lds, dim3(nres), dim3(256), lds, g.stream, dd, d_res);
+        ++g_resident_info.resident_launches;
+    }
+    if (g_fold_resident) { g_resident_info.resident_items += nres; g_resident_info.table_items += (uint32_t)(ni - nres); }
+}
+template <class Dev> static void tbatch_launch_resident(const Dev *, const uint32_t *, uint32_t, size_t, size_t) {}
+
 static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
     if (!tbatch_sides_valid(q) || q.nterms < 0 || q.nterms > RHJ_JOIN_SUM_MAX_TERMS) return false;
@@ -2279,7 +2309,7 @@ static void tbatch_zero(rhj_join_foldk_desc &q) { for (int o = 0; o < q.nouts; +
 static void tbatch_zero(rhj_join_foldn_desc &q) { for (int o = 0; o < q.nouts; ++o) q.outs[o].total = 0; }
 
 static inline uint64_t tbatch_table_bytes(const rhj_join_sum_desc &q) { return tbatch_slots(q) * JSUM_SLOT_BYTES; }
-static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_resident(q) ? 0 : tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }    // (a resident item's table is in LDS)
 static inline uint64_t tbatch_table_bytes(const rhj_join_foldk_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 static inline uint64_t tbatch_table_bytes(const rhj_join_foldn_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 
@@ -2323,6 +2353,12 @@ static void tbatch_fill_fold(const D &q, Dev &d, uint32_t (&t)[3])
 static void tbatch_fill(const rhj_join_fold_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldDesc &d, uint32_t (&t)[3])
 {
     tbatch_common(q, table, words, d);
+    if (tbatch_resident(q)) {                            // no table in the arena and no tile in the three launches: k_fold_lds takes the item
+        uint32_t none[3] = {0, 0, 0};
+        d.table = nullptr;
+        tbatch_fill_fold(q, d, none);
+        return;
+    }
     tbatch_fill_fold(q, d, t);
 }
 static void tbatch_fill(const rhj_join_foldk_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldKDesc &d, uint32_t (&t)[3])
@@ -2392,6 +2428,8 @@ static inline int tbatch_path(const rhj_join_sum_desc &) { return PATH_BATCH_JOI
 static inline int tbatch_path(const rhj_join_fold_desc &) { return PATH_BATCH_JOIN_FOLD; }
 static inline int tbatch_path(const rhj_join_foldk_desc &) { return PATH_BATCH_JOIN_FOLDK; }
 static inline int tbatch_path(const rhj_join_foldn_desc &) { return PATH_BATCH_JOIN_FOLDN; }
+// what an item reports; tbatch_path is what the call does (rhj_last_stats().reserved)
+template <class D> static inline int tbatch_item_path(const D &q) { return tbatch_resident(q) ? PATH_BATCH_JOIN_FOLD_LDS : tbatch_path(q); }
 static inline const char *tbatch_noun(const rhj_join_sum_desc &) { return "join sums"; }
 static inline const char *tbatch_noun(const rhj_join_fold_desc &) { return "join folds"; }
 static inline const char *tbatch_noun(const rhj_join_foldk_desc &) { return "join folds on tuple keys"; }
@@ -2413,15 +2451,17 @@ static int tbatch_chunk(D *items, const uint64_t *which, size_t lo, size_t hi, u
     if (batch_arena(g.jsum_arena, (size_t)bytes, JSUM_ARENA_BYTES)) return -1;
     Block blk;
     unsigned long long *back, *words, *d_words; Dev *hd, *dd;
-    uint32_t *ts[3], *d_ts[3];
+    uint32_t *ts[3], *d_ts[3], *res, *d_res;
+    size_t nres = 0, res_lds = 0;                         // the resident items (rhj_set_fold_resident) and the largest's LDS bytes
+    for (size_t k = 0; k < ni; ++k) nres += tbatch_resident(items[which[lo + k]]);
     const auto pieces = [&](Block &b) {
         b.back(back, ni * WORDS);
-        b.up(hd, dd, ni); b.up(ts[0], d_ts[0], ni + 1); b.up(ts[1], d_ts[1], ni + 1); b.up(ts[2], d_ts[2], ni + 1); b.up(words, d_words, ni * WORDS);
+        b.up(hd, dd, ni); b.up(ts[0], d_ts[0], ni + 1); b.up(ts[1], d_ts[1], ni + 1); b.up(ts[2], d_ts[2], ni + 1); b.up(res, d_res, nres); b.up(words, d_words, ni * WORDS);
     };
     if (batch_block(blk, pieces)) return -1;
     memset(words, 0, ni * WORDS * 8);
     uint32_t t[3] = {0, 0, 0};
-    size_t at = 0;
+    size_t at = 0, r = 0;
     for (size_t k = 0; k < ni; ++k) {
         const D &q = items[which[lo + k]];
         ts[0][k] = t[0]; ts[1][k] = t[1]; ts[2][k] = t[2];
@@ -2429,21 +2469,28 @@ static int tbatch_chunk(D *items, const uint64_t *which, size_t lo, size_t hi, u
         tbatch_fill(q, (unsigned long long *)((char *)g.jsum_arena.p + at), d_words + k * WORDS, d, t);
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
         at += (size_t)tbatch_table_bytes(q);
+        if (tbatch_resident(q)) {
+            res[r++] = (uint32_t)k;
+            res_lds = std::max(res_lds, tbatch_resident_lds(q));
+        }
     }
     ts[0][ni] = t[0]; ts[1][ni] = t[1]; ts[2][ni] = t[2];
     if (at != (size_t)bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a chunk of %s were placed beyond its arena\n", tbatch_noun(items[which[lo]])); return -1; }
     if (batch_upload(blk, hd, blk.host_end())) return -1;
-    HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));         // every key word JSUM_EMPTY (0), every count and every A_c 0
-    tbatch_launch(items[which[lo]], dd, (uint32_t)ni, d_ts, t);
+    if (nres < ni) {                                      // (always, with the resident switch off)
+        HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, at, g.stream));     // every key word JSUM_EMPTY (0), every count and every A_c 0
+        tbatch_launch(items[which[lo]], dd, (uint32_t)ni, d_ts, t);
+    }
+    tbatch_launch_resident(dd, d_res, (uint32_t)nres, res_lds, ni);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(back, d_words, ni * WORDS * 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     for (size_t k = 0; k < ni; ++k) {
         D &q = items[which[lo + k]];
         tbatch_take(q, back + k * WORDS);
-        q.path = tbatch_path(q);
+        q.path = tbatch_item_path(q);
     }
-    tbatch_combine_take<D>(t, back, ni);
+    tbatch_combine_take<D>(t, back, ni);                 // (a resident item has no tile in t and its two counters are 0)
     return 0;
 }
 
@@ -3625,18 +3672,25 @@ static void ow_fix_fold(D &d, uintptr_t base)
 }
 
 // a round's items of one kind into the block: descriptors, tile starts, tables from byte `at` of the arena on, words from `wat` on
+// (`res` takes the indices of the resident ones, `res_lds` the largest's LDS bytes: rhj_set_fold_resident)
 template <class D, class Dev>
-static void ow_fill(const std::vector<D> &items, Dev *hd, uint32_t *const (&ts)[3], uint32_t (&t)[3], size_t &at, unsigned long long *d_words, size_t &wat)
+static void ow_fill(const std::vector<D> &items, Dev *hd, uint32_t *const (&ts)[3], uint32_t (&t)[3], size_t &at, unsigned long long *d_words, size_t &wat,
+                    uint32_t *res, size_t &res_lds)
 {
     constexpr size_t WORDS = tbatch_dev<D>::words;
     t[0] = t[1] = t[2] = 0;
-    for (size_t k = 0; k < items.size(); ++k) {
+    res_lds = 0;
+    for (size_t k = 0, r = 0; k < items.size(); ++k) {
         ts[0][k] = t[0]; ts[1][k] = t[1]; ts[2][k] = t[2];
         Dev d;
         tbatch_fill(items[k], (unsigned long long *)((char *)g.jsum_arena.p + at), d_words + wat, d, t);
         memcpy((void *)&hd[k], (const void *)&d, sizeof(d));
         at += (size_t)tbatch_table_bytes(items[k]);
         wat += WORDS;
+        if (tbatch_resident(items[k])) {
+            res[r++] = (uint32_t)k;
+            res_lds = std::max(res_lds, tbatch_resident_lds(items[k]));
+        }
     }
     ts[0][items.size()] = t[0]; ts[1][items.size()] = t[1]; ts[2][items.size()] = t[2];
 }
@@ -3659,8 +3713,12 @@ static int ow_run(QueryRun &R, OwProgram &P)
         for (rhj_join_fold_desc &d : rd.fd) ow_fix_fold(d, base);
         for (rhj_join_foldk_desc &d : rd.kd) ow_fix_fold(d, base);
     }
-    struct RoundPieces { JoinFoldDesc *hf, *df; JoinFoldKDesc *hk, *dk; uint32_t *ts[2][3], *d_ts[2][3]; uint32_t t[2][3]; };
+    struct RoundPieces { JoinFoldDesc *hf, *df; JoinFoldKDesc *hk, *dk; uint32_t *ts[2][3], *d_ts[2][3]; uint32_t t[2][3]; uint32_t *res, *d_res; size_t nres, res_lds; };
     std::vector<RoundPieces> rp(nr);
+    for (size_t r = 0; r < nr; ++r) {
+        rp[r].nres = 0;
+        for (const rhj_join_fold_desc &d : P.rounds[r].fd) rp[r].nres += tbatch_resident(d);
+    }
     Block blk;
     unsigned long long *back, *words, *d_words; FoldPredDesc *hp, *dp; uint32_t *ptile, *d_ptile;
     const auto pieces = [&](Block &b) {
@@ -3670,6 +3728,7 @@ static int ow_run(QueryRun &R, OwProgram &P)
             const size_t nf = P.rounds[r].fd.size(), nk = P.rounds[r].kd.size();
             b.up(rp[r].hf, rp[r].df, nf);
             for (int j = 0; j < 3; ++j) b.up(rp[r].ts[0][j], rp[r].d_ts[0][j], nf + 1);
+            b.up(rp[r].res, rp[r].d_res, rp[r].nres);
             b.up(rp[r].hk, rp[r].dk, nk);
             for (int j = 0; j < 3; ++j) b.up(rp[r].ts[1][j], rp[r].d_ts[1][j], nk + 1);
         }
@@ -3692,9 +3751,10 @@ static int ow_run(QueryRun &R, OwProgram &P)
     for (size_t r = 0; r < nr; ++r) {
         size_t at = 0;
         wfold[r] = wat;
-        ow_fill(P.rounds[r].fd, rp[r].hf, rp[r].ts[0], rp[r].t[0], at, d_words, wat);
+        size_t none;
+        ow_fill(P.rounds[r].fd, rp[r].hf, rp[r].ts[0], rp[r].t[0], at, d_words, wat, rp[r].res, rp[r].res_lds);
         wfoldk[r] = wat;
-        ow_fill(P.rounds[r].kd, rp[r].hk, rp[r].ts[1], rp[r].t[1], at, d_words, wat);
+        ow_fill(P.rounds[r].kd, rp[r].hk, rp[r].ts[1], rp[r].t[1], at, d_words, wat, nullptr, none);
         if (at != (size_t)P.rounds[r].bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a round of a fold program were placed beyond its arena\n"); return -1; }
     }
     if (wat != nwords) { fprintf(stderr, "rhj: a fold program's words were miscounted\n"); return -1; }
@@ -3708,11 +3768,19 @@ static int ow_run(QueryRun &R, OwProgram &P)
         const OwRound &rd = P.rounds[r];
         if (rd.fd.empty() && rd.kd.empty()) continue;
         // the arena's tables of the round before are dead: stream order puts this memset behind their last reader
-        HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, (size_t)rd.bytes, g.stream));
-        ++info.memsets; ++info.rounds;
-        if (!rd.fd.empty()) {
+        // (a round whose items are all resident, rhj_set_fold_resident, has no table: no memset, and one launch)
+        if (rd.bytes) {
+            HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, (size_t)rd.bytes, g.stream));
+            ++info.memsets;
+        }
+        ++info.rounds;
+        if (rp[r].nres < rd.fd.size()) {
             tbatch_launch(rd.fd[0], rp[r].df, (uint32_t)rd.fd.size(), rp[r].d_ts[0], rp[r].t[0]);
             info.launches += 2 + (rp[r].t[0][0] != 0);
+        }
+        if (!rd.fd.empty()) {
+            tbatch_launch_resident(rp[r].df, rp[r].d_res, (uint32_t)rp[r].nres, rp[r].res_lds, rd.fd.size());
+            info.launches += rp[r].nres != 0;
         }
         if (!rd.kd.empty()) {
             tbatch_launch(rd.kd[0], rp[r].dk, (uint32_t)rd.kd.size(), rp[r].d_ts[1], rp[r].t[1]);
@@ -4541,12 +4609,16 @@ const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void) { return &
 int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {};
+    g_combine_info = {}; g_resident_info = {};
     return g_query_products ? query_products(rels, nrel, queries, n) : query_batch(rels, nrel, queries, n);
 }
 void rhj_set_fold_combine(int on) { RhjApiLock api_lock; g_fold_combine = on != 0; }
 int rhj_get_fold_combine(void) { return g_fold_combine; }
 const rhj_table_batch_combine_info *rhj_table_batch_last_combine_info(void) { return &g_combine_info; }
+void rhj_set_fold_resident(int on) { RhjApiLock api_lock; g_fold_resident = on != 0; }
+int rhj_get_fold_resident(void) { return g_fold_resident; }
+int rhj_fold_resident_rule(uint64_t nR, uint64_t nS, int nvalues) { return fold_resident_rule(nR, nS, nvalues); }
+const rhj_table_batch_resident_info *rhj_table_batch_last_resident_info(void) { return &g_resident_info; }
 int rhj_query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp) { return query_components(q, nrel, rels, comp); }
 void rhj_set_query_products(int on) { RhjApiLock api_lock; g_query_products = on != 0; }
 const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void) { return &g_query_products_info; }
@@ -4575,28 +4647,28 @@ int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_rela
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {};
+    g_combine_info = {}; g_resident_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {};
+    g_combine_info = {}; g_resident_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {};
+    g_combine_info = {}; g_resident_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {};
+    g_combine_info = {}; g_resident_info = {};
     return table_batch(items, n);
 }
 

@@ -173,6 +173,16 @@ __device__ __forceinline__ void fold_add_values(const Desc &d, jsum_gull table, 
     combine_report(L, d.words + w_combine, combined, adds);
 }
 
+// the lane that adds for the wave when the rows of one round that have a slot are two or more and all in ONE slot, else 64
+__device__ __forceinline__ uint32_t fold_wave_lead(uint64_t slot)
+{
+    const uint64_t have = __ballot(slot < FOLD_OUTSIDE);
+    const uint32_t first = have ? (uint32_t)__ffsll((unsigned long long)have) - 1u : 0u;
+    const uint64_t s0 = __shfl(slot, (int)first, 64);
+    const uint64_t same = __ballot(slot == s0);
+    return (have & (have - 1)) && (have & ~same) == 0 ? first : 64u;
+}
+
 __global__ __launch_bounds__(256) void k_fold_claim(const JoinFoldDesc *__restrict__ descs, const uint32_t *__restrict__ tile_start, uint32_t ni)
 {
     const uint32_t j = fbatch_find(tile_start, ni, blockIdx.x);
@@ -216,11 +226,7 @@ __global__ __launch_bounds__(256) void k_fold_add(const JoinFoldDesc *__restrict
                 if (key[k] == JSUM_EMPTY) slot[k] = FOLD_OUTSIDE;
                 else slot[k] = claims ? jsum_claim(table, sw, log2_slots, key[k]) : jsum_find(table, sw, log2_slots, key[k]);
             }
-            const uint64_t have = __ballot(slot[k] < FOLD_OUTSIDE);
-            const uint32_t first = have ? (uint32_t)__ffsll((unsigned long long)have) - 1u : 0u;
-            const uint64_t s0 = __shfl(slot[k], (int)first, 64);
-            const uint64_t same = __ballot(slot[k] == s0);
-            lead[k] = (have & (have - 1)) && (have & ~same) == 0 ? first : 64u;       // two or more rows, all in one slot
+            lead[k] = fold_wave_lead(slot[k]);
         }
     }
     fold_add_values<true>(d, table, sw, FOLD_W_COMBINE, slot, pos, lead);

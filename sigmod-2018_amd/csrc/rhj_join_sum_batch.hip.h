@@ -94,6 +94,7 @@ struct JoinSumDesc {
 
 typedef __attribute__((address_space(1))) unsigned long long *jsum_gull;
 typedef __attribute__((address_space(1))) uint32_t *jsum_gu32;
+typedef __attribute__((address_space(3))) unsigned long long *jsum_lull;     // a table in LDS (rhj_fold_lds.hip.h)
 
 // the keys of a thread's 8 rows of one side; a row out of bounds reads row 0 in its place (n >= 1)
 __device__ __forceinline__ void jsum_keys(fb_gcu64 col, fb_gcu64 sel, uint64_t n, uint64_t base, uint64_t (&key)[JSUM_ROUNDS])
@@ -111,9 +112,11 @@ __device__ __forceinline__ void jsum_keys(fb_gcu64 col, fb_gcu64 sel, uint64_t n
     for (int k = 0; k < JSUM_ROUNDS; ++k) key[k] = col[key[k]];
 }
 
-// The table's two functions, over slots of `sw` u64 words whose first is the key (`key` != JSUM_EMPTY).
+// The table's two functions, over slots of `sw` u64 words whose first is the key (`key` != JSUM_EMPTY).  Table: jsum_gull, a
+// table in the arena, or jsum_lull, one in LDS, whose claims are atomics of SCOPE workgroup: one hash and one protocol for both.
 // jsum_find: the slot that holds `key`, or JSUM_NONE when the table has none: at most `slots` steps
-__device__ __forceinline__ uint64_t jsum_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
+template <class Table>
+__device__ __forceinline__ uint64_t jsum_find(Table table, uint32_t sw, uint32_t log2_slots, uint64_t key)
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
     uint64_t s = jsum_hash(key, log2_slots);
@@ -127,15 +130,16 @@ __device__ __forceinline__ uint64_t jsum_find(jsum_gull table, uint32_t sw, uint
 
 // jsum_claim: the slot of `key`, found or claimed, at most `slots` steps (a free slot is always met: at most half are taken);
 // JSUM_NONE only if the table were full
-__device__ __forceinline__ uint64_t jsum_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, uint64_t key)
+template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT, class Table>
+__device__ __forceinline__ uint64_t jsum_claim(Table table, uint32_t sw, uint32_t log2_slots, uint64_t key)
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
     uint64_t s = jsum_hash(key, log2_slots);
     for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, SCOPE);
         if (seen == JSUM_EMPTY) {
             // one exchange; on failure `seen` is the key somebody else put there, which stays
-            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) seen = key;
+            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE)) seen = key;
         }
         if (seen == key) return s;
     }

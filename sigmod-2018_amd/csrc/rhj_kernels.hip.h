@@ -48,6 +48,8 @@
 //                          item a table of {key, count of R, count of S}.
 //   rhj_join_fold_batch.hip.h many weighted join folds in three launches: a child side's values summed per key in the same
 //                          table, then multiplied into per-row u64 weights of the parent side.
+//   rhj_fold_lds.hip.h     the same folds for an item whose table fits a workgroup's LDS: one workgroup folds it in one launch,
+//                          with no table in the arena, no memset and no claim launch (rhj_set_fold_resident).
 //   rhj_join_foldk_batch.hip.h the same folds on keys of up to four columns: a slot holds the build row that owns it, not a key,
 //                          and equality is decided on that row's words, gathered from the build side's own columns.
 //   rhj_join_foldn_batch.hip.h the tuple-key folds with a row-id vector per key word: the keys of a materialised node, whose
@@ -79,6 +81,7 @@
 #include "rhj_slot_combine.hip.h"
 #include "rhj_join_sum_batch.hip.h"
 #include "rhj_join_fold_batch.hip.h"
+#include "rhj_fold_lds.hip.h"
 #include "rhj_join_foldk_batch.hip.h"
 #include "rhj_join_foldn_batch.hip.h"
 #include "rhj_fold_self_batch.hip.h"
