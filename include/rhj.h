@@ -268,7 +268,7 @@ typedef struct rhj_stats {
     uint64_t n_r, n_s, matches;
     uint64_t units, hbm_units, max_build, table_slots;
     int radix_bits;
-    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit), 6 a batch (rhj_join_batch_device), 7 a batch of filters (rhj_filter_batch_device), 8 a batch of rebuilds and view sums (rhj_apply_batch_device, rhj_inter.h), 9 a batch of two-column equalities (rhj_filter_eq2_batch_device, rhj_inter.h), 10 a batch of queries (rhj_query_batch_device, rhj_inter.h), 11 a batch of column statistics (rhj_column_stats_batch_device, rhj_inter.h), 12 a batch of final joins' sums (rhj_join_sum_batch_device, rhj_inter.h), 13 a batch of weighted join folds (rhj_join_fold_batch_device, rhj_inter.h), 14 a batch of weighted join folds on tuple keys (rhj_join_foldk_batch_device, rhj_inter.h), 15 a batch of folds with no child (rhj_fold_self_batch_device, rhj_inter.h), 16 a batch of weighted join folds on tuple keys with a row-id vector per key word (rhj_join_foldn_batch_device, rhj_inter.h), 17 a batch of folds with no child and constant predicates (rhj_fold_pred_batch_device, rhj_inter.h), 18 an item of a batch of weighted join folds that one workgroup folded in LDS (the `path` of a resident item, rhj_set_fold_resident, rhj_inter.h; never the `reserved` of a call) */
+    int reserved;      /* path of the last join: 0 tiled, 1 fused, 3 small (fused join behind the two- or three-launch partition of csrc/rhj_small.hip.h), 4 low-radix (csrc/rhj_lowradix.hip.h), 5 sub-bucket (csrc/rhj_subbucket.hip.h: ms_build is its split pass, ms_probe the internal join, ms_offsets the emit), 6 a batch (rhj_join_batch_device), 7 a batch of filters (rhj_filter_batch_device), 8 a batch of rebuilds and view sums (rhj_apply_batch_device, rhj_inter.h), 9 a batch of two-column equalities (rhj_filter_eq2_batch_device, rhj_inter.h), 10 a batch of queries (rhj_query_batch_device, rhj_inter.h), 11 a batch of column statistics (rhj_column_stats_batch_device, rhj_inter.h), 12 a batch of final joins' sums (rhj_join_sum_batch_device, rhj_inter.h), 13 a batch of weighted join folds (rhj_join_fold_batch_device, rhj_inter.h), 14 a batch of weighted join folds on tuple keys (rhj_join_foldk_batch_device, rhj_inter.h), 15 a batch of folds with no child (rhj_fold_self_batch_device, rhj_inter.h), 16 a batch of weighted join folds on tuple keys with a row-id vector per key word (rhj_join_foldn_batch_device, rhj_inter.h), 17 a batch of folds with no child and constant predicates (rhj_fold_pred_batch_device, rhj_inter.h), 18 an item of a batch of weighted join folds that one workgroup folded in LDS (the `path` of a resident item, rhj_set_fold_resident, rhj_inter.h; never the `reserved` of a call), 19 an item of a batch of weighted join folds on tuple keys that one workgroup folded in LDS (the `path` of a resident item of rhj_join_foldk_batch_device or rhj_join_foldn_batch_device, rhj_set_fold_resident_keys, rhj_inter.h; never the `reserved` of a call) */
 } rhj_stats;
 
 /* Join two device-resident AoS relations (rhj_tuple[nR], rhj_tuple[nS]).

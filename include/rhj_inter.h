@@ -422,7 +422,7 @@ typedef struct rhj_join_foldk_desc {
     rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
     rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
     int rc;                  /* out */
-    int path;                /* out: 14, or 0 when nothing was launched */
+    int path;                /* out: 14 (19 for a resident item, rhj_set_fold_resident_keys below), or 0 when nothing was launched */
 } rhj_join_foldk_desc;
 int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n);
 
@@ -544,7 +544,7 @@ typedef struct rhj_join_foldn_desc {
     rhj_fold_factor values[RHJ_FOLD_MAX_VALUES];      /* over S's positions */
     rhj_fold_out    outs[RHJ_FOLD_MAX_OUTS];
     int rc;                  /* out */
-    int path;                /* out: 16, or 0 when nothing was launched */
+    int path;                /* out: 16 (19 for a resident item, rhj_set_fold_resident_keys below), or 0 when nothing was launched */
 } rhj_join_foldn_desc;
 int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n);
 
@@ -722,7 +722,7 @@ const rhj_table_batch_combine_info *rhj_table_batch_last_combine_info(void);
  * rhj_table_batch_last_combine_info(), which counts the table items only.  The switch reaches the fold batches on one key
  * wherever they are issued: the entry point, the fold route of rhj_query_batch_device by waits, and its one-wait programs, where
  * a round whose items are all resident issues no memset and one launch (rhj_query_batch_one_wait_info counts what was issued).
- * The folds on tuple keys and the join sums have no resident form.
+ * The folds on tuple keys have a resident form under a switch of their own (rhj_set_fold_resident_keys below); the join sums have none.
  *
  * rhj_fold_resident_rule(nR, nS, nvalues), a pure function that needs no device: 1 when an item of these sizes is resident
  * while the switch is on, else 0.  All of: both sides have rows; slots * (1 + nvalues) <= 16 384 u64 words (128 KiB), slots the
@@ -736,6 +736,34 @@ int rhj_get_fold_resident(void);         /* the switch as it stands: the default
 int rhj_fold_resident_rule(uint64_t nR, uint64_t nS, int nvalues);
 typedef struct { uint32_t resident_items, resident_launches, table_items; } rhj_table_batch_resident_info;
 const rhj_table_batch_resident_info *rhj_table_batch_last_resident_info(void);
+
+/* rhj_join_foldk_batch_device and rhj_join_foldn_batch_device with this switch on (DEFAULT OFF; environment
+ * RHJ_FOLD_RESIDENT_KEYS=0|1): the resident form above for the folds on tuple keys
+ * (csrc/rhj_fold_keys_lds.hip.h).  ONE workgroup folds a resident item in ONE launch, k_foldk_lds or k_foldn_lds.  The table in
+ * LDS is the table of the arena: a slot holds the build row that owns it and the sums, not the key, and equality is still
+ * decided on the owner's words, gathered from the build side's columns in memory.  Such an item counts 0 bytes where a batch is
+ * cut into chunks (4096 items and 2^24 tiles still cut), is not part of the chunk's memset and has no tile in the three
+ * launches; a chunk whose items are all resident issues no memset and one launch, a mixed one the memset and three launches of
+ * its table items and then the resident launch.  Every d_out word and every total is bit for bit what the table form gives;
+ * call order, rc, validation, empty sides and the refusal of a whole batch are unchanged.  A resident item reports path 19;
+ * rhj_last_stats().reserved of the call stays 14 or 16.  The switch is independent of rhj_set_fold_resident: with that one
+ * alone the items on tuple keys keep paths 14 and 16, with this one alone the items on one key keep 13.  It reaches the
+ * tuple-key folds wherever they are issued: the two entry points, the fold route of rhj_query_batch_device by waits, and its
+ * one-wait programs, where a round's items on tuple keys have a resident launch of their own behind their table launches (which
+ * run only if a table item exists); with both switches on, a round whose items are all resident issues no memset and at most
+ * two launches.
+ *
+ * rhj_fold_resident_keys_rule(nR, nS, nvalues), a pure function that needs no device: 1 when an item of these sizes is resident
+ * while the switch is on, else 0.  All of: both sides have rows; 0 <= nvalues <= 9; slots * (1 + nvalues) <= 16 384 u64 words,
+ * slots the table's rule; and the other side has at most 4096 rows (FOLDK_LDS_MAX_ROWS in csrc/rhj_fold_keys_lds.hip.h;
+ * DESIGN.md 6 has the measurement behind it).  The number of key columns does not enter: a slot holds an owner, not a key.
+ *
+ * rhj_table_batch_last_resident_keys_info(): the resident items, the k_foldk_lds and k_foldn_lds launches and the table items of
+ * the two batches on tuple keys.  Reset where rhj_table_batch_last_resident_info() is; all zero with the switch off. */
+void rhj_set_fold_resident_keys(int on);
+int rhj_get_fold_resident_keys(void);    /* the switch as it stands: the default, the environment's value or the last call's */
+int rhj_fold_resident_keys_rule(uint64_t nR, uint64_t nS, int nvalues);
+const rhj_table_batch_resident_info *rhj_table_batch_last_resident_keys_info(void);
 
 /* 1 when the object was created by this library's device-resident side */
 int rhj_resident_relation(const rhj_relation *rel);

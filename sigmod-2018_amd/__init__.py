@@ -50,6 +50,7 @@ INTER_SYMBOLS = [
     "rhj_query_components", "rhj_set_query_products", "rhj_query_batch_last_products_info",
     "rhj_set_fold_combine", "rhj_get_fold_combine", "rhj_table_batch_last_combine_info",
     "rhj_set_fold_resident", "rhj_get_fold_resident", "rhj_fold_resident_rule", "rhj_table_batch_last_resident_info",
+    "rhj_set_fold_resident_keys", "rhj_get_fold_resident_keys", "rhj_fold_resident_keys_rule", "rhj_table_batch_last_resident_keys_info",
 ]
 
 
@@ -640,6 +641,13 @@ def load_library(path=None):
         L.rhj_fold_resident_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
         L.rhj_fold_resident_rule.restype = C.c_int
         L.rhj_table_batch_last_resident_info.restype = C.POINTER(TableBatchResidentInfo)
+    if hasattr(L, "rhj_set_fold_resident_keys"):
+        L.rhj_set_fold_resident_keys.argtypes = [C.c_int]
+        L.rhj_set_fold_resident_keys.restype = None
+        L.rhj_get_fold_resident_keys.restype = C.c_int
+        L.rhj_fold_resident_keys_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
+        L.rhj_fold_resident_keys_rule.restype = C.c_int
+        L.rhj_table_batch_last_resident_keys_info.restype = C.POINTER(TableBatchResidentInfo)
     L.rhj_register_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_unregister_relation_map.argtypes = [C.POINTER(RelationMap), C.c_int]
     L.rhj_bucket_histogram_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -968,14 +976,14 @@ class RHJ:
     def join_foldk_batch_device(self, items, with_info=False):
         """join_fold_batch_device on tuple keys (rhj_join_foldk_batch_device, include/rhj_inter.h): items as there, but colR and
         colS are lists of 1..4 key columns, word t of R against word t of S, all of a side read through its one row-id vector.
-        Path id 14."""
+        Path id 14 (19: one workgroup with the table in LDS, set_fold_resident_keys)."""
         return self._fold_batch(JoinFoldKDesc, "rhj_join_foldk_batch_device", items, with_info)
 
     def join_foldn_batch_device(self, items, with_info=False):
         """join_foldk_batch_device with a row-id vector per key word (rhj_join_foldn_batch_device, include/rhj_inter.h): items as
         there, but selR and selS are lists with one vector or None per key column; word t of a side's position p is
         col[t][sel[t][p]] (col[t][p] without a vector).  A side's positions are the length of its first vector, or of its first
-        column when it has none.  Path id 16."""
+        column when it has none.  Path id 16 (19: one workgroup with the table in LDS, set_fold_resident_keys)."""
         return self._fold_batch(JoinFoldNDesc, "rhj_join_foldn_batch_device", items, with_info)
 
     def set_query_fold_nodes(self, on):
@@ -1191,6 +1199,21 @@ class RHJ:
         """rhj_table_batch_last_resident_info() as a dict: resident_items, resident_launches, table_items (all 0 with
         set_fold_resident off)"""
         return self.lib.rhj_table_batch_last_resident_info().contents.as_dict()
+
+    def set_fold_resident_keys(self, on):
+        """the same for join_foldk_batch_device and join_foldn_batch_device (fold_resident_keys_rule), under a switch of its own
+        (default off): a resident item reports path 19, and every answer is bit for bit the same under both settings"""
+        self.lib.rhj_set_fold_resident_keys(1 if on else 0)
+
+    def fold_resident_keys_rule(self, nR, nS, nvalues):
+        """rhj_fold_resident_keys_rule: whether a tuple-key item of these sizes is resident while set_fold_resident_keys is on (no
+        device needed)"""
+        return bool(self.lib.rhj_fold_resident_keys_rule(int(nR), int(nS), int(nvalues)))
+
+    def table_batch_last_resident_keys_info(self):
+        """rhj_table_batch_last_resident_keys_info() as a dict: resident_items, resident_launches, table_items of the two batches
+        on tuple keys (all 0 with set_fold_resident_keys off)"""
+        return self.lib.rhj_table_batch_last_resident_keys_info().contents.as_dict()
 
     def set_query_fold(self, on):
         """query_batch_device sums the queries whose join predicates form a tree over their bindings by rounds of weighted join

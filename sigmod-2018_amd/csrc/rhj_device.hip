@@ -74,6 +74,8 @@ constexpr uint32_t FUSED_LDS_CAP = (FUSED_LDS - 128) * 2 / 9;                 //
 static_assert(LDS_MAX_SLOTS * 4 / 5 <= 65534 && FUSED_LDS_CAP <= 65534, "LDS-indexed build sides: 16-bit position + 1");
 constexpr uint32_t FOLD_LDS_MAX_BYTES = (uint32_t)(FOLD_LDS_FIXED_WORDS + FOLD_LDS_WORDS) * 8;        // k_fold_lds: the largest resident table and the fixed words
 static_assert(FOLD_LDS_MAX_BYTES <= LDS_BUDGET, "a resident fold's table and its fixed words fit a workgroup's LDS");
+constexpr uint32_t FOLDK_LDS_MAX_BYTES = (uint32_t)(FOLDK_LDS_FIXED_WORDS + FOLD_LDS_WORDS) * 8;      // k_foldk_lds, k_foldn_lds: the same for the folds on tuple keys
+static_assert(FOLDK_LDS_MAX_BYTES <= LDS_BUDGET, "a resident tuple-key fold's table and its fixed words fit a workgroup's LDS");
 constexpr uint32_t BUILD_CHUNK = 4096;            // build tuples per 64-bit-table build unit
 
 enum Stage { ST_HIST, ST_SCAN, ST_SCATTER, ST_PLAN, ST_BUILD, ST_COUNT, ST_OFFSETS, ST_PROBE, ST_END, ST_N };
@@ -178,6 +180,7 @@ uint64_t g_query_fold_one_wait_rows = 4096;              // the most rows of a r
 int g_query_sum_last = 0;            // 1: rhj_query_batch_device takes a query's last join as a rhj_join_sum_batch_device item (rhj_set_query_sum_last, env RHJ_QUERY_SUM_LAST)
 int g_fold_combine = 1;              // 1: the add launches of the four table batches combine a tile's adds to one slot in LDS and send one atomic per (tile, slot, value) (rhj_slot_combine.hip.h; rhj_set_fold_combine, env RHJ_FOLD_COMBINE)
 int g_fold_resident = 0;             // 1: an item of rhj_join_fold_batch_device whose table fits a workgroup's LDS (fold_resident_rule) is folded by one workgroup in one k_fold_lds launch, with no table in the arena (rhj_fold_lds.hip.h; rhj_set_fold_resident, env RHJ_FOLD_RESIDENT)
+int g_fold_resident_keys = 0;        // 1: the same for an item of rhj_join_foldk_batch_device or rhj_join_foldn_batch_device (fold_keys_resident_rule): one workgroup, one k_foldk_lds / k_foldn_lds launch, the table of owners in LDS (rhj_fold_keys_lds.hip.h; rhj_set_fold_resident_keys, env RHJ_FOLD_RESIDENT_KEYS); independent of g_fold_resident
 int g_query_products = 0;            // 1: rhj_query_batch_device takes a query whose bindings end in several nodes (a cross product) as one query per component and multiplies their answers on the host (rhj_set_query_products, env RHJ_QUERY_PRODUCTS)
 
 // environment defaults are read once at load time; the rhj_set_* calls override them
@@ -216,6 +219,7 @@ struct EnvDefaults {
         if ((e = getenv("RHJ_QUERY_PRODUCTS"))) g_query_products = atoi(e) != 0;
         if ((e = getenv("RHJ_FOLD_COMBINE"))) g_fold_combine = atoi(e) != 0;
         if ((e = getenv("RHJ_FOLD_RESIDENT"))) g_fold_resident = atoi(e) != 0;
+        if ((e = getenv("RHJ_FOLD_RESIDENT_KEYS"))) g_fold_resident_keys = atoi(e) != 0;
         if ((e = getenv("RHJ_SMALL_TILES"))) { g.small_tiles = (uint32_t)atoi(e); if (g.small_tiles > SM_MAX_TILES) g.small_tiles = SM_MAX_TILES; }
     }
 } env_defaults;
@@ -298,6 +302,8 @@ int ctx_init()
     HIP_TRY(hipFuncSetAttribute((const void *)k_scatter_runs<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
     HIP_TRY(hipFuncSetAttribute((const void *)k_lr_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lr_lds_bytes(PT_MAX_BITS)));
     HIP_TRY(hipFuncSetAttribute((const void *)k_fold_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLD_LDS_MAX_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_foldk_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLDK_LDS_MAX_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_foldn_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLDK_LDS_MAX_BYTES));
     g.ready = true;
     return 0;
 }
@@ -1381,7 +1387,7 @@ constexpr size_t BATCH_SLOT_WORDS = 16;                   // u64 words of a join
 static_assert(sizeof(PlanSummary) / 8 + 1 <= BATCH_SLOT_WORDS, "a join's pinned slot holds its summary and its walk count");
 
 // what an item's `path` and rhj_stats::reserved say of the batched launches (include/rhj.h, include/rhj_inter.h)
-enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16, PATH_BATCH_FOLD_PRED = 17, PATH_BATCH_JOIN_FOLD_LDS = 18 };
+enum { PATH_BATCH_JOIN = 6, PATH_BATCH_FILTER = 7, PATH_BATCH_APPLY = 8, PATH_BATCH_EQ2 = 9, PATH_QUERY_BATCH = 10, PATH_BATCH_STATS = 11, PATH_BATCH_JOIN_SUM = 12, PATH_BATCH_JOIN_FOLD = 13, PATH_BATCH_JOIN_FOLDK = 14, PATH_BATCH_FOLD_SELF = 15, PATH_BATCH_JOIN_FOLDN = 16, PATH_BATCH_FOLD_PRED = 17, PATH_BATCH_JOIN_FOLD_LDS = 18, PATH_BATCH_JOIN_FOLDK_LDS = 19 };
 
 static int batch_takes(int bits, uint64_t nR, uint64_t nS)
 {
@@ -2209,7 +2215,8 @@ static int stats_batch(rhj_colstats_desc *cols, uint64_t n)
 // copy of its accumulator words and one stream synchronisation; the uploaded block is
 //   [descriptors][items + 1 tile starts of the first launch][of the second][of the third][the indices of the resident items][the
 //   item's accumulator words, zero]
-// (the resident items: those of rhj_join_fold_batch_device that one workgroup folds in LDS with rhj_set_fold_resident on; they have
+// (the resident items: those of the three fold batches that one workgroup folds in LDS with rhj_set_fold_resident, on one key, or
+// rhj_set_fold_resident_keys, on tuple keys, on; they have
 // no table, no tile in the three launches and a launch of their own, and a chunk of them alone has no memset: tbatch_resident below)
 constexpr size_t JSUM_MAX_ITEMS = 4096;
 constexpr uint64_t JSUM_MAX_TILES = 1ull << 24;
@@ -2254,8 +2261,8 @@ static void tbatch_combine_take(const uint32_t (&t)[3], const unsigned long long
 // The resident form of the folds on one key (rhj_fold_lds.hip.h).  With g_fold_resident on, an item that
 // fold_resident_rule names has no table in the arena (tbatch_table_bytes 0), no tile in the three launches (tbatch_fill) and path
 // 18; a chunk's such items are ONE k_fold_lds launch over an index array that is uploaded with the chunk.  The descriptors stay
-// one array in call order, so fbatch_find passes over a resident item as over any item without a tile in a launch.  The other
-// three descriptors have no resident form.  g_resident_info counts, where g_combine_info counts, the resident items, their
+// one array in call order, so fbatch_find passes over a resident item as over any item without a tile in a launch.  The two
+// descriptors on tuple keys have the form under a switch of their own (below); the join sums have none.  g_resident_info counts, where g_combine_info counts, the resident items, their
 // launches and the table items of the fold batches on one key; all zero with the switch off.
 rhj_table_batch_resident_info g_resident_info = {};
 template <class D> static inline bool tbatch_resident(const D &) { return false; }
@@ -2272,6 +2279,30 @@ static void tbatch_launch_resident(const JoinFoldDesc *dd, const uint32_t *d_res
     if (g_fold_resident) { g_resident_info.resident_items += nres; g_resident_info.table_items += (uint32_t)(ni - nres); }
 }
 template <class Dev> static void tbatch_launch_resident(const Dev *, const uint32_t *, uint32_t, size_t, size_t) {}
+// The same for the folds on tuple keys (rhj_fold_keys_lds.hip.h), under a switch of their own,
+// g_fold_resident_keys: an item that fold_keys_resident_rule names has no table in the arena, no tile in the three launches and
+// path 19, and a chunk's such items are ONE k_foldk_lds or k_foldn_lds launch.  g_resident_keys_info counts for the two tuple-key
+// batches what g_resident_info counts for the batch on one key, and is reset where it is; all zero with the switch off.
+rhj_table_batch_resident_info g_resident_keys_info = {};
+static inline bool tbatch_resident(const rhj_join_foldk_desc &q) { return g_fold_resident_keys && fold_keys_resident_rule(q.nR, q.nS, q.nvalues); }
+static inline bool tbatch_resident(const rhj_join_foldn_desc &q) { return g_fold_resident_keys && fold_keys_resident_rule(q.nR, q.nS, q.nvalues); }
+static inline size_t tbatch_resident_lds(const rhj_join_foldk_desc &q) { return fold_keys_lds_bytes(q.nR, q.nS, q.nvalues); }
+static inline size_t tbatch_resident_lds(const rhj_join_foldn_desc &q) { return fold_keys_lds_bytes(q.nR, q.nS, q.nvalues); }
+static inline void tbatch_resident_keys_count(uint32_t nres, size_t ni)
+{
+    g_resident_keys_info.resident_launches += nres != 0;
+    if (g_fold_resident_keys) { g_resident_keys_info.resident_items += nres; g_resident_keys_info.table_items += (uint32_t)(ni - nres); }
+}
+static void tbatch_launch_resident(const JoinFoldKDesc *dd, const uint32_t *d_res, uint32_t nres, size_t lds, size_t ni)
+{
+    if (nres) RHJ_LAUNCH(k_foldk_lds, dim3(nres), dim3(256), lds, g.stream, dd, d_res);
+    tbatch_resident_keys_count(nres, ni);
+}
+static void tbatch_launch_resident(const JoinFoldNDesc *dd, const uint32_t *d_res, uint32_t nres, size_t lds, size_t ni)
+{
+    if (nres) RHJ_LAUNCH(k_foldn_lds, dim3(nres), dim3(256), lds, g.stream, dd, d_res);
+    tbatch_resident_keys_count(nres, ni);
+}
 
 static bool tbatch_valid(const rhj_join_sum_desc &q)
 {
@@ -2310,8 +2341,8 @@ static void tbatch_zero(rhj_join_foldn_desc &q) { for (int o = 0; o < q.nouts; +
 
 static inline uint64_t tbatch_table_bytes(const rhj_join_sum_desc &q) { return tbatch_slots(q) * JSUM_SLOT_BYTES; }
 static inline uint64_t tbatch_table_bytes(const rhj_join_fold_desc &q) { return tbatch_resident(q) ? 0 : tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }    // (a resident item's table is in LDS)
-static inline uint64_t tbatch_table_bytes(const rhj_join_foldk_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
-static inline uint64_t tbatch_table_bytes(const rhj_join_foldn_desc &q) { return tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_foldk_desc &q) { return tbatch_resident(q) ? 0 : tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
+static inline uint64_t tbatch_table_bytes(const rhj_join_foldn_desc &q) { return tbatch_resident(q) ? 0 : tbatch_slots(q) * (uint64_t)(1 + q.nvalues) * 8; }
 
 // the fields both device descriptors have
 template <class D, class Dev>
@@ -2372,6 +2403,12 @@ static void tbatch_fill(const rhj_join_foldk_desc &q, unsigned long long *table,
     d.table = table; d.words = words;
     d.nkeys = q.nkeys;
     d.combine = g_fold_combine;
+    if (tbatch_resident(q)) {                            // no table in the arena and no tile in the three launches: the LDS kernel takes the item
+        uint32_t none[3] = {0, 0, 0};
+        d.table = nullptr;
+        tbatch_fill_fold(q, d, none);
+        return;
+    }
     tbatch_fill_fold(q, d, t);
 }
 static void tbatch_fill(const rhj_join_foldn_desc &q, unsigned long long *table, unsigned long long *words, JoinFoldNDesc &d, uint32_t (&t)[3])
@@ -2387,6 +2424,12 @@ static void tbatch_fill(const rhj_join_foldn_desc &q, unsigned long long *table,
     d.table = table; d.words = words;
     d.nkeys = q.nkeys;
     d.combine = g_fold_combine;
+    if (tbatch_resident(q)) {                            // no table in the arena and no tile in the three launches: the LDS kernel takes the item
+        uint32_t none[3] = {0, 0, 0};
+        d.table = nullptr;
+        tbatch_fill_fold(q, d, none);
+        return;
+    }
     tbatch_fill_fold(q, d, t);
 }
 
@@ -2429,7 +2472,9 @@ static inline int tbatch_path(const rhj_join_fold_desc &) { return PATH_BATCH_JO
 static inline int tbatch_path(const rhj_join_foldk_desc &) { return PATH_BATCH_JOIN_FOLDK; }
 static inline int tbatch_path(const rhj_join_foldn_desc &) { return PATH_BATCH_JOIN_FOLDN; }
 // what an item reports; tbatch_path is what the call does (rhj_last_stats().reserved)
-template <class D> static inline int tbatch_item_path(const D &q) { return tbatch_resident(q) ? PATH_BATCH_JOIN_FOLD_LDS : tbatch_path(q); }
+static inline int tbatch_resident_path(const rhj_join_fold_desc &) { return PATH_BATCH_JOIN_FOLD_LDS; }
+template <class D> static inline int tbatch_resident_path(const D &) { return PATH_BATCH_JOIN_FOLDK_LDS; }             // (the two on tuple keys; the join sums are never resident)
+template <class D> static inline int tbatch_item_path(const D &q) { return tbatch_resident(q) ? tbatch_resident_path(q) : tbatch_path(q); }
 static inline const char *tbatch_noun(const rhj_join_sum_desc &) { return "join sums"; }
 static inline const char *tbatch_noun(const rhj_join_fold_desc &) { return "join folds"; }
 static inline const char *tbatch_noun(const rhj_join_foldk_desc &) { return "join folds on tuple keys"; }
@@ -3713,11 +3758,12 @@ static int ow_run(QueryRun &R, OwProgram &P)
         for (rhj_join_fold_desc &d : rd.fd) ow_fix_fold(d, base);
         for (rhj_join_foldk_desc &d : rd.kd) ow_fix_fold(d, base);
     }
-    struct RoundPieces { JoinFoldDesc *hf, *df; JoinFoldKDesc *hk, *dk; uint32_t *ts[2][3], *d_ts[2][3]; uint32_t t[2][3]; uint32_t *res, *d_res; size_t nres, res_lds; };
+    struct RoundPieces { JoinFoldDesc *hf, *df; JoinFoldKDesc *hk, *dk; uint32_t *ts[2][3], *d_ts[2][3]; uint32_t t[2][3]; uint32_t *res[2], *d_res[2]; size_t nres[2], res_lds[2]; };
     std::vector<RoundPieces> rp(nr);
     for (size_t r = 0; r < nr; ++r) {
-        rp[r].nres = 0;
-        for (const rhj_join_fold_desc &d : P.rounds[r].fd) rp[r].nres += tbatch_resident(d);
+        rp[r].nres[0] = rp[r].nres[1] = 0;               // (by kind: the folds on one key, rhj_set_fold_resident, and on tuples, rhj_set_fold_resident_keys)
+        for (const rhj_join_fold_desc &d : P.rounds[r].fd) rp[r].nres[0] += tbatch_resident(d);
+        for (const rhj_join_foldk_desc &d : P.rounds[r].kd) rp[r].nres[1] += tbatch_resident(d);
     }
     Block blk;
     unsigned long long *back, *words, *d_words; FoldPredDesc *hp, *dp; uint32_t *ptile, *d_ptile;
@@ -3728,9 +3774,10 @@ static int ow_run(QueryRun &R, OwProgram &P)
             const size_t nf = P.rounds[r].fd.size(), nk = P.rounds[r].kd.size();
             b.up(rp[r].hf, rp[r].df, nf);
             for (int j = 0; j < 3; ++j) b.up(rp[r].ts[0][j], rp[r].d_ts[0][j], nf + 1);
-            b.up(rp[r].res, rp[r].d_res, rp[r].nres);
+            b.up(rp[r].res[0], rp[r].d_res[0], rp[r].nres[0]);
             b.up(rp[r].hk, rp[r].dk, nk);
             for (int j = 0; j < 3; ++j) b.up(rp[r].ts[1][j], rp[r].d_ts[1][j], nk + 1);
+            b.up(rp[r].res[1], rp[r].d_res[1], rp[r].nres[1]);
         }
         b.up(words, d_words, nwords);
     };
@@ -3751,10 +3798,9 @@ static int ow_run(QueryRun &R, OwProgram &P)
     for (size_t r = 0; r < nr; ++r) {
         size_t at = 0;
         wfold[r] = wat;
-        size_t none;
-        ow_fill(P.rounds[r].fd, rp[r].hf, rp[r].ts[0], rp[r].t[0], at, d_words, wat, rp[r].res, rp[r].res_lds);
+        ow_fill(P.rounds[r].fd, rp[r].hf, rp[r].ts[0], rp[r].t[0], at, d_words, wat, rp[r].res[0], rp[r].res_lds[0]);
         wfoldk[r] = wat;
-        ow_fill(P.rounds[r].kd, rp[r].hk, rp[r].ts[1], rp[r].t[1], at, d_words, wat, nullptr, none);
+        ow_fill(P.rounds[r].kd, rp[r].hk, rp[r].ts[1], rp[r].t[1], at, d_words, wat, rp[r].res[1], rp[r].res_lds[1]);
         if (at != (size_t)P.rounds[r].bytes || at > g.jsum_arena.cap) { fprintf(stderr, "rhj: the tables of a round of a fold program were placed beyond its arena\n"); return -1; }
     }
     if (wat != nwords) { fprintf(stderr, "rhj: a fold program's words were miscounted\n"); return -1; }
@@ -3768,23 +3814,28 @@ static int ow_run(QueryRun &R, OwProgram &P)
         const OwRound &rd = P.rounds[r];
         if (rd.fd.empty() && rd.kd.empty()) continue;
         // the arena's tables of the round before are dead: stream order puts this memset behind their last reader
-        // (a round whose items are all resident, rhj_set_fold_resident, has no table: no memset, and one launch)
+        // (a round whose items are all resident, rhj_set_fold_resident and rhj_set_fold_resident_keys, has no table: no memset, and
+        // one launch a kind)
         if (rd.bytes) {
             HIP_TRY(hipMemsetAsync(g.jsum_arena.p, 0, (size_t)rd.bytes, g.stream));
             ++info.memsets;
         }
         ++info.rounds;
-        if (rp[r].nres < rd.fd.size()) {
+        if (rp[r].nres[0] < rd.fd.size()) {
             tbatch_launch(rd.fd[0], rp[r].df, (uint32_t)rd.fd.size(), rp[r].d_ts[0], rp[r].t[0]);
             info.launches += 2 + (rp[r].t[0][0] != 0);
         }
         if (!rd.fd.empty()) {
-            tbatch_launch_resident(rp[r].df, rp[r].d_res, (uint32_t)rp[r].nres, rp[r].res_lds, rd.fd.size());
-            info.launches += rp[r].nres != 0;
+            tbatch_launch_resident(rp[r].df, rp[r].d_res[0], (uint32_t)rp[r].nres[0], rp[r].res_lds[0], rd.fd.size());
+            info.launches += rp[r].nres[0] != 0;
         }
-        if (!rd.kd.empty()) {
+        if (rp[r].nres[1] < rd.kd.size()) {
             tbatch_launch(rd.kd[0], rp[r].dk, (uint32_t)rd.kd.size(), rp[r].d_ts[1], rp[r].t[1]);
             info.launches += 2 + (rp[r].t[1][0] != 0);
+        }
+        if (!rd.kd.empty()) {
+            tbatch_launch_resident(rp[r].dk, rp[r].d_res[1], (uint32_t)rp[r].nres[1], rp[r].res_lds[1], rd.kd.size());
+            info.launches += rp[r].nres[1] != 0;
         }
         info.fold_items += (uint32_t)rd.fd.size(); info.foldk_items += (uint32_t)rd.kd.size();
     }
@@ -4609,7 +4660,7 @@ const rhj_colstats_batch_info *rhj_column_stats_batch_last_info(void) { return &
 int rhj_query_batch_device(const rhj_device_relation *rels, int nrel, rhj_query_desc *queries, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {}; g_resident_info = {};
+    g_combine_info = {}; g_resident_info = {}; g_resident_keys_info = {};
     return g_query_products ? query_products(rels, nrel, queries, n) : query_batch(rels, nrel, queries, n);
 }
 void rhj_set_fold_combine(int on) { RhjApiLock api_lock; g_fold_combine = on != 0; }
@@ -4619,6 +4670,10 @@ void rhj_set_fold_resident(int on) { RhjApiLock api_lock; g_fold_resident = on !
 int rhj_get_fold_resident(void) { return g_fold_resident; }
 int rhj_fold_resident_rule(uint64_t nR, uint64_t nS, int nvalues) { return fold_resident_rule(nR, nS, nvalues); }
 const rhj_table_batch_resident_info *rhj_table_batch_last_resident_info(void) { return &g_resident_info; }
+void rhj_set_fold_resident_keys(int on) { RhjApiLock api_lock; g_fold_resident_keys = on != 0; }
+int rhj_get_fold_resident_keys(void) { return g_fold_resident_keys; }
+int rhj_fold_resident_keys_rule(uint64_t nR, uint64_t nS, int nvalues) { return fold_keys_resident_rule(nR, nS, nvalues); }
+const rhj_table_batch_resident_info *rhj_table_batch_last_resident_keys_info(void) { return &g_resident_keys_info; }
 int rhj_query_components(const rhj_query_desc *q, int nrel, const rhj_device_relation *rels, int *comp) { return query_components(q, nrel, rels, comp); }
 void rhj_set_query_products(int on) { RhjApiLock api_lock; g_query_products = on != 0; }
 const rhj_query_batch_products_info *rhj_query_batch_last_products_info(void) { return &g_query_products_info; }
@@ -4647,28 +4702,28 @@ int rhj_query_fold_plan(const rhj_query_desc *q, int nrel, const rhj_device_rela
 int rhj_join_sum_batch_device(rhj_join_sum_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {}; g_resident_info = {};
+    g_combine_info = {}; g_resident_info = {}; g_resident_keys_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldk_batch_device(rhj_join_foldk_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {}; g_resident_info = {};
+    g_combine_info = {}; g_resident_info = {}; g_resident_keys_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_foldn_batch_device(rhj_join_foldn_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {}; g_resident_info = {};
+    g_combine_info = {}; g_resident_info = {}; g_resident_keys_info = {};
     return table_batch(items, n);
 }
 
 int rhj_join_fold_batch_device(rhj_join_fold_desc *items, uint64_t n)
 {
     RhjApiLock api_lock;
-    g_combine_info = {}; g_resident_info = {};
+    g_combine_info = {}; g_resident_info = {}; g_resident_keys_info = {};
     return table_batch(items, n);
 }
 

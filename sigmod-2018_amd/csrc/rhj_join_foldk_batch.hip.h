@@ -127,9 +127,10 @@ __device__ __forceinline__ bool foldk_owner_is(const FoldKSide &build, int nkeys
 }
 
 // foldk_find: the slot whose owner carries `mine`, or JSUM_NONE when the table has none: at most `slots` steps.  (Side: FoldKSide,
-// or rhj_join_foldn_batch.hip.h's side with a row-id vector per word; the table protocol is stated here once for both.)
-template <class Side>
-__device__ __forceinline__ uint64_t foldk_find(jsum_gull table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
+// or rhj_join_foldn_batch.hip.h's side with a row-id vector per word; the table protocol is stated here once for both.  Table:
+// jsum_gull, a table in the arena, or jsum_lull, one in LDS, rhj_fold_keys_lds.hip.h, whose claims are atomics of SCOPE workgroup.)
+template <class Table, class Side>
+__device__ __forceinline__ uint64_t foldk_find(Table table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
                                                const uint64_t (&mine)[RHJ_FOLD_MAX_KEYS])
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
@@ -146,8 +147,8 @@ __device__ __forceinline__ uint64_t foldk_find(jsum_gull table, uint32_t sw, uin
 
 // foldk_claim: the slot of the tuple `mine` of the build side's row at position `pos`, found or claimed, at most `slots` steps (a
 // free slot is always met: at most half are taken); JSUM_NONE only if the table were full
-template <class Side>
-__device__ __forceinline__ uint64_t foldk_claim(jsum_gull table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
+template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT, class Table, class Side>
+__device__ __forceinline__ uint64_t foldk_claim(Table table, uint32_t sw, uint32_t log2_slots, const Side &build, int nkeys,
                                                 const uint64_t (&mine)[RHJ_FOLD_MAX_KEYS], uint64_t pos)
 {
     const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
@@ -156,10 +157,10 @@ __device__ __forceinline__ uint64_t foldk_claim(jsum_gull table, uint32_t sw, ui
     const unsigned long long me = ((unsigned long long)tag << 32) | (unsigned long long)(pos + 1);
     uint64_t s = foldk_home(h, log2_slots);
     for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long seen = __hip_atomic_load(&table[sw * s], __ATOMIC_RELAXED, SCOPE);
         if (seen == 0) {
             // one exchange; on failure `seen` is the owner word somebody else put there, which stays
-            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return s;
+            if (__hip_atomic_compare_exchange_strong(&table[sw * s], &seen, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE)) return s;
         }
         if ((uint32_t)(seen >> 32) == tag && foldk_owner_is(build, nkeys, (uint32_t)seen - 1u, mine)) return s;
     }

@@ -54,6 +54,8 @@
 //                          and equality is decided on that row's words, gathered from the build side's own columns.
 //   rhj_join_foldn_batch.hip.h the tuple-key folds with a row-id vector per key word: the keys of a materialised node, whose
 //                          words belong to different member bindings.
+//   rhj_fold_keys_lds.hip.h the tuple-key folds of both files for an item whose table of owners fits a workgroup's LDS: one
+//                          workgroup, one launch, owners' words still gathered from memory (rhj_set_fold_resident_keys).
 //   rhj_fold_self_batch.hip.h many folds with no child in one launch: the equalities between two columns of one side as a 0/1
 //                          factor on its weights, and the sums of a query without a join.
 //   rhj_fold_pred_batch.hip.h the same with comparisons against constants in the mask: a filter as a 0/1 factor on a side's
@@ -84,6 +86,7 @@
 #include "rhj_fold_lds.hip.h"
 #include "rhj_join_foldk_batch.hip.h"
 #include "rhj_join_foldn_batch.hip.h"
+#include "rhj_fold_keys_lds.hip.h"
 #include "rhj_fold_self_batch.hip.h"
 #include "rhj_fold_pred_batch.hip.h"
 #include "rhj_diag.hip.h"
